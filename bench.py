@@ -9,8 +9,15 @@ on the backbone's point features, boxes decoded; NMS post-processing is not part
 inference (BN in eval mode), the configuration BASELINE.json's metric is quoted on (configs[2]): bs = 32
 clouds of 16384 points per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (frames/s, ms_per_step).  --full adds
+everything else this script measures or checks after the timed steps: the bit-equality check of the timed step
+against the serial detector, the per-kernel and in-situ passes with their roofline blocks, the API-exact
+ball_query + group_points section, the PDM neck's two forms, the copy bandwidth, the extra configurations (training
+step, lidar-like clouds, configs[4], bs = 8, split-bf16 point head; --no-extras drops them) and the CPU baselines
+(--no-cpu-baseline drops them).  --dump-outputs DIR writes the four outputs of the last timed step as DIR/<name>.npy.
 
 Multi-GPU = pure data parallel over whole clouds (weak scaling, 32 clouds per rank, no data-path
 collective; only the timing barriers).  Rank 0 prints ONE JSON line.  Started as plain `python bench.py
@@ -938,7 +945,16 @@ def main():
                          "single-thread CPU leg, median over 50 steps)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch + barrier + max-over-ranks protocol only, no kernels (launch diagnostic / CPU test)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check of the line: verification against "
+                         "the serial detector, per-kernel / in-situ passes and roofline blocks, API-exact operator section, "
+                         "PDM neck forms, copy bandwidth, extras (unless --no-extras), CPU baselines (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; outputs larger than their "
+                         "share of 64 MB as a fixed, seeded sample of their elements)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher BEFORE any torch.cuda / HIP call in this process
@@ -980,29 +996,35 @@ def main():
         _, points = make_batch(B, N, args.clouds, 1234 + rank * B, device)
         line = train_bench(args, model, points, B, N, rank, world, local_rank, device, scaling=scaling)
         if rank == 0 and line is not None:
+            if args.dump_outputs:     # what the timed train step returns to its caller: the loss of the last step
+                line["outputs_dumped"] = dump_outputs(args.dump_outputs, {"loss": torch.tensor([line["final_loss"]], dtype=torch.float64)})
             print(json.dumps(line))
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         return
-    backbone, neck = model.backbone_3d, model.map_to_bev_module
 
     bench = Bench(model, B, N, args.clouds, args.pipeline_depth, device, seed0=1234 + rank * B, serial=args.serial,
                   graph=not args.no_graph, autotune=not args.no_autotune)
     elapsed = bench.timed(args.steps, args.warmup, barrier=dist_utils.barrier)
     elapsed = dist_utils.max_over_ranks(elapsed, device)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else runs the step again
+        dumped = dump_outputs(args.dump_outputs, dict(zip(Bench.OUTPUTS, bench.outputs())))
     LAUNCH_MODE[0] = bench.mode
     LAUNCH_MODE[1] = None if bench.hoisting is None else [d["use_pre"] for d in bench.hoisting]
     if not args.serial:
         bench.pipe.check_sampling()   # N > 16384: no cooperating FPS workgroup gave up waiting for a peer
-    # untimed: the timed object (rotation + pipelined step under graph replay) against the serial detector, on every rank
-    try:
-        verified = bench.verify(2)
-    except AssertionError as e:
-        print(f"[bench] rank {rank}: VERIFICATION FAILED: {e}", file=sys.stderr, flush=True)
-        if world > 1:
-            dist.destroy_process_group()
-        sys.exit(3)
+    verified = None
+    if args.full:
+        # untimed: the timed object (rotation + pipelined step under graph replay) against the serial detector, on every rank
+        try:
+            verified = bench.verify(2)
+        except AssertionError as e:
+            print(f"[bench] rank {rank}: VERIFICATION FAILED: {e}", file=sys.stderr, flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+            sys.exit(3)
 
     if rank != 0:
         if world > 1:
@@ -1010,8 +1032,76 @@ def main():
             dist.destroy_process_group()
         return
 
-    ms_per_step = elapsed / args.steps * 1e3
-    frames_per_s = world * B * args.steps / elapsed
+    line = headline(args, B, N, world, scaling, elapsed)
+    if dumped is not None:
+        line["outputs_dumped"] = dumped
+    if args.full:
+        held = [bench]    # full_report takes the only reference: its `del bench` frees the graph and pools before the extras
+        del bench
+        full_report(line, args, model, held, B, N, world, rank, local_rank, device, verified)
+    print(json.dumps(line))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def headline(args, B, N, world, scaling, elapsed):
+    """The line of a plain run: frames/s and ms per step of the timed steps, and what was timed."""
+    return {
+        "metric": f"frames/sec ({N}-pt clouds, bs={B})", "value": round(world * B * args.steps / elapsed, 2), "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"configs[2]: full PDM-SSD forward (PointNet2MSG backbone + PDM neck + hybrid head: BEV heat-map "
+                               f"head + point box head with decoded boxes), bs={B}/GPU x {N} pts, {args.clouds} KITTI-range clouds, "
+                               f"fp32 inference, inputs resident in HBM, {Bench.NBATCH} distinct batches in rotation",
+                   "launch": LAUNCH_MODE[0], "parallelism": f"dp{world}", "global_batch": world * B,
+                   "overlap": "none" if args.serial else
+                              ("FPS chain of batch i+1 on a side stream under the feature half of batch i "
+                               "(pdm_ssd_amd/pipeline.py)" if args.pipeline_depth == 1 else
+                               f"level-1 FPS cut into {args.pipeline_depth - 1} resumable segments: one launch per step runs "
+                               f"segment s of batch i+{args.pipeline_depth}-s side by side, the rest of batch i+1's coordinate "
+                               "chain on a third stream, under the feature half of batch i (heat-map head behind the neck on "
+                               "the neck's stream, point head behind the FP layers); every step does one full batch of every "
+                               "kind of work (pdm_ssd_amd/pipeline.py)" if args.pipeline_depth >= 3 else
+                               "sampling two batches deep: level-1 FPS of batch i+2 and levels 2-4 of batch i+1 on side "
+                               "streams under the feature half of batch i; every step does one full batch of every "
+                               "kind of work (pdm_ssd_amd/pipeline.py)"),
+                   "sa_first_layer_hoisted": LAUNCH_MODE[1]},
+    }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every output as `path`/<name>.npy, float32 (float64 stays float64), so that two builds can be
+    compared output for output.  An output larger than its share of `limit` is written as a fixed sample instead: the
+    elements at the sorted flat indices np.unique(default_rng(k).integers(0, numel, share)), k = the output's position —
+    the same elements in every run with the same arguments.  Returns {name: shape, elements written} for the line."""
+    os.makedirs(path, exist_ok=True)
+    share = (limit - 4096 * len(outputs)) // len(outputs)      # (.npy headers: 128 bytes each)
+    out = {}
+    for k, (name, t) in enumerate(outputs.items()):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        flat = t.reshape(-1)
+        cap = share // (8 if dt == torch.float64 else 4)
+        if flat.numel() > cap:
+            idx = np.unique(np.random.default_rng(k).integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.to(dt).cpu().numpy()
+            out[name] = {"shape": list(t.shape), "written": f"sample of {arr.size} elements (seed {k})"}
+        else:
+            arr = t.to(dt).cpu().numpy()
+            out[name] = {"shape": list(t.shape), "written": "all"}
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return out
+
+
+def full_report(line, args, model, held, B, N, world, rank, local_rank, device, verified):
+    """--full: every measurement of the line beyond the timed steps, added to `line`.  `held` = [the timed Bench]."""
+    bench = held.pop()
+    backbone, neck = model.backbone_3d, model.map_to_bev_module
     extras = {}
     if not args.no_extras:
         med, lo, hi = bench.median_ms(max(50, args.steps))
@@ -1308,29 +1398,9 @@ def main():
                     extras["split_bf16_chain"] = split_bf16_section(model, B, N, args, device)
             except Exception as e:
                 extras["split_bf16_chain"] = {"error": f"{type(e).__name__}: {e}"}
-    # rebuilt if deleted above: only its attributes are needed for the line
-    line = {
-        "metric": f"frames/sec ({N}-pt clouds, bs={B})", "value": round(frames_per_s, 2), "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"configs[2]: full PDM-SSD forward (PointNet2MSG backbone + PDM neck + hybrid head: BEV heat-map "
-                               f"head + point box head with decoded boxes), bs={B}/GPU x {N} pts, {args.clouds} KITTI-range clouds, "
-                               f"fp32 inference, inputs resident in HBM, {Bench.NBATCH} distinct batches in rotation",
-                   "launch": LAUNCH_MODE[0], "parallelism": f"dp{world}", "global_batch": world * B,
-                   "overlap": "none" if args.serial else
-                              ("FPS chain of batch i+1 on a side stream under the feature half of batch i "
-                               "(pdm_ssd_amd/pipeline.py)" if args.pipeline_depth == 1 else
-                               f"level-1 FPS cut into {args.pipeline_depth - 1} resumable segments: one launch per step runs "
-                               f"segment s of batch i+{args.pipeline_depth}-s side by side, the rest of batch i+1's coordinate "
-                               "chain on a third stream, under the feature half of batch i (heat-map head behind the neck on "
-                               "the neck's stream, point head behind the FP layers); every step does one full batch of every "
-                               "kind of work (pdm_ssd_amd/pipeline.py)" if args.pipeline_depth >= 3 else
-                               "sampling two batches deep: level-1 FPS of batch i+2 and levels 2-4 of batch i+1 on side "
-                               "streams under the feature half of batch i; every step does one full batch of every "
-                               "kind of work (pdm_ssd_amd/pipeline.py)"),
-                   "ms_per_step_eager_serial": round(serial_ms, 4),
-                   "verified": verified,
-                   "sa_first_layer_hoisted": LAUNCH_MODE[1]},
+    line["config"]["ms_per_step_eager_serial"] = round(serial_ms, 4)
+    line["config"]["verified"] = verified
+    line.update({
         "roofline": roofline,
         "roofline_fps": roofline_fps,
         "roofline_mfma": roofline_mfma,
@@ -1348,11 +1418,7 @@ def main():
         "extras": extras,
         "cpu_baseline": cpu,
         "cpu_baseline_single_thread": cpu1,
-    }
-    print(json.dumps(line))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    })
 
 
 LAUNCH_MODE = [None, None]

@@ -69,6 +69,8 @@ def _run_bench(*argv, timeout=240):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    # the launcher's CPU behaviour (gloo ranks) on any box: a visible GPU would make the ranks pick RCCL, one GPU per rank
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     return subprocess.run([sys.executable, os.path.join(root, "bench.py")] + list(argv), env=env, capture_output=True,
                           text=True, timeout=timeout)
 

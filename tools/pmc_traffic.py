@@ -4,9 +4,9 @@
 Collection (separate passes, --kernel-trace only; MI355X_MICROARCH.md "HBM" / "rocprofv3" sections):
     cd /tmp && export TMPDIR=/tmp
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o run -- \
-        python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --serial
+        python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --serial
     rocprofv3 --pmc WRITE_SIZE TCC_EA0_ATOMIC_sum --kernel-trace --output-format csv -d $OUT/pmc_write -o run -- \
-        python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --serial
+        python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --serial
     python tools/pmc_traffic.py $OUT/pmc_fetch $OUT/pmc_write profiles/rNN_pmc_traffic.json [command] [batch points clouds]
 bench.py attaches the file's numbers to a run only when batch / points / clouds match (default 32 16384 uniform).
 

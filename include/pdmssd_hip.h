@@ -517,6 +517,28 @@ int pdm_boxes_aligned_overlap_bev(void *stream, int n, const float *boxes_a, con
 size_t pdm_nms_workspace_bytes(int n);
 int pdm_nms(void *stream, int n, const float *boxes, float thresh, int normal, void *workspace,
             size_t workspace_bytes, long long *keep, int *num_out);
+/* Batched detector post-processing (post_process.hip; Detector3DTemplate.post_processing with
+ * POST_PROCESSING.BATCHED): for all B samples at once, score threshold, the first pre_max candidates in
+ * pdm_topk_sampling's order (score descending, equal scores by lower row), NMS as pdm_nms (bit-identical keep lists),
+ * the first post_max survivors.  multi_class = 0: one segment per sample, score = max over the C columns (lowest
+ * class wins a tie), label = argmax + 1.  multi_class = 1 (C <= 64): one segment per (sample, class k), score =
+ * cls[:, k], label = k + 1, a sample's survivors class after class.  cls (rows, C) probabilities with row stride
+ * cls_stride, boxes (rows, >= 7) with row stride box_stride; offsets (B + 1) int32 DEVICE rows of each sample;
+ * batch_index (rows) float or NULL: when given, a row outside its sample's range or of another sample sets *err_flag.
+ * Outputs (P = post_max, or C * post_max in multi-class mode), every entry written: out_rows (B, P) int64 row within
+ * the sample (-1 padding), out_boxes (B, P, 7), out_scores (B, P), out_labels (B, P) int64, out_count (B) int32.
+ * gt (B, G, gt_dim >= 7) or NULL: recall (1 + num_thresh) int64 = [gt rows, kept-box recall at each threshold]
+ * summed over the batch (generate_recall_record: trailing all-zero gt rows trimmed, 3-D IoU max over the kept boxes
+ * > threshold); recall_thresh is a HOST array of num_thresh <= 8 floats.  pre_max <= 16384, G <= 4096, B * segments
+ * <= 65535; workspace >= pdm_post_process_workspace_bytes(segments, pre_max, post_max), of which the NMS mask is
+ * segments * pre_max * ceil(pre_max / 64) * 8 bytes.  Nothing synchronises; counts, flag and recall stay on the device. */
+size_t pdm_post_process_workspace_bytes(int num_segments, int pre_max, int post_max);
+int pdm_post_process(void *stream, int B, int C, int multi_class, long long rows, const float *cls, int cls_stride,
+                     const float *boxes, int box_stride, const int *offsets, const float *batch_index, float score_thresh,
+                     int pre_max, int post_max, float nms_thresh, int nms_normal, int G, int gt_dim, const float *gt,
+                     int num_thresh, const float *recall_thresh, void *workspace, size_t workspace_bytes, long long *out_rows,
+                     float *out_boxes, float *out_scores, long long *out_labels, int *out_count, int *err_flag,
+                     long long *recall);
 /* roiaware_pool3d's points_in_boxes_gpu (roiaware_pool3d.cpp / roiaware_pool3d_kernel.cu:313-336): boxes (B,T,7),
  * pts (B,M,3) -> box_idx (B,M) = first containing box of the sample's list, -1 for background (every entry written). */
 int pdm_points_in_boxes(void *stream, int B, int T, int M, const float *boxes, const float *pts, int *box_idx);

@@ -7,40 +7,9 @@
 //   idx[b, r] = index of the r-th ranked point, r = 0 .. k-1.
 // One workgroup per cloud: 4 rounds of 8-bit radix select find the k-th key, the chosen points are emitted in index
 // order (ties with the k-th key by lowest index) and bitonic-sorted in LDS as 8-byte (key, index) items.
-#include "common.h"
+#include "rank_select.h"
 
 namespace pdm {
-
-constexpr int TK_THREADS = 1024;
-constexpr int TK_MAXK = 16384;   // 128 KB of 8-byte items
-
-// smaller key = higher rank
-__device__ __host__ __forceinline__ unsigned topk_key(unsigned bits) {
-    if ((bits & 0x7fffffffu) > 0x7f800000u) return 0u;                     // NaN: ranks first
-    const unsigned mono = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);   // ascending with the float order
-    return ~mono;
-}
-
-__device__ __forceinline__ int tk_block_scan(int v, int *s_wave, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < TK_THREADS / 64; ++w) {
-        const int x = s_wave[w];
-        if (w < wave) base += x;
-        tot += x;
-    }
-    *total = tot;
-    return base + incl - v;
-}
 
 __global__ __launch_bounds__(TK_THREADS) void topk_sampling_kernel(int N, int K, const float *__restrict__ scores,
                                                                   int *__restrict__ idx_out) {

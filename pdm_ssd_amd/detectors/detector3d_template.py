@@ -127,12 +127,49 @@ class Detector3DTemplate(nn.Module):
 
     def post_processing(self, batch_dict):
         """batch_cls_preds (N1 + N2 + ..., num_class | 1) logits, batch_box_preds (.., 7), batch_index (..) ->
-        [{'pred_boxes', 'pred_scores', 'pred_labels'}] per sample: sigmoid, arg-max class, score threshold, top
-        NMS_PRE_MAXSIZE, rotated NMS (HIP kernels of iou3d_nms.hip), first NMS_POST_MAXSIZE (ref :178-263, the
-        single-class-NMS branch the point heads use)."""
+        ([{'pred_boxes', 'pred_scores', 'pred_labels'}] per sample, recall_dict) as the reference (ref :178-263).
+
+        The default is the reference's per-sample loop.  POST_PROCESSING.BATCHED (absent = False) runs the whole batch
+        through pdm_post_process on the device (post_process.py) with identical results; it falls back to the loop,
+        with a one-time warning, for a list of cls_preds, has_class_labels, rois, NMS_PRE_MAXSIZE > 16384,
+        NMS_THRESH < 0 or a batch_index that is not sample-major."""
+        cfg = _get(self.model_cfg, 'POST_PROCESSING')
+        if _get(cfg, 'BATCHED', False):
+            from .. import post_process
+            nms_cfg = _get(cfg, 'NMS_CONFIG')
+            reason = None
+            if isinstance(batch_dict['batch_cls_preds'], list):
+                reason = 'a list of cls_preds'
+            elif batch_dict.get('has_class_labels', False):
+                reason = 'has_class_labels'
+            elif 'rois' in batch_dict:
+                reason = 'rois'
+            elif int(_get(nms_cfg, 'NMS_PRE_MAXSIZE')) > post_process.MAX_PRE:
+                reason = f'NMS_PRE_MAXSIZE > {post_process.MAX_PRE}'
+            elif float(_get(nms_cfg, 'NMS_THRESH')) < 0:
+                reason = 'NMS_THRESH < 0'
+            if reason is None:
+                out = post_process.batched_post_processing(batch_dict, cfg, self.num_class,
+                                                           gt_boxes=batch_dict.get('gt_boxes', None))
+                if out is not None:
+                    return out
+                reason = 'batch_index is not sample-major'
+            post_process.warn_once(reason)
+        return self.post_processing_loop(batch_dict)
+
+    def post_processing_loop(self, batch_dict):
+        """The reference's per-sample loop (ref :178-263): sigmoid, then either
+        - class-agnostic NMS: arg-max class, score threshold, top NMS_PRE_MAXSIZE, rotated NMS (HIP kernels of
+          iou3d_nms.hip), first NMS_POST_MAXSIZE; OUTPUT_RAW_SCORE reports the raw maximum instead; or
+        - MULTI_CLASSES_NMS: the same per class column (iou3d_nms_utils.multi_classes_nms), survivors class after class.
+          The reference's line builds the label mapping as torch.arange(1, self.num_class), which fails its own
+          `assert cur_cls_preds.shape[1] == len(cur_label_mapping)` for num_class columns; the evident intent, labels
+          1 .. num_class, is implemented here (a list of cls_preds with multihead_label_mapping is not supported).
+        and generate_recall_record when batch_dict holds gt_boxes."""
         cfg = _get(self.model_cfg, 'POST_PROCESSING')
         nms_cfg = _get(cfg, 'NMS_CONFIG')
-        assert not _get(nms_cfg, 'MULTI_CLASSES_NMS', False), 'multi-class NMS is not part of the point path'
+        assert not isinstance(batch_dict['batch_cls_preds'], list), 'a list of cls_preds is not part of the point path'
+        recall_dict = {}
         pred_dicts = []
         for index in range(batch_dict['batch_size']):
             if batch_dict.get('batch_index', None) is not None:
@@ -142,20 +179,69 @@ class Detector3DTemplate(nn.Module):
                 assert batch_dict['batch_box_preds'].dim() == 3
                 batch_mask = index
             box_preds = batch_dict['batch_box_preds'][batch_mask]
+            src_box_preds = box_preds
             cls_preds = batch_dict['batch_cls_preds'][batch_mask]
             src_cls_preds = cls_preds
             assert cls_preds.shape[1] in [1, self.num_class]
             if not batch_dict['cls_preds_normalized']:
                 cls_preds = torch.sigmoid(cls_preds)
-            cls_preds, label_preds = torch.max(cls_preds, dim=-1)
-            label_preds = label_preds + 1
-            selected, selected_scores = iou3d_nms_utils.class_agnostic_nms(
-                box_scores=cls_preds, box_preds=box_preds, nms_config=nms_cfg, score_thresh=_get(cfg, 'SCORE_THRESH'))
-            if _get(cfg, 'OUTPUT_RAW_SCORE', False):
-                selected_scores = torch.max(src_cls_preds, dim=-1)[0][selected]
-            pred_dicts.append({'pred_boxes': box_preds[selected], 'pred_scores': selected_scores,
-                               'pred_labels': label_preds[selected]})
-        return pred_dicts, {}
+            if _get(nms_cfg, 'MULTI_CLASSES_NMS', False):
+                label_mapping = torch.arange(1, self.num_class + 1, device=cls_preds.device)
+                assert cls_preds.shape[1] == len(label_mapping)
+                final_scores, final_labels, final_boxes = iou3d_nms_utils.multi_classes_nms(
+                    cls_scores=cls_preds, box_preds=box_preds, nms_config=nms_cfg, score_thresh=_get(cfg, 'SCORE_THRESH'))
+                final_labels = label_mapping[final_labels]
+            else:
+                cls_preds, label_preds = torch.max(cls_preds, dim=-1)
+                if batch_dict.get('has_class_labels', False):
+                    label_key = 'roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'
+                    label_preds = batch_dict[label_key][index]
+                else:
+                    label_preds = label_preds + 1
+                selected, selected_scores = iou3d_nms_utils.class_agnostic_nms(
+                    box_scores=cls_preds, box_preds=box_preds, nms_config=nms_cfg, score_thresh=_get(cfg, 'SCORE_THRESH'))
+                if _get(cfg, 'OUTPUT_RAW_SCORE', False):
+                    selected_scores = torch.max(src_cls_preds, dim=-1)[0][selected]
+                final_scores, final_labels, final_boxes = selected_scores, label_preds[selected], box_preds[selected]
+            recall_dict = self.generate_recall_record(
+                box_preds=final_boxes if 'rois' not in batch_dict else src_box_preds, recall_dict=recall_dict,
+                batch_index=index, data_dict=batch_dict, thresh_list=_get(cfg, 'RECALL_THRESH_LIST'))
+            pred_dicts.append({'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels})
+        return pred_dicts, recall_dict
+
+    @staticmethod
+    def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
+        """ref :265-300: counts of gt boxes ('gt') and of gt boxes whose best 3-D IoU with a kept box exceeds each
+        threshold ('rcnn_<t>'; 'roi_<t>' for the rois, when batch_dict holds any), accumulated over the samples.
+        Trailing gt rows whose sum is 0 are padding."""
+        if 'gt_boxes' not in data_dict:
+            return recall_dict
+        rois = data_dict['rois'][batch_index] if 'rois' in data_dict else None
+        gt_boxes = data_dict['gt_boxes'][batch_index]
+        if len(recall_dict) == 0:
+            recall_dict = {'gt': 0}
+            for cur_thresh in thresh_list:
+                recall_dict['roi_%s' % (str(cur_thresh))] = 0
+                recall_dict['rcnn_%s' % (str(cur_thresh))] = 0
+        cur_gt = gt_boxes
+        k = cur_gt.__len__() - 1
+        while k >= 0 and cur_gt[k].sum() == 0:
+            k -= 1
+        cur_gt = cur_gt[:k + 1]
+        if cur_gt.shape[0] > 0:
+            if box_preds.shape[0] > 0:
+                iou3d_rcnn = iou3d_nms_utils.boxes_iou3d_gpu(box_preds[:, 0:7], cur_gt[:, 0:7])
+            else:
+                iou3d_rcnn = torch.zeros((0, cur_gt.shape[0]))
+            if rois is not None:
+                iou3d_roi = iou3d_nms_utils.boxes_iou3d_gpu(rois[:, 0:7], cur_gt[:, 0:7])
+            for cur_thresh in thresh_list:
+                if iou3d_rcnn.shape[0] > 0:
+                    recall_dict['rcnn_%s' % str(cur_thresh)] += (iou3d_rcnn.max(dim=0)[0] > cur_thresh).sum().item()
+                if rois is not None:
+                    recall_dict['roi_%s' % str(cur_thresh)] += (iou3d_roi.max(dim=0)[0] > cur_thresh).sum().item()
+            recall_dict['gt'] += cur_gt.shape[0]
+        return recall_dict
 
     def load_params_from_state_dict(self, model_state_disk, strict=True):
         """Copy every entry whose key and shape match (ref :330-359, without the spconv weight re-layout).  As in the

@@ -142,3 +142,35 @@ def class_agnostic_nms(box_scores, box_preds, nms_config, score_thresh=None):
         original_idxs = scores_mask.nonzero().view(-1)
         selected = original_idxs[selected]
     return selected, src_box_scores[selected]
+
+
+def multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh=None):
+    """ref pcdet/models/model_utils/model_nms_utils.py:29-70 — class_agnostic_nms per score column k of cls_scores
+    (N, num_class): threshold, top NMS_PRE_MAXSIZE, NMS, first NMS_POST_MAXSIZE; returns (scores, labels 0 .. num_class-1,
+    boxes) of the survivors, class after class.  The pre-selection is pdm_topk_sampling (ties by lower index), as in
+    class_agnostic_nms."""
+    from ..pointnet2_batch.pointnet2_utils import topk_sample
+    get = (lambda k: nms_config[k]) if isinstance(nms_config, dict) else (lambda k: getattr(nms_config, k))
+    nms_fn = {'nms_gpu': nms_gpu, 'nms_normal_gpu': nms_normal_gpu}[get('NMS_TYPE')]
+    pred_scores, pred_labels, pred_boxes = [], [], []
+    for k in range(cls_scores.shape[1]):
+        if score_thresh is not None:
+            scores_mask = cls_scores[:, k] >= score_thresh
+            box_scores = cls_scores[scores_mask, k]
+            cur_box_preds = box_preds[scores_mask]
+        else:
+            box_scores = cls_scores[:, k]
+            cur_box_preds = box_preds
+        selected = torch.zeros((0,), dtype=torch.int64, device=box_scores.device)
+        if box_scores.shape[0] > 0:
+            n = min(int(get('NMS_PRE_MAXSIZE')), box_scores.shape[0])
+            if n <= 16384:
+                indices = topk_sample(box_scores.view(1, -1), n)[0].long()
+            else:
+                indices = torch.topk(box_scores, k=n)[1]
+            keep_idx, _ = nms_fn(cur_box_preds[indices][:, 0:7], box_scores[indices], get('NMS_THRESH'))
+            selected = indices[keep_idx[:int(get('NMS_POST_MAXSIZE'))]]
+        pred_scores.append(box_scores[selected])
+        pred_labels.append(box_scores.new_ones(len(selected)).long() * k)
+        pred_boxes.append(cur_box_preds[selected])
+    return torch.cat(pred_scores, dim=0), torch.cat(pred_labels, dim=0), torch.cat(pred_boxes, dim=0)

@@ -1,0 +1,373 @@
+"""Batched on-device post-processing (pdm_post_process, pdm_ssd_amd/post_process.py, POST_PROCESSING.BATCHED) against
+Detector3DTemplate's per-sample loop, the CPU oracle and pdm_nms: bit-equal boxes, scores, labels and recall counts."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from detector_case import scene_boxes
+from pdm_ssd_amd import post_process as pp
+from pdm_ssd_amd.detectors.detector3d_template import Detector3DTemplate
+from pdm_ssd_amd.iou3d_nms import iou3d_nms_utils as iu
+
+pytestmark = pytest.mark.gpu
+
+THRESH_LIST = [0.3, 0.5, 0.7]
+
+
+def post_cfg(pre=4096, post=500, nms_type='nms_gpu', thresh=0.1, raw=False, multi=False, score=0.1, batched=False):
+    return {'RECALL_THRESH_LIST': THRESH_LIST, 'SCORE_THRESH': score, 'OUTPUT_RAW_SCORE': raw, 'BATCHED': batched,
+            'NMS_CONFIG': {'MULTI_CLASSES_NMS': multi, 'NMS_TYPE': nms_type, 'NMS_THRESH': thresh,
+                           'NMS_PRE_MAXSIZE': pre, 'NMS_POST_MAXSIZE': post}}
+
+
+def detector(cfg, num_class=3):
+    """the two methods of Detector3DTemplate that post-processing needs, on a stand-in for the module"""
+    return types.SimpleNamespace(model_cfg={'POST_PROCESSING': cfg}, num_class=num_class,
+                                 generate_recall_record=Detector3DTemplate.generate_recall_record)
+
+
+def loop(cfg, bd, num_class=3):
+    return Detector3DTemplate.post_processing_loop(detector(cfg, num_class), bd)
+
+
+def routed(cfg, bd, num_class=3):
+    d = detector(dict(cfg, BATCHED=True), num_class)
+    d.post_processing_loop = lambda b: Detector3DTemplate.post_processing_loop(d, b)
+    return Detector3DTemplate.post_processing(d, bd)
+
+
+def clustered_boxes(rng, n, clusters=48, spread=0.35):
+    """rows scattered around a few object centres (NMS suppresses most of them), rotated, car / cyclist sizes"""
+    c = np.stack([rng.uniform(0, 70, clusters), rng.uniform(-40, 40, clusters), rng.uniform(-2, 0, clusters)], 1)
+    which = rng.integers(0, clusters, n)
+    b = np.zeros((n, 7), np.float32)
+    b[:, :3] = c[which] + rng.normal(0, spread, (n, 3))
+    sizes = np.array([[3.9, 1.6, 1.56], [1.76, 0.6, 1.73]], np.float32)
+    b[:, 3:6] = sizes[rng.integers(0, 2, n)] * rng.uniform(0.8, 1.2, (n, 3))
+    b[:, 6] = rng.uniform(-np.pi, np.pi, n)
+    return b
+
+
+def make_batch(dev, B, N, C=3, seed=0, normalized=False, below=(), layout=3, ties=False):
+    """batch_dict with tie-free logits (a permutation of distinct values) unless ties; samples in `below` entirely
+    below SCORE_THRESH = 0.1"""
+    rng = np.random.default_rng(seed)
+    boxes = np.stack([clustered_boxes(rng, N) for _ in range(B)])
+    if ties:
+        logits = rng.integers(-8, 4, (B, N, C)).astype(np.float32) * 0.5
+    else:
+        logits = (rng.permutation(B * N * C).astype(np.float64) / (B * N * C) * 7.0 - 5.0).astype(np.float32).reshape(B, N, C)
+    for b in below:
+        logits[b] = -6.0 - rng.uniform(0, 1, (N, C)).astype(np.float32)
+    cls = torch.from_numpy(logits).to(dev)
+    if normalized:
+        cls = torch.sigmoid(cls)
+    bd = {'batch_size': B, 'batch_cls_preds': cls, 'batch_box_preds': torch.from_numpy(boxes).to(dev),
+          'cls_preds_normalized': normalized}
+    if layout == 2:
+        bd['batch_cls_preds'] = cls.reshape(B * N, C)
+        bd['batch_box_preds'] = bd['batch_box_preds'].reshape(B * N, 7)
+        bd['batch_index'] = torch.arange(B, device=dev, dtype=torch.float32).repeat_interleave(N)
+    return bd
+
+
+def assert_same(got, want):
+    (gp, gr), (wp, wr) = got, want
+    assert len(gp) == len(wp)
+    for g, w in zip(gp, wp):
+        for k in ('pred_boxes', 'pred_scores', 'pred_labels'):
+            assert g[k].dtype == w[k].dtype and g[k].shape == w[k].shape, (k, g[k].shape, w[k].shape)
+            assert torch.equal(g[k], w[k]), k
+    assert gr == wr
+
+
+@pytest.mark.parametrize("B,pre,post,nms_type,raw,normalized,layout", [
+    (1, 4096, 500, 'nms_gpu', False, False, 3),
+    (4, 1024, 40, 'nms_normal_gpu', True, False, 2),
+    (4, 16384, 100, 'nms_gpu', False, True, 3),
+    (32, 4096, 500, 'nms_gpu', True, True, 2),
+    (32, 2048, 30, 'nms_normal_gpu', False, False, 3),
+])
+def test_batched_equals_loop_class_agnostic(dev, B, pre, post, nms_type, raw, normalized, layout):
+    N = 16384
+    bd = make_batch(dev, B, N, seed=B + pre, normalized=normalized, below=(B - 1,) if B > 1 else (), layout=layout)
+    cfg = post_cfg(pre=pre, post=post, nms_type=nms_type, raw=raw)
+    want = loop(cfg, bd)
+    got = pp.batched_post_processing(bd, cfg, 3)
+    assert_same(got, want)
+    assert_same(routed(cfg, bd), want)
+    counts = [d['pred_boxes'].shape[0] for d in want[0]]
+    if B > 1:
+        assert counts[-1] == 0                        # the sample below the threshold
+    assert max(counts) > 0
+    if post <= 40:
+        assert max(counts) == post                    # the POST_MAX cut is active
+    # NMS did suppress: far fewer survivors than candidates
+    assert max(counts) < pre
+
+
+def test_tie_order_against_cpu_oracle(dev, oracle):
+    B, N, thresh, pre = 2, 3000, 0.1, 1500
+    bd = make_batch(dev, B, N, C=1, seed=7, normalized=False, ties=True, layout=3)
+    cfg = post_cfg(pre=pre, post=10000, thresh=thresh)
+    out = pp.post_process_padded(bd, cfg, 3)
+    probs = torch.sigmoid(bd['batch_cls_preds']).cpu().numpy()[..., 0]
+    boxes = bd['batch_box_preds'].cpu().numpy()
+    count = out['count'].cpu().numpy()
+    rows = out['rows'].cpu().numpy()
+    for b in range(B):
+        cand = np.nonzero(probs[b] >= np.float32(0.1))[0]
+        order = cand[np.lexsort((cand, -probs[b, cand]))][:pre]        # score descending, lower row first
+        ref = order[oracle.nms(boxes[b, order], thresh)]
+        got = rows[b, :count[b]]
+        assert (rows[b, count[b]:] == -1).all()
+        if not np.array_equal(got, ref):
+            iou = oracle.boxes_iou_bev(boxes[b, order], boxes[b, order])
+            assert (np.abs(iou - thresh) < 1e-4).any(), "NMS differs from the oracle away from the threshold"
+            assert np.array_equal(got[:1], ref[:1])
+    # the tie order itself: equal scores ranked by lower row in the selection the NMS walks
+    assert np.unique(probs).size < probs.size / 10
+
+
+def _prefilter_scene(rng):
+    """footprints separated by gaps below inside_box's 0.01 tolerance, touching corners, long thin rotated boxes"""
+    rows = []
+    for i in range(60):   # axis-aligned pairs with a gap of 0 .. 0.012
+        x0, y0, gap = 2.0 + 6 * (i % 10), -30.0 + 8 * (i // 10), 0.0002 * i
+        rows.append([x0, y0, 0, 4.0, 2.0, 1.5, 0])
+        rows.append([x0 + 4.0 + gap, y0, 0, 4.0, 2.0, 1.5, 0])
+        rows.append([x0, y0 + 2.0 + gap, 0, 4.0, 2.0, 1.5, 0])
+    for i in range(40):   # corner to corner: a 2 x 2 square and its copy shifted by (2 + e, 2 + e), rotated pairs
+        x0, y0, e = 70.0 + 5 * (i % 8), -20.0 + 6 * (i // 8), (i - 20) * 0.0005
+        rows.append([x0, y0, 0, 2.0, 2.0, 1.0, 0])
+        rows.append([x0 + 2.0 + e, y0 + 2.0 + e, 0, 2.0, 2.0, 1.0, 0])
+        rows.append([x0 + 1.0, y0 - 2.4142 - e, 0, 2.0, 2.0, 1.0, np.pi / 4])
+    for i in range(80):   # long thin boxes, rotated, crossing and nearly crossing each other
+        c = rng.uniform([120, -20], [140, 20])
+        rows.append([c[0], c[1], 0, rng.uniform(6, 12), rng.uniform(0.05, 0.3), 1.0, rng.uniform(-np.pi, np.pi)])
+    return np.asarray(rows, np.float32)
+
+
+@pytest.mark.parametrize("thresh,nms_type", [(0.0, 'nms_gpu'), (0.1, 'nms_gpu'), (0.0, 'nms_normal_gpu'), (0.01, 'nms_gpu')])
+def test_prefilter_keeps_pdm_nms_decisions(dev, thresh, nms_type):
+    rng = np.random.default_rng(3)
+    boxes = _prefilter_scene(rng)
+    n = boxes.shape[0]
+    scores = rng.permutation(n).astype(np.float32) / n * 0.8 + 0.15
+    B = 2
+    bx = torch.from_numpy(np.stack([boxes, boxes[::-1].copy()])).to(dev)
+    sc = torch.from_numpy(np.stack([scores, scores])).to(dev).view(B, n, 1)
+    bd = {'batch_size': B, 'batch_cls_preds': sc, 'batch_box_preds': bx, 'cls_preds_normalized': True}
+    cfg = post_cfg(pre=4096, post=4096, nms_type=nms_type, thresh=thresh)
+    out = pp.post_process_padded(bd, cfg, 3)
+    fn = iu.nms_normal_gpu if nms_type == 'nms_normal_gpu' else iu.nms_gpu
+    for b in range(B):
+        keep, _ = fn(bx[b], sc[b, :, 0], thresh)             # pdm_nms on the same (distinct-score) order
+        c = int(out['count'][b])
+        assert torch.equal(out['rows'][b, :c], keep), b
+        assert c < n                                        # something was suppressed
+
+
+def reference_multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh):
+    """model_nms_utils.py:29-70 restated in torch (torch.topk; the scores here are tie-free)"""
+    pred_scores, pred_labels, pred_boxes = [], [], []
+    for k in range(cls_scores.shape[1]):
+        scores_mask = cls_scores[:, k] >= score_thresh
+        box_scores = cls_scores[scores_mask, k]
+        cur_box_preds = box_preds[scores_mask]
+        selected = torch.zeros((0,), dtype=torch.int64, device=box_scores.device)
+        if box_scores.shape[0] > 0:
+            box_scores_nms, indices = torch.topk(box_scores, k=min(nms_config['NMS_PRE_MAXSIZE'], box_scores.shape[0]))
+            keep_idx, _ = getattr(iu, nms_config['NMS_TYPE'])(cur_box_preds[indices][:, 0:7], box_scores_nms,
+                                                              nms_config['NMS_THRESH'])
+            selected = indices[keep_idx[:nms_config['NMS_POST_MAXSIZE']]]
+        pred_scores.append(box_scores[selected])
+        pred_labels.append(box_scores.new_ones(len(selected)).long() * k)
+        pred_boxes.append(cur_box_preds[selected])
+    return torch.cat(pred_scores), torch.cat(pred_labels), torch.cat(pred_boxes)
+
+
+@pytest.mark.parametrize("B,layout,post", [(1, 3, 500), (4, 2, 25), (32, 3, 200)])
+def test_multi_class_equals_loop_and_reference(dev, B, layout, post):
+    N = 16384
+    bd = make_batch(dev, B, N, seed=11 + B, layout=layout, below=(0,) if B > 1 else ())
+    cfg = post_cfg(pre=2048, post=post, multi=True)
+    want = loop(cfg, bd)
+    assert_same(pp.batched_post_processing(bd, cfg, 3), want)
+    assert_same(routed(cfg, bd), want)
+    cls = bd['batch_cls_preds'].reshape(B, N, 3)
+    box = bd['batch_box_preds'].reshape(B, N, 7)
+    for b in range(B):
+        s, l, x = reference_multi_classes_nms(torch.sigmoid(cls[b]), box[b], cfg['NMS_CONFIG'], 0.1)
+        d = want[0][b]
+        assert torch.equal(d['pred_scores'], s) and torch.equal(d['pred_labels'], l + 1) and torch.equal(d['pred_boxes'], x)
+    assert sum(len(d['pred_labels'].unique()) for d in want[0]) > B   # more than one class survives
+
+
+def test_recall_equals_loop(dev):
+    B, N = 4, 16384
+    bd = make_batch(dev, B, N, seed=5, layout=2, below=(2,))
+    gt = scene_boxes(B, 12, 9)
+    first = loop(post_cfg(pre=4096, post=500), bd)
+    for b in range(B):   # some gt boxes close to kept boxes, so that the rcnn_ counts are not trivially zero
+        kb = first[0][b]['pred_boxes'][:4].cpu().numpy()
+        gt[b, :kb.shape[0], :7] = kb + np.float32(0.05)
+    bd['gt_boxes'] = torch.from_numpy(gt).to(dev)
+    for cfg in (post_cfg(pre=4096, post=500), post_cfg(pre=1024, post=50, multi=True, nms_type='nms_normal_gpu')):
+        want = loop(cfg, bd)
+        assert want[1]['gt'] == int((np.abs(gt).sum(2) != 0).sum()) and want[1]['rcnn_0.3'] > 0
+        assert_same(pp.batched_post_processing(bd, cfg, 3, gt_boxes=bd['gt_boxes']), want)
+        assert_same(routed(cfg, bd), want)
+
+
+def test_recall_hand_built_counts(dev):
+    """sample 0: gt 1 = kept box A (IoU 1), gt 2 = kept box B moved 1 m along x (IoU 9 / 15 = 0.6), gt 3 far away,
+    two trailing zero rows; sample 1: no kept box, two gt rows; sample 2: kept boxes, gt all zero."""
+    B, N = 3, 4
+    boxes = np.zeros((B, N, 7), np.float32)
+    boxes[:, :, 0] = np.arange(N) * 20.0 + 10.0
+    boxes[:, :, 3:6] = [4.0, 2.0, 1.5]
+    scores = np.full((B, N, 1), 0.05, np.float32)
+    scores[0, :2, 0] = [0.9, 0.8]
+    scores[2, :, 0] = [0.5, 0.49, 0.48, 0.47]   # distinct: the loop's nms_gpu re-sorts with torch.sort, whose tie order is unspecified
+    gt = np.zeros((B, 5, 8), np.float32)
+    gt[0, 0] = [10, 0, 0, 4, 2, 1.5, 0, 1]
+    gt[0, 1] = [31, 0, 0, 4, 2, 1.5, 0, 1]
+    gt[0, 2] = [50, 20, 0, 4, 2, 1.5, 0, 2]
+    gt[1, 0] = [10, 0, 0, 4, 2, 1.5, 0, 1]
+    gt[1, 3] = [5, 5, 0, 1, 1, 1, 0, 3]       # an all-zero row before it is not trailing
+    bd = {'batch_size': B, 'batch_cls_preds': torch.from_numpy(scores).to(dev),
+          'batch_box_preds': torch.from_numpy(boxes).to(dev), 'cls_preds_normalized': True,
+          'gt_boxes': torch.from_numpy(gt).to(dev)}
+    cfg = post_cfg()
+    expect = {'gt': 3 + 4, 'roi_0.3': 0, 'rcnn_0.3': 2, 'roi_0.5': 0, 'rcnn_0.5': 2, 'roi_0.7': 0, 'rcnn_0.7': 1}
+    got = pp.batched_post_processing(bd, cfg, 3, gt_boxes=bd['gt_boxes'])
+    assert got[1] == expect
+    assert [d['pred_boxes'].shape[0] for d in got[0]] == [2, 0, 4]
+    assert_same(got, loop(cfg, bd))
+
+
+def test_padded_entry_does_not_sync_and_captures(dev):
+    B, N = 8, 16384
+    bd = make_batch(dev, B, N, seed=21, layout=2)
+    gt = torch.from_numpy(scene_boxes(B, 10, 4)).to(dev)
+    cfg = post_cfg(pre=4096, post=200)
+    pp.post_process_padded(bd, cfg, 3, gt_boxes=gt)            # warm-up
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        eager0 = pp.post_process_padded(bd, cfg, 3, gt_boxes=gt)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        pp.post_process_padded(bd, cfg, 3, gt_boxes=gt)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        static = pp.post_process_padded(bd, cfg, 3, gt_boxes=gt)
+    new = make_batch(dev, B, N, seed=22, layout=2)
+    new_gt = torch.from_numpy(scene_boxes(B, 10, 5)).to(dev)
+    bd['batch_cls_preds'].copy_(new['batch_cls_preds'])
+    bd['batch_box_preds'].copy_(new['batch_box_preds'])
+    gt.copy_(new_gt)
+    g.replay()
+    eager = pp.post_process_padded(new, cfg, 3, gt_boxes=new_gt)
+    torch.cuda.synchronize()
+    for k in ('rows', 'boxes', 'scores', 'labels', 'count', 'error', 'recall'):
+        assert torch.equal(static[k], eager[k]), k
+    assert not torch.equal(eager0['rows'], eager['rows'])
+    assert int(eager['recall'][0]) > 0 and int(eager['error'][0]) == 0
+
+
+def test_ragged_and_non_sample_major_batch_index(dev):
+    rng = np.random.default_rng(8)
+    sizes = [3000, 16384, 1, 700, 0, 9000]
+    B = len(sizes)
+    boxes = np.concatenate([clustered_boxes(rng, n) for n in sizes]).astype(np.float32)
+    logits = rng.normal(-1.5, 1.5, (boxes.shape[0], 3)).astype(np.float32)
+    bi = np.repeat(np.arange(B), sizes).astype(np.float32)
+    bd = {'batch_size': B, 'batch_cls_preds': torch.from_numpy(logits).to(dev),
+          'batch_box_preds': torch.from_numpy(boxes).to(dev), 'cls_preds_normalized': False,
+          'batch_index': torch.from_numpy(bi).to(dev)}
+    cfg = post_cfg(pre=2048, post=300)
+    want = loop(cfg, bd)
+    assert_same(pp.batched_post_processing(bd, cfg, 3), want)
+    assert int(pp.post_process_padded(bd, cfg, 3)['error'][0]) == 0
+    # rows of sample 3 moved in front of sample 1: not sample-major
+    perm = np.concatenate([np.arange(3000), np.arange(19385, 20085), np.arange(3000, 19385), np.arange(20085, boxes.shape[0])])
+    bd2 = dict(bd, batch_cls_preds=bd['batch_cls_preds'][perm], batch_box_preds=bd['batch_box_preds'][perm],
+               batch_index=bd['batch_index'][perm])
+    assert int(pp.post_process_padded(bd2, cfg, 3)['error'][0]) == 1
+    assert pp.batched_post_processing(bd2, cfg, 3) is None
+    with pytest.warns(RuntimeWarning):
+        pp._warned.discard('batch_index is not sample-major')
+        got = routed(cfg, bd2)
+    assert_same(got, loop(cfg, bd2))
+
+
+@pytest.mark.parametrize("B,N,pre,post,below,multi", [
+    (1, 5000, 4096, 500, False, False), (3, 0, 4096, 500, False, False), (2, 3000, 4096, 500, True, False),
+    (2, 3000, 1, 500, False, False), (2, 3000, 4096, 1, False, True), (2, 20000, 16384, 500, False, False),
+    (1, 1, 1, 1, False, False)])
+def test_workspace_tail_untouched(dev, B, N, pre, post, below, multi):
+    bd = make_batch(dev, B, N, seed=N + pre, below=range(B) if below else (), layout=3)
+    cfg = post_cfg(pre=pre, post=post, multi=multi)
+    S = B * (3 if multi else 1)
+    nbytes = pp.workspace_bytes(S, pre, post)
+    assert nbytes >= S * pre * ((pre + 63) // 64) * 8
+    buf = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+    pattern = (torch.arange(256, device=dev) * 37 % 251).to(torch.uint8)
+    buf[nbytes:] = pattern
+    gt = torch.from_numpy(scene_boxes(B, 6, 1)).to(dev)
+    out = pp.post_process_padded(bd, cfg, 3, gt_boxes=gt, workspace=buf[:nbytes])
+    torch.cuda.synchronize()
+    assert torch.equal(buf[nbytes:], pattern)
+    want = loop(cfg, dict(bd, gt_boxes=gt))
+    for b in range(B):
+        c = int(out['count'][b])
+        assert c == want[0][b]['pred_boxes'].shape[0]
+        assert torch.equal(out['boxes'][b, :c], want[0][b]['pred_boxes'])
+        assert (out['rows'][b, c:] == -1).all() and (out['boxes'][b, c:] == 0).all()
+    if below or N == 0:
+        assert int(out['count'].sum()) == 0
+
+
+def test_detector_end_to_end_batched_equals_loop(dev):
+    import copy
+
+    from pdm_ssd_amd import synthetic
+    from pdm_ssd_amd.detector_config import build_pdm_ssd
+    from detector_case import SMALL
+    torch.manual_seed(2)
+    model = build_pdm_ssd(SMALL).to(dev).eval()
+    with torch.no_grad():
+        model.point_head.cls_layers[-1].bias.fill_(0.5)
+    B, N = 2, 2048
+    pts = torch.from_numpy(synthetic.to_batch_points(synthetic.lidar_like_clouds(B, N, 9))).to(dev)
+    gt = torch.from_numpy(scene_boxes(B, 6, 3)).to(dev)
+    captured = {}
+    orig = model.post_processing
+
+    def grab(bd):
+        captured['bd'] = bd
+        return orig(bd)
+    model.post_processing = grab
+    with torch.no_grad():
+        want = model({'batch_size': B, 'points': pts, 'gt_boxes': gt})
+    bd = captured['bd']
+    first = Detector3DTemplate.post_processing_loop(model, {k: v for k, v in bd.items() if k != 'gt_boxes'})
+    for b in range(B):                                     # gt on kept boxes: the rcnn_ counts are not all zero
+        kb = first[0][b]['pred_boxes'][:3]
+        bd['gt_boxes'][b, :kb.shape[0], :7] = kb
+    want = Detector3DTemplate.post_processing(model, bd)
+    assert want[1]['gt'] > 0 and want[1]['rcnn_0.7'] > 0
+    model.model_cfg = copy.copy(model.model_cfg)
+    model.model_cfg['POST_PROCESSING'] = dict(model.model_cfg['POST_PROCESSING'], BATCHED=True)
+    got = Detector3DTemplate.post_processing(model, bd)
+    assert_same(got, want)
+    assert all(d['pred_boxes'].shape[0] > 0 for d in got[0])

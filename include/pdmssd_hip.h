@@ -552,6 +552,49 @@ int pdm_points_in_boxes(void *stream, int B, int T, int M, const float *boxes, c
 int pdm_sample_points(void *stream, int B, int num_points, unsigned seed, int C, const float *raw,
                       const int *counts, float *out, int *choice);
 
+/* ---- training augmentation (csrc/augment.hip) --------------------------------------------
+ * The reference's DataAugmentor.forward with gt_sampling, random_world_flip / _rotation / _scaling
+ * (data_augmentor.py:290-318, database_sampler.py:130-147 / :365-443 / :445-502, augmentor_utils.py:8-92), limit_period,
+ * and the range mask + class column of the data processor (data_processor.py:79-93, dataset.py:158-215), for B scenes
+ * at once.  Box rows are 8 floats [x, y, z, dx, dy, dz, heading, class]: class > 0 a target (index + 1), < 0 a
+ * non-target box that only blocks candidates, 0 padding.  Limits: B <= 1024, G <= 8 sample groups, K = sum of the
+ * groups' sample numbers <= 256 candidate slots per scene, M <= 256 input boxes per scene, M_out <= 512,
+ * 3 <= C <= 16 point features.  Group arrays (class index, sample number, database entries, first database index of
+ * the class) are HOST arrays; everything else is on the device.  The draws are build-defined functions of
+ * (seed, state, scene, group) documented in augment.hip.  workspace >= pdm_augment_workspace_bytes(B, K), shared by
+ * the calls of one augmentation (draw -> select -> scene_count -> scene_fill on one stream).
+ *   draw:   state (1 + 2G) int32 [step, (epoch, pointer) per group], advanced in place -> sampled (B, K) database
+ *           indices (-1 padded; group t owns the slots from the sum of the earlier sample numbers), flip (B) bits
+ *           (1 = x, 2 = y), angle (B), scale (B).  flip_axes: bit mask of the configured axes.
+ *   select: collision test, accepted (B, K) (-1 padded) / num_accepted (B), out_boxes (B, M_out, 8) = the target and
+ *           accepted boxes transformed, heading wrapped, range-masked (remove_outside), zero-padded; out_num_boxes (B).
+ *           ops = the transform list, one nibble each from the lowest: 1 flip x, 2 flip y, 3 rotation, 4 scaling.
+ *           point_cloud_range: HOST array of 6 floats.  Sampled indices outside [0, db_entries) count as padding.
+ *   scene_count / scene_fill: rows = [object points of the accepted entries] + [scene points outside every accepted
+ *           box enlarged by extra_width (HOST, 3 floats)], transformed, x / y range-masked; out_counts (B) and the
+ *           overflow flag (total > capacity) are written by scene_count, the rows (scene after scene, C floats each,
+ *           never past capacity) by scene_fill.  db_points (P, C) relative to the box centre, db_offsets (entries + 1). */
+size_t pdm_augment_workspace_bytes(int B, int K);
+int pdm_augment_draw(void *stream, int B, int G, const int *group_class, const int *group_num, const int *group_len,
+                     const int *group_first, int limit_whole_scene, int M, const float *gt_boxes, unsigned seed, int *state,
+                     int flip_axes, int use_rot, float rot_lo, float rot_hi, int use_scale, float scale_lo, float scale_hi,
+                     int K, int *sampled, int *flip, float *angle, float *scale, void *workspace, size_t workspace_bytes);
+int pdm_augment_select(void *stream, int B, int M, const float *gt_boxes, int G, const int *group_class,
+                       const int *group_num, long long db_entries, const float *db_boxes, const long long *db_offsets, int K,
+                       const int *sampled, const int *flip, const float *angle, const float *scale, unsigned ops,
+                       const float *point_cloud_range, int remove_outside, int M_out, float *out_boxes, int *out_num_boxes,
+                       int *accepted, int *num_accepted, void *workspace, size_t workspace_bytes);
+int pdm_augment_scene_count(void *stream, int B, int C, const float *raw, const int *counts, const float *db_points,
+                            const long long *db_offsets, const float *db_boxes, int K, const int *accepted,
+                            const int *num_accepted, const int *flip, const float *angle, const float *scale, unsigned ops,
+                            const float *point_cloud_range, const float *extra_width, long long capacity, int *out_counts,
+                            int *overflow, float *out_rows, void *workspace, size_t workspace_bytes);
+int pdm_augment_scene_fill(void *stream, int B, int C, const float *raw, const int *counts, const float *db_points,
+                           const long long *db_offsets, const float *db_boxes, int K, const int *accepted,
+                           const int *num_accepted, const int *flip, const float *angle, const float *scale, unsigned ops,
+                           const float *point_cloud_range, const float *extra_width, long long capacity, int *out_counts,
+                           int *overflow, float *out_rows, void *workspace, size_t workspace_bytes);
+
 /* ---- rows form of the FP module's input for the training path (csrc/interpolate.hip) --------------------------------
  * out (B, n, ld) bf16 = [ three_interpolate(known, idx, weight) (C2) | skip (C1) | zeros ]: the reference's
  * cat([interpolated, unknow_feats], dim=1) (pointnet2_modules.py:158-165) written once as the rows the bf16 layers read, each

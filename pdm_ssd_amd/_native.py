@@ -66,6 +66,14 @@ _SIGNATURES = {
     "pdm_point_head_decode": [ctypes.c_longlong, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
     "pdm_bev_head_fused": [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i],
     "pdm_sample_points": [_i, _i, ctypes.c_uint, _i, _vp, _vp, _vp, _vp],
+    "pdm_augment_draw": [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_uint, _vp, _i, _i, _f, _f, _i, _f, _f, _i, _vp, _vp, _vp,
+                         _vp, _vp, ctypes.c_size_t],
+    "pdm_augment_select": [_i, _i, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp, _i, _i,
+                           _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t],
+    "pdm_augment_scene_count": [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp, _vp, ctypes.c_longlong,
+                                _vp, _vp, _vp, _vp, ctypes.c_size_t],
+    "pdm_augment_scene_fill": [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp, _vp, ctypes.c_longlong,
+                               _vp, _vp, _vp, _vp, ctypes.c_size_t],
     "pdm_stack_ball_query": [_i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "pdm_stack_group_points": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pdm_stack_group_points_grad": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
@@ -167,7 +175,7 @@ _SIGNATURES = {
 EXPORTS = ["pdm_abi_version", "pdm_last_error", "pdm_ball_query_grid_workspace_bytes",
            "pdm_three_nn_grid_workspace_bytes", "pdm_furthest_point_sampling_ws_bytes",
            "pdm_fps_max_coresident_workgroups",
-           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_sa_pack_workspace_bytes",
+           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_sa_pack_workspace_bytes",
            "pdm_sa_pack_rows", "pdm_rows_mlp_x3_stream_bytes", "pdm_point_head_loss_workspace_bytes", "pdm_heatmap_focal_loss_workspace_bytes", "pdm_three_interpolate_grad_ws_bytes",
            "pdm_group_points_grad_ws_bytes", "pdm_group_concat_cl_grad_ws_bytes", "pdm_bn_parts", "pdm_bn_pool_parts",
            "pdm_tg_stats_parts", "pdm_tg_dy_stats_parts", "pdm_tg_wgrad_ws_bytes", "pdm_tg_colsum_ws_floats"] + list(_SIGNATURES)
@@ -219,6 +227,8 @@ def lib():
         l.pdm_nms_workspace_bytes.argtypes = [_i]
         l.pdm_post_process_workspace_bytes.restype = ctypes.c_size_t
         l.pdm_post_process_workspace_bytes.argtypes = [_i, _i, _i]
+        l.pdm_augment_workspace_bytes.restype = ctypes.c_size_t
+        l.pdm_augment_workspace_bytes.argtypes = [_i, _i]
         l.pdm_bn_pool_parts.restype = _i
         l.pdm_bn_pool_parts.argtypes = [_i, ctypes.c_longlong, _i]
         l.pdm_tg_colsum_ws_floats.restype = ctypes.c_size_t

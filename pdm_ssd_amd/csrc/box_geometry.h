@@ -90,6 +90,15 @@ __device__ inline float box_overlap_bev(const float *a, const float *b) {
     return fabsf(area) / 2.0f;
 }
 
+// bounding-circle prefilter: true only if the two BEV footprints are certainly disjoint (then box_overlap_bev and
+// iou_normal both return an overlap of exactly 0).  The margin covers inside_box's 1e-2 tolerance (a corner within
+// 1e-2 of the other box lies within its circle radius + 0.0142) plus the rounding of corners and distances.
+__device__ __forceinline__ bool bev_circles_disjoint(float ax, float ay, float ar, float bx, float by, float br) {
+    const float dx = ax - bx, dy = ay - by;
+    const float lim = ar + br + 0.05f + 1e-3f * (ar + br) + 2e-5f * (fabsf(ax) + fabsf(ay) + fabsf(bx) + fabsf(by));
+    return dx * dx + dy * dy > lim * lim;   // NaN / inf anywhere: false, the pair is evaluated
+}
+
 __device__ __forceinline__ float iou_bev(const float *a, const float *b) {
     const float so = box_overlap_bev(a, b);
     return so / fmaxf(a[3] * a[4] + b[3] * b[4] - so, 1e-8f);

@@ -187,15 +187,6 @@ __global__ __launch_bounds__(TK_THREADS) void pp_select_kernel(PPArgs a) {
     }
 }
 
-// bounding-circle prefilter: true only if the two BEV footprints are certainly disjoint (then box_overlap_bev and
-// iou_normal both return an overlap of exactly 0).  The margin covers inside_box's 1e-2 tolerance (a corner within
-// 1e-2 of the other box lies within its circle radius + 0.0142) plus the rounding of corners and distances.
-__device__ __forceinline__ bool pp_disjoint(float ax, float ay, float ar, float bx, float by, float br) {
-    const float dx = ax - bx, dy = ay - by;
-    const float lim = ar + br + 0.05f + 1e-3f * (ar + br) + 2e-5f * (fabsf(ax) + fabsf(ay) + fabsf(bx) + fabsf(by));
-    return dx * dx + dy * dy > lim * lim;   // NaN / inf anywhere: false, the pair is evaluated
-}
-
 __device__ __forceinline__ float pp_radius(const float *box) { return 0.5f * sqrtf(box[3] * box[3] + box[4] * box[4]); }
 
 __global__ __launch_bounds__(64) void pp_mask_kernel(PPArgs a) {
@@ -221,7 +212,7 @@ __global__ __launch_bounds__(64) void pp_mask_kernel(PPArgs a) {
     const int start = row_start == col_start ? threadIdx.x + 1 : 0;
     for (int i = start; i < col_size; ++i) {
         const float *o = col + i * 7;
-        if (prefilter && pp_disjoint(me[0], me[1], mr, o[0], o[1], crad[i])) continue;
+        if (prefilter && bev_circles_disjoint(me[0], me[1], mr, o[0], o[1], crad[i])) continue;
         const float v = a.normal ? iou_normal(me, o) : iou_bev(me, o);
         if (v > a.nms_thresh) t |= 1ull << i;
     }

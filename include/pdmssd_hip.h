@@ -595,6 +595,48 @@ int pdm_augment_scene_fill(void *stream, int B, int C, const float *raw, const i
                            const float *point_cloud_range, const float *extra_width, long long capacity, int *out_counts,
                            int *overflow, float *out_rows, void *workspace, size_t workspace_bytes);
 
+/* ---- KITTI object evaluation (csrc/kitti_eval.hip) ---------------------------------------------
+ * From the padded detections of pdm_post_process to the counts behind KITTI's AP, restating
+ * pcdet/datasets/kitti/kitti_dataset.py:277-330, pcdet/utils/box_utils.py:203-288, pcdet/utils/calibration_kitti.py:65-84 and
+ * pcdet/datasets/kitti/kitti_object_eval_python/eval.py:30-275.  No atomics anywhere: two runs give the same bits.
+ *
+ * pdm_kitti_boxes_to_camera: boxes (B, P, 7) lidar, count (B) live slots per sample, V2C (B, 3, 4), R0 (B, 3, 3), P2 (B, 3, 4),
+ * image_shape (B, 2) int32 [height, width] or NULL (no clip) -> cam (B, P, 7) [x, y, z, l, h, w, ry], img (B, P, 4)
+ * [x1, y1, x2, y2], alpha (B, P); slots at or past count are zeroed.
+ *
+ * The evaluator works on F ragged frames: gt_off, dt_off (F + 1) box ranges, ov_off (F + 1) the start of each frame's
+ * (detections x ground truths) overlap block, NP = ov_off[F] pairs.  Boxes are doubles: bbox (n, 4), cam (n, 7).  A
+ * combination is (metric, class, difficulty, overlap set) with index ((mi nC + c) nD + d) K + k; metrics[nM], classes[nC] and
+ * difficulties[nD] are HOST arrays; class ids are 0 Car, 1 Pedestrian, 2 Cyclist, 3 Van, 4 Person_sitting, 5 Truck,
+ * 6 DontCare, 7 anything else.  Flags (ign_gt (nC nD, NG), ign_dt (nC nD, ND)) are clean_data's 0 / 1 / -1 as bytes.
+ *   overlaps (nM, NP): metric 0 image_box_overlap in fp64; 1 rotated BEV IoU on fp32 casts; 2 fp32 rotated intersection
+ *     area, height overlap and union volume in fp64.
+ *   pass1 (compute_fp = False): the scores of the true positives of (mi, k, c, d, frame f) go to
+ *     slab[(mi K + k) SV + slot_off[(c nD + d)(F + 1) + f] ...], at most slot_off[.. f + 1] - slot_off[.. f] of them (the
+ *     frame's valid ground truths), the rest of the slot range is filled with NaN.
+ *   pass2 (compute_fp = True): thresholds (combinations, 41) fp64 with num_thresholds (combinations) ->
+ *     sums (combinations, 41, 4) int64 = [tp, fp, fn, bits of the fp64 similarity sum] over all frames; workspace >=
+ *     pdm_kitti_eval_workspace_bytes(F, combinations).
+ * Limits: 4096 detections per frame, 1024 combinations, 8 classes. */
+int pdm_kitti_boxes_to_camera(void *stream, int B, int P, const float *boxes, const int *count, const float *V2C,
+                              const float *R0, const float *P2, const int *image_shape, float *cam, float *img, float *alpha);
+int pdm_kitti_eval_overlaps(void *stream, int F, const int *gt_off, const int *dt_off, const int *ov_off, long long NP, int nM,
+                            const int *metrics, const double *gt_bbox, const double *dt_bbox, const double *gt_cam,
+                            const double *dt_cam, double *overlaps);
+int pdm_kitti_eval_dt_flags(void *stream, long long ND, const double *dt_bbox, const int *dt_name, int nC, const int *classes,
+                            int nD, const int *difficulties, signed char *ign_dt);
+size_t pdm_kitti_eval_workspace_bytes(int F, int combinations);
+int pdm_kitti_eval_pass1(void *stream, int F, const int *gt_off, const int *dt_off, const int *ov_off, int max_dt, int nM,
+                         const int *metrics, int nC, int nD, int K, const double *overlaps, long long NP,
+                         const signed char *ign_gt, long long NG, const signed char *ign_dt, long long ND,
+                         const double *dt_score, const double *min_overlap, const int *slot_off, long long SV, double *slab);
+int pdm_kitti_eval_pass2(void *stream, int F, const int *gt_off, const int *dt_off, const int *ov_off, int max_dt, int nM,
+                         const int *metrics, int nC, int nD, int K, const double *overlaps, long long NP,
+                         const signed char *ign_gt, long long NG, const signed char *ign_dt, long long ND,
+                         const double *dt_score, const double *gt_alpha, const double *dt_alpha, const double *gt_bbox,
+                         const double *dt_bbox, const int *gt_name, const double *min_overlap, const double *thresholds,
+                         const int *num_thresholds, int compute_aos, void *workspace, size_t workspace_bytes, long long *sums);
+
 /* ---- rows form of the FP module's input for the training path (csrc/interpolate.hip) --------------------------------
  * out (B, n, ld) bf16 = [ three_interpolate(known, idx, weight) (C2) | skip (C1) | zeros ]: the reference's
  * cat([interpolated, unknow_feats], dim=1) (pointnet2_modules.py:158-165) written once as the rows the bf16 layers read, each

@@ -637,6 +637,48 @@ int pdm_kitti_eval_pass2(void *stream, int F, const int *gt_off, const int *dt_o
                          const double *dt_bbox, const int *gt_name, const double *min_overlap, const double *thresholds,
                          const int *num_thresholds, int compute_aos, void *workspace, size_t workspace_bytes, long long *sums);
 
+/* ---- KITTI dataset front end (csrc/kitti_data.hip) ----------------------------------------
+ * The per-point work of the reference's KittiDataset.get_infos / create_groundtruth_database / __getitem__
+ * (pcdet/datasets/kitti/kitti_dataset.py:124-139, :150-275, :371-428) for B ragged frames at once.  Frames are packed as
+ * the augmentor takes them: raw (total_rows, C) fp32 rows, counts (B) int32 on the device, frame b starting at the sum of
+ * the earlier counts (nothing at or past total_rows is read); calibration V2C (B, 3, 4), R0 (B, 3, 3), P2 (B, 3, 4) fp32 and
+ * image_shape (B, 2) int32 [height, width] per frame.  Limits: B <= 1024, M <= 256 boxes per frame, 3 <= C <= 16 (rows of
+ * C = 4 floats must be 16 B aligned).  No atomics and no memset: two runs give the same bits.
+ *
+ * FOV crop (get_fov_flag o rect_to_img o lidar_to_rect, calibration_kitti.py:65-84, in double from the fp32 inputs in the
+ * operation order written in kitti_data.hip): fov_count writes out_counts (B) = kept rows per frame, overflow (1) = the
+ * total exceeds `capacity`, and, when flags != NULL, flags (total_rows) uint8 = 1 for a kept row; fov_fill writes the kept
+ * rows, frame after frame in input order, never at or past `capacity` rows.  workspace >= pdm_kitti_data_fov_workspace_bytes(B),
+ * shared by the two calls on one stream.
+ *
+ * Box membership: boxes (B, M, 7) fp32 lidar boxes, box_count (B) live boxes per frame.  boxes_count writes, per
+ * (frame, box), num_points_in_gt (B, M) = points inside the FOV and inside the exact oriented box (box_utils.in_hull's
+ * rule, in double) and db_count (B, M) = all points under points_in_boxes_cpu's rule (roiaware_pool3d.cpp:121-140, margin
+ * 1e-2: the very test of the augmentation's point removal), both 0 at or past box_count; totals (2) int64 = [database
+ * points P, database entries N = sum of box_count].  boxes_fill writes GTDatabase's layout: out_points (P, C) with xyz
+ * relative to `centres` (B, M, 3) float64 (fp32(double(x) - centre), the other columns unchanged), in point order within
+ * an entry; out_offsets (capacity_entries + 1) int64; out_boxes (N, 7).  Entries are ordered frame after frame, box after
+ * box; a point inside two boxes goes to both.  Nothing is written at or past capacity_points rows / capacity_entries
+ * entries.  workspace >= pdm_kitti_data_boxes_workspace_bytes(B, M), shared by boxes_count -> boxes_fill on one stream. */
+size_t pdm_kitti_data_fov_workspace_bytes(int B);
+size_t pdm_kitti_data_boxes_workspace_bytes(int B, int M);
+int pdm_kitti_data_fov_count(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,
+                             const float *V2C, const float *R0, const float *P2, const int *image_shape, long long capacity,
+                             int *out_counts, int *overflow, unsigned char *flags, void *workspace, size_t workspace_bytes);
+int pdm_kitti_data_fov_fill(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,
+                            const float *V2C, const float *R0, const float *P2, const int *image_shape, long long capacity,
+                            int *out_counts, int *overflow, float *out_rows, void *workspace, size_t workspace_bytes);
+int pdm_kitti_data_boxes_count(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,
+                               const float *V2C, const float *R0, const float *P2, const int *image_shape, int M,
+                               const float *boxes, const int *box_count, int *num_points_in_gt, int *db_count,
+                               long long *totals, void *workspace, size_t workspace_bytes);
+int pdm_kitti_data_boxes_fill(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,
+                              const float *V2C, const float *R0, const float *P2, const int *image_shape, int M,
+                              const float *boxes, const int *box_count, const double *centres, int *num_points_in_gt,
+                              int *db_count, long long *totals, long long capacity_points, long long capacity_entries,
+                              float *out_points, long long *out_offsets, float *out_boxes, void *workspace,
+                              size_t workspace_bytes);
+
 /* ---- rows form of the FP module's input for the training path (csrc/interpolate.hip) --------------------------------
  * out (B, n, ld) bf16 = [ three_interpolate(known, idx, weight) (C2) | skip (C1) | zeros ]: the reference's
  * cat([interpolated, unknow_feats], dim=1) (pointnet2_modules.py:158-165) written once as the rows the bf16 layers read, each

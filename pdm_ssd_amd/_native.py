@@ -75,6 +75,11 @@ _SIGNATURES = {
     "pdm_augment_scene_fill": [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp, _vp, ctypes.c_longlong,
                                _vp, _vp, _vp, _vp, ctypes.c_size_t],
     "pdm_kitti_boxes_to_camera": [_i, _i] + [_vp] * 9,
+    "pdm_kitti_data_fov_count": [_i, _i, ctypes.c_longlong] + [_vp] * 6 + [ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_size_t],
+    "pdm_kitti_data_fov_fill": [_i, _i, ctypes.c_longlong] + [_vp] * 6 + [ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_size_t],
+    "pdm_kitti_data_boxes_count": [_i, _i, ctypes.c_longlong] + [_vp] * 6 + [_i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t],
+    "pdm_kitti_data_boxes_fill": [_i, _i, ctypes.c_longlong] + [_vp] * 6 + [_i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong,
+                                  ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_size_t],
     "pdm_kitti_eval_overlaps": [_i, _vp, _vp, _vp, ctypes.c_longlong, _i] + [_vp] * 6,
     "pdm_kitti_eval_dt_flags": [ctypes.c_longlong, _vp, _vp, _i, _vp, _i, _vp, _vp],
     "pdm_kitti_eval_pass1": [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp,
@@ -182,7 +187,8 @@ _SIGNATURES = {
 EXPORTS = ["pdm_abi_version", "pdm_last_error", "pdm_ball_query_grid_workspace_bytes",
            "pdm_three_nn_grid_workspace_bytes", "pdm_furthest_point_sampling_ws_bytes",
            "pdm_fps_max_coresident_workgroups",
-           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_kitti_eval_workspace_bytes", "pdm_sa_pack_workspace_bytes",
+           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_kitti_eval_workspace_bytes", "pdm_kitti_data_fov_workspace_bytes",
+           "pdm_kitti_data_boxes_workspace_bytes", "pdm_sa_pack_workspace_bytes",
            "pdm_sa_pack_rows", "pdm_rows_mlp_x3_stream_bytes", "pdm_point_head_loss_workspace_bytes", "pdm_heatmap_focal_loss_workspace_bytes", "pdm_three_interpolate_grad_ws_bytes",
            "pdm_group_points_grad_ws_bytes", "pdm_group_concat_cl_grad_ws_bytes", "pdm_bn_parts", "pdm_bn_pool_parts",
            "pdm_tg_stats_parts", "pdm_tg_dy_stats_parts", "pdm_tg_wgrad_ws_bytes", "pdm_tg_colsum_ws_floats"] + list(_SIGNATURES)
@@ -238,6 +244,10 @@ def lib():
         l.pdm_augment_workspace_bytes.argtypes = [_i, _i]
         l.pdm_kitti_eval_workspace_bytes.restype = ctypes.c_size_t
         l.pdm_kitti_eval_workspace_bytes.argtypes = [_i, _i]
+        l.pdm_kitti_data_fov_workspace_bytes.restype = ctypes.c_size_t
+        l.pdm_kitti_data_fov_workspace_bytes.argtypes = [_i]
+        l.pdm_kitti_data_boxes_workspace_bytes.restype = ctypes.c_size_t
+        l.pdm_kitti_data_boxes_workspace_bytes.argtypes = [_i, _i]
         l.pdm_bn_pool_parts.restype = _i
         l.pdm_bn_pool_parts.argtypes = [_i, ctypes.c_longlong, _i]
         l.pdm_tg_colsum_ws_floats.restype = ctypes.c_size_t

@@ -91,10 +91,7 @@ __device__ __forceinline__ unsigned ag_perm(unsigned i, unsigned n, unsigned kp)
     return x;
 }
 
-__device__ __forceinline__ void ag_cos_sin(float a, float *c, float *s) {
-    *c = (float)cos((double)a);
-    *s = (float)sin((double)a);
-}
+__device__ __forceinline__ void ag_cos_sin(float a, float *c, float *s) { box_cos_sin(a, c, s); }
 
 // (x, y, z) through the scene's transform list (points: h == nullptr, dims == nullptr)
 __device__ __forceinline__ void ag_world(unsigned ops, int flip, float c, float s, float angle, float scale, float &x,
@@ -376,11 +373,7 @@ __device__ __forceinline__ AGRowCtx ag_scene_setup(const AGScene &a, const AGWor
         ag_cos_sin(-bx[6], &c, &s);
         L.cs[2 * k] = c;
         L.cs[2 * k + 1] = s;
-        // a point inside lies within sqrt((dx/2 + 0.01)^2 + (dy/2 + 0.01)^2) <= r + 0.0142 of the centre; the rest of
-        // the slack covers the rounding of the local coordinates and of this bound (NaN: never rejected)
-        const float r = ag_radius(bx);
-        const float lim = r * 1.001f + 0.02f + 4e-5f * (fabsf(bx[0]) + fabsf(bx[1]) + r + 1.f);
-        L.lim2[k] = lim * lim;
+        L.lim2[k] = box_reach2(bx);   // bounding-circle reject radius (box_geometry.h)
     }
     x.obj_total = oo[x.nacc];
     ag_cos_sin(a.angle[b], &x.c, &x.s);
@@ -413,12 +406,7 @@ __device__ __forceinline__ bool ag_row(const AGScene &a, const AGWorld &wd, cons
             const float *bx = L.box + k * 7;
             const float dx = px - bx[0], dy = py - bx[1];
             if (dx * dx + dy * dy > L.lim2[k]) continue;
-            if ((double)fabsf(pz - bx[2]) > (double)bx[5] / 2.0) continue;
-            const float c = L.cs[2 * k], s = L.cs[2 * k + 1];
-            const float lx = __fadd_rn(__fmul_rn(dx, c), __fmul_rn(dy, -s));
-            const float ly = __fadd_rn(__fmul_rn(dx, s), __fmul_rn(dy, c));
-            if ((double)fabsf(lx) < (double)bx[3] / 2.0 + (double)1e-2f && (double)fabsf(ly) < (double)bx[4] / 2.0 + (double)1e-2f)
-                return false;
+            if (point_in_box_margin(dx, dy, pz, bx, L.cs[2 * k], L.cs[2 * k + 1])) return false;
         }
     }
     ag_world(wd.ops, x.flip, x.c, x.s, x.angle, x.scale, px, py, pz, nullptr, nullptr);

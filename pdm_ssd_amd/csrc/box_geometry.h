@@ -112,4 +112,29 @@ __device__ __forceinline__ float iou_normal(const float *a, const float *b) {
     return inter / fmaxf(a[3] * a[4] + b[3] * b[4] - inter, 1e-8f);
 }
 
+// ---- point-in-box with points_in_boxes_cpu's margin (roiaware_pool3d.cpp:121-140), shared by the augmentation's point
+// removal (augment.hip) and the ground-truth database builder (kitti_data.hip) so that both evaluate one and the same
+// test.  c, s = box_cos_sin(-heading); dx, dy = fp32 (point - centre).  The local coordinates are fp32, one rounding at a
+// time; the comparisons are in double.  The callers' translation units are built with -ffp-contract=off.
+__device__ __forceinline__ void box_cos_sin(float a, float *c, float *s) {
+    *c = (float)cos((double)a);
+    *s = (float)sin((double)a);
+}
+
+// squared bounding-circle reject radius of the margin test: a point inside lies within
+// sqrt((dx/2 + 0.01)^2 + (dy/2 + 0.01)^2) <= r + 0.0142 of the centre; the rest of the slack covers the rounding of the
+// local coordinates and of this bound (NaN: never rejected)
+__device__ __forceinline__ float box_reach2(const float *bx) {
+    const float r = 0.5f * sqrtf(bx[3] * bx[3] + bx[4] * bx[4]);
+    const float lim = r * 1.001f + 0.02f + 4e-5f * (fabsf(bx[0]) + fabsf(bx[1]) + r + 1.f);
+    return lim * lim;
+}
+
+__device__ __forceinline__ bool point_in_box_margin(float dx, float dy, float pz, const float *bx, float c, float s) {
+    if ((double)fabsf(pz - bx[2]) > (double)bx[5] / 2.0) return false;
+    const float lx = __fadd_rn(__fmul_rn(dx, c), __fmul_rn(dy, -s));
+    const float ly = __fadd_rn(__fmul_rn(dx, s), __fmul_rn(dy, c));
+    return (double)fabsf(lx) < (double)bx[3] / 2.0 + (double)1e-2f && (double)fabsf(ly) < (double)bx[4] / 2.0 + (double)1e-2f;
+}
+
 }  // namespace pdm

@@ -62,12 +62,8 @@ struct AGWorld {          // the per-scene transform: ops = up to 4 nibbles (1 f
     float extra[3];
 };
 
-__device__ __host__ __forceinline__ unsigned ag_fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
 __device__ __forceinline__ unsigned ag_scene_key(unsigned seed, unsigned step, unsigned b, unsigned s) {
-    return ag_fmix32(ag_fmix32(seed ^ step * 0x85EBCA6Bu) ^ b * 0x9E3779B1u ^ s * 0x7F4A7C15u);
+    return fmix32(fmix32(seed ^ step * 0x85EBCA6Bu) ^ b * 0x9E3779B1u ^ s * 0x7F4A7C15u);
 }
 __device__ __forceinline__ float ag_uniform(float lo, float hi, unsigned k) {
     const float u = (float)(k >> 8) * 0x1p-24f;
@@ -81,7 +77,7 @@ __device__ __forceinline__ unsigned ag_perm(unsigned i, unsigned n, unsigned kp)
     do {
         unsigned L = x >> w, R = x & mask;
         for (unsigned r = 0; r < 4; ++r) {
-            const unsigned f = ag_fmix32(kp ^ R * 0x9E3779B1u ^ (r + 1u) * 0x7F4A7C15u) & mask;
+            const unsigned f = fmix32(kp ^ R * 0x9E3779B1u ^ (r + 1u) * 0x7F4A7C15u) & mask;
             const unsigned t = L ^ f;
             L = R;
             R = t;
@@ -90,8 +86,6 @@ __device__ __forceinline__ unsigned ag_perm(unsigned i, unsigned n, unsigned kp)
     } while (x >= n);
     return x;
 }
-
-__device__ __forceinline__ void ag_cos_sin(float a, float *c, float *s) { box_cos_sin(a, c, s); }
 
 // (x, y, z) through the scene's transform list (points: h == nullptr, dims == nullptr)
 __device__ __forceinline__ void ag_world(unsigned ops, int flip, float c, float s, float angle, float scale, float &x,
@@ -119,28 +113,6 @@ __device__ __forceinline__ void ag_world(unsigned ops, int flip, float c, float 
 
 __device__ __forceinline__ bool ag_in_range_xy(const float *r, float x, float y) {
     return x >= r[0] && x <= r[3] && y >= r[1] && y <= r[4];
-}
-
-// block-wide exclusive scan of one int per thread (AG_THREADS threads); *total = block sum
-__device__ __forceinline__ int ag_block_scan(int v, int *s_wave, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < AG_THREADS / 64; ++w) {
-        const int x = s_wave[w];
-        if (w < wave) base += x;
-        tot += x;
-    }
-    *total = tot;
-    return base + incl - v;
 }
 
 // ---- draw: state + seed -> sampled database indices (-1 padded), flip bits, angle, scale ------------------------------
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(1024) void ag_draw_kernel(int B, AGGroups g, int li
             if (j < 0 || j >= g.num[t]) continue;
             const int *w = walk + ((size_t)b * AG_MAXG + t) * 3;
             if (j < w[2]) {
-                const unsigned kp = ag_fmix32(ag_fmix32(seed ^ 0x5BD1E995u ^ (unsigned)t * 0x9E3779B1u) + (unsigned)w[0] * 0x85EBCA6Bu);
+                const unsigned kp = fmix32(fmix32(seed ^ 0x5BD1E995u ^ (unsigned)t * 0x9E3779B1u) + (unsigned)w[0] * 0x85EBCA6Bu);
                 out = g.first[t] + (int)ag_perm((unsigned)(w[1] + j), (unsigned)g.len[t], kp);
             }
         }
@@ -211,8 +183,6 @@ struct AGSelect {
     int *out_nbox, *accepted, *num_accepted, *obj_off;
 };
 
-__device__ __forceinline__ float ag_radius(const float *box) { return 0.5f * sqrtf(box[3] * box[3] + box[4] * box[4]); }
-
 __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGroups g, AGWorld wd) {
     __shared__ float ex[(AG_MAXM + AG_MAXK) * 7];
     __shared__ float exr[AG_MAXM + AG_MAXK];
@@ -231,11 +201,11 @@ __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGro
         const int m = m0 + tid;
         const float *src = a.gt + ((size_t)b * a.M + m) * 8;
         const bool present = m < a.M && src[7] != 0.f;
-        const int pos = n_exist + ag_block_scan(present ? 1 : 0, s_wave, &tot);
+        const int pos = n_exist + block_scan<AG_THREADS>(present ? 1 : 0, s_wave, &tot);
         if (present) {
             for (int f = 0; f < 7; ++f) ex[pos * 7 + f] = src[f];
             exc[pos] = src[7];
-            exr[pos] = ag_radius(src);
+            exr[pos] = bev_radius(src);
         }
         n_exist += tot;
     }
@@ -250,7 +220,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGro
             s_idx[tid] = idx;
             if (idx >= 0) {
                 for (int f = 0; f < 7; ++f) cand[tid * 7 + f] = a.db_boxes[(size_t)idx * 7 + f];
-                crad[tid] = ag_radius(cand + tid * 7);
+                crad[tid] = bev_radius(cand + tid * 7);
             }
         }
         __syncthreads();
@@ -268,7 +238,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGro
                 if (!(box_overlap_bev(me, cand + c * 7) == 0.f)) valid = false;
             }
         }
-        const int r = ag_block_scan(valid ? 1 : 0, s_wave, &tot);
+        const int r = block_scan<AG_THREADS>(valid ? 1 : 0, s_wave, &tot);
         if (valid) {
             const int pos = n_exist + r;
             for (int f = 0; f < 7; ++f) ex[pos * 7 + f] = cand[tid * 7 + f];
@@ -294,7 +264,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGro
 
     // box outputs: [target scene boxes] + [accepted], transformed, heading wrapped, range-masked, compacted, zero-padded
     float c = 1.f, s = 0.f;
-    ag_cos_sin(a.angle[b], &c, &s);
+    box_cos_sin(a.angle[b], &c, &s);
     const int fl = a.flip[b];
     const float ang = a.angle[b], sc = a.scale[b];
     int n_out = 0;
@@ -311,7 +281,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_select_kernel(AGSelect a, AGGro
                    (bx[0] >= wd.range[0] && bx[0] <= wd.range[3] && bx[1] >= wd.range[1] && bx[1] <= wd.range[4] &&
                     bx[2] >= wd.range[2] && bx[2] <= wd.range[5]);
         }
-        const int pos = n_out + ag_block_scan(keep ? 1 : 0, s_wave, &tot);
+        const int pos = n_out + block_scan<AG_THREADS>(keep ? 1 : 0, s_wave, &tot);
         if (keep && pos < a.M_out)
             for (int f = 0; f < 8; ++f) a.out_boxes[((size_t)b * a.M_out + pos) * 8 + f] = bx[f];
         n_out += tot;
@@ -370,13 +340,13 @@ __device__ __forceinline__ AGRowCtx ag_scene_setup(const AGScene &a, const AGWor
         bx[4] = __fadd_rn(bx[4], wd.extra[1]);
         bx[5] = __fadd_rn(bx[5], wd.extra[2]);
         float c, s;
-        ag_cos_sin(-bx[6], &c, &s);
+        box_cos_sin(-bx[6], &c, &s);
         L.cs[2 * k] = c;
         L.cs[2 * k + 1] = s;
         L.lim2[k] = box_reach2(bx);   // bounding-circle reject radius (box_geometry.h)
     }
     x.obj_total = oo[x.nacc];
-    ag_cos_sin(a.angle[b], &x.c, &x.s);
+    box_cos_sin(a.angle[b], &x.c, &x.s);
     x.angle = a.angle[b];
     x.scale = a.scale[b];
     x.flip = a.flip[b];
@@ -441,16 +411,20 @@ __global__ __launch_bounds__(AG_THREADS) void ag_count_kernel(AGScene a, AGWorld
     }
 }
 
-__global__ __launch_bounds__(1024) void ag_scan_kernel(AGScene a) {
+// seg_count (B, W) -> seg_base, out_counts, offsets (B + 1), overflow: see common.h.  One workgroup, thread b = frame b.
+__global__ __launch_bounds__(1024) void segment_scan_kernel(int B, int W, const int *__restrict__ seg_count,
+                                                            int *__restrict__ seg_base, int *__restrict__ out_counts,
+                                                            long long *__restrict__ offsets, int *__restrict__ overflow,
+                                                            long long capacity) {
     __shared__ long long s[1024];
     const int b = threadIdx.x;
     long long tot = 0;
-    if (b < a.B) {
-        for (int w = 0; w < a.W; ++w) {
-            a.seg_base[(size_t)b * a.W + w] = (int)tot;
-            tot += a.seg_count[(size_t)b * a.W + w];
+    if (b < B) {
+        for (int w = 0; w < W; ++w) {
+            seg_base[(size_t)b * W + w] = (int)tot;
+            tot += seg_count[(size_t)b * W + w];
         }
-        a.out_counts[b] = (int)tot;
+        out_counts[b] = (int)tot;
     }
     s[b] = tot;
     __syncthreads();
@@ -460,11 +434,18 @@ __global__ __launch_bounds__(1024) void ag_scan_kernel(AGScene a) {
         s[b] += v;
         __syncthreads();
     }
-    if (b < a.B) a.scene_off[b] = s[b] - tot;
+    if (b < B) offsets[b] = s[b] - tot;
     if (b == 0) {
-        a.scene_off[a.B] = s[1023];
-        a.overflow[0] = s[1023] > a.capacity ? 1 : 0;
+        offsets[B] = s[1023];
+        overflow[0] = s[1023] > capacity ? 1 : 0;
     }
+}
+
+int segment_scan_launch(void *stream, const char *what, int B, int W, const int *seg_count, int *seg_base, int *out_counts,
+                        long long *offsets, int *overflow, long long capacity) {
+    hipLaunchKernelGGL(segment_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), B, W, seg_count, seg_base, out_counts,
+                       offsets, overflow, capacity);
+    return check_launch(what);
 }
 
 __global__ __launch_bounds__(AG_THREADS) void ag_fill_kernel(AGScene a, AGWorld wd) {
@@ -480,7 +461,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_fill_kernel(AGScene a, AGWorld 
         const float *src = nullptr;
         const bool keep = r < r1 && ag_row(a, wd, L, x, r, px, py, pz, src);
         int tot;
-        const long long p = pos + ag_block_scan(keep ? 1 : 0, L.s_wave, &tot);
+        const long long p = pos + block_scan<AG_THREADS>(keep ? 1 : 0, L.s_wave, &tot);
         if (keep && p < a.capacity) {
             float *o = a.out + (size_t)p * a.C;
             o[0] = px; o[1] = py; o[2] = pz;
@@ -492,8 +473,6 @@ __global__ __launch_bounds__(AG_THREADS) void ag_fill_kernel(AGScene a, AGWorld 
 
 static int ag_segments(int B) { return max(1, min(64, 2048 / max(B, 1))); }
 
-static size_t ag_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct AGLayout {
     size_t walk, obj_off, seg_count, seg_base, scene_off, total;
 };
@@ -502,11 +481,11 @@ static AGLayout ag_layout(int B, int K) {
     AGLayout l;
     const int W = ag_segments(B);
     size_t o = 0;
-    l.walk = o; o += ag_align((size_t)B * AG_MAXG * 3 * sizeof(int));
-    l.obj_off = o; o += ag_align((size_t)B * (K + 1) * sizeof(int));
-    l.seg_count = o; o += ag_align((size_t)B * W * sizeof(int));
-    l.seg_base = o; o += ag_align((size_t)B * W * sizeof(int));
-    l.scene_off = o; o += ag_align((size_t)(B + 1) * sizeof(long long));
+    l.walk = o; o += align256((size_t)B * AG_MAXG * 3 * sizeof(int));
+    l.obj_off = o; o += align256((size_t)B * (K + 1) * sizeof(int));
+    l.seg_count = o; o += align256((size_t)B * W * sizeof(int));
+    l.seg_base = o; o += align256((size_t)B * W * sizeof(int));
+    l.scene_off = o; o += align256((size_t)(B + 1) * sizeof(long long));
     l.total = o;
     return l;
 }
@@ -658,8 +637,8 @@ extern "C" int pdm_augment_scene_count(void *stream, int B, int C, const float *
     hipLaunchKernelGGL(ag_count_kernel, dim3(a.W, B), dim3(AG_THREADS), 0, as_stream(stream), a, wd);
     int e = check_launch("augment_scene_count(count)");
     if (e) return e;
-    hipLaunchKernelGGL(ag_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), a);
-    return check_launch("augment_scene_count(scan)");
+    return segment_scan_launch(stream, "augment_scene_count(scan)", B, a.W, a.seg_count, a.seg_base, a.out_counts, a.scene_off,
+                               a.overflow, a.capacity);
 }
 
 extern "C" int pdm_augment_scene_fill(void *stream, int B, int C, const float *raw, const int *counts,

@@ -1,5 +1,7 @@
-// Rotated-box BEV geometry shared by iou3d_nms.hip (pdm_nms, the pairwise IoU entries) and post_process.hip (the
-// batched post-processing), so that both evaluate one and the same IoU function, operation for operation.
+// Rotated-box geometry, one definition per function so that every operator evaluates it operation for operation:
+//   box_overlap_bev / iou_bev / iou_normal   iou3d_nms.hip, post_process.hip (through nms.h), augment.hip
+//   bev_radius / bev_circles_disjoint        the bounding-circle prefilter of those
+//   box_cos_sin / box_reach2 / point_in_box_margin   the point-in-box test of augment.hip and kitti_data.hip
 // Boxes are 7 floats [x, y, z, dx, dy, dz, heading]; see iou3d_nms.hip for the geometry.
 #pragma once
 #include "common.h"
@@ -90,6 +92,9 @@ __device__ inline float box_overlap_bev(const float *a, const float *b) {
     return fabsf(area) / 2.0f;
 }
 
+// radius of the BEV footprint's bounding circle
+__device__ __forceinline__ float bev_radius(const float *box) { return 0.5f * sqrtf(box[3] * box[3] + box[4] * box[4]); }
+
 // bounding-circle prefilter: true only if the two BEV footprints are certainly disjoint (then box_overlap_bev and
 // iou_normal both return an overlap of exactly 0).  The margin covers inside_box's 1e-2 tolerance (a corner within
 // 1e-2 of the other box lies within its circle radius + 0.0142) plus the rounding of corners and distances.
@@ -125,7 +130,7 @@ __device__ __forceinline__ void box_cos_sin(float a, float *c, float *s) {
 // sqrt((dx/2 + 0.01)^2 + (dy/2 + 0.01)^2) <= r + 0.0142 of the centre; the rest of the slack covers the rounding of the
 // local coordinates and of this bound (NaN: never rejected)
 __device__ __forceinline__ float box_reach2(const float *bx) {
-    const float r = 0.5f * sqrtf(bx[3] * bx[3] + bx[4] * bx[4]);
+    const float r = bev_radius(bx);
     const float lim = r * 1.001f + 0.02f + 4e-5f * (fabsf(bx[0]) + fabsf(bx[1]) + r + 1.f);
     return lim * lim;
 }

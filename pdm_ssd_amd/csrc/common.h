@@ -23,9 +23,53 @@ bool csr_form_applies(int b, int row_len, long long ne, int m);
 int csr_scatter_grad_launch(void *stream, const char *who, int b, int c, int row_len, int per, int m, const float *grad_out,
                             const int *idx, const float *weight, float *grad_points, void *workspace);
 
+// Ragged compaction in W segments per frame (augment.hip, kitti_data.hip; defined in augment.hip): seg_count (B, W) ->
+// seg_base (B, W) the exclusive prefix inside the frame, out_counts (B) the frame totals, offsets (B + 1) their exclusive
+// prefix over the frames, overflow[0] = offsets[B] > capacity.  B <= 1024.
+int segment_scan_launch(void *stream, const char *what, int B, int W, const int *seg_count, int *seg_base, int *out_counts,
+                        long long *offsets, int *overflow, long long capacity);
+
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int divup(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// workspace sections start on 256-byte boundaries
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the murmur3 finaliser behind every counter-based draw (input_path.hip, augment.hip)
+__device__ __host__ __forceinline__ unsigned fmix32(unsigned h) {
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+
+// how many lanes below `lane` are set in a ballot: the lane's rank among the hits
+__device__ __forceinline__ int lanes_below(unsigned long long mask, int lane) {
+    return __popcll(mask & ((1ull << lane) - 1ull));
+}
+
+// block-wide exclusive scan of one int per thread (NT threads, every one calls it); returns the exclusive prefix,
+// *total = block sum.  s_wave: NT / 64 ints of LDS, reusable by the next call at once.
+template <int NT>
+__device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += t;
+    }
+    __syncthreads();                      // s_wave reuse across calls
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int w = 0; w < NT / 64; ++w) {
+        const int x = s_wave[w];
+        if (w < wave) base += x;
+        tot += x;
+    }
+    *total = tot;
+    return base + incl - v;
+}
 
 // Squared distance with the rounding sequence pinned:
 //   d = fma(dz,dz, fma(dy,dy, rn(dx*dx)))

@@ -8,49 +8,22 @@
 //   key_s(i) = fmix32(fmix32(seed ^ cloud * 0x9E3779B1 ^ s * 0x7F4A7C15) + i * 0x9E3779B9)     (murmur3 finaliser)
 //   "k random points of a set"  := the k members with the smallest (key_1, i)
 //   "shuffle"                   := ascending (key_2+copy(entry), i, copy) over the chosen entries.
-#include "common.h"
+#include "rank_select.h"
 
 namespace pdm {
 
-constexpr int IP_THREADS = 1024;
+constexpr int IP_THREADS = TK_THREADS;   // rank_select.h's workgroup
 constexpr int IP_MAXP = 16384;          // quota per cloud the in-LDS sort handles (128 KB of 8-byte items)
 
-__device__ __host__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
 __device__ __forceinline__ unsigned ip_key(unsigned base, unsigned i) { return fmix32(base + i * 0x9E3779B9u); }
-
-// block-wide exclusive scan of one int per thread (1024 threads); returns the exclusive prefix, *total = block sum
-__device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();                      // s_wave reuse across calls
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < IP_THREADS / 64; ++w) {
-        const int x = s_wave[w];
-        if (w < wave) base += x;
-        tot += x;
-    }
-    *total = tot;
-    return base + incl - v;
-}
 
 __global__ __launch_bounds__(IP_THREADS) void sample_points_kernel(int B, int P, unsigned seed, int C,
                                                                   const float *__restrict__ raw,
                                                                   const int *__restrict__ counts,
                                                                   float *__restrict__ out, int *__restrict__ choice_out) {
     extern __shared__ unsigned long long s_items[];   // P2 sort items
-    __shared__ int s_hist[256];
-    __shared__ int s_wave[IP_THREADS / 64];
-    __shared__ int s_far, s_digit, s_before;
+    __shared__ alignas(16) RankLds lds;
+    __shared__ int s_far;
     const int cloud = blockIdx.x, tid = threadIdx.x;
     long long start = 0;
     for (int k = 0; k < cloud; ++k) start += counts[k];
@@ -85,29 +58,15 @@ __global__ __launch_bounds__(IP_THREADS) void sample_points_kernel(int B, int P,
     const int K = mode == 0 ? P - F : mode == 1 ? P : min(P - N, N);
     auto candidate = [&](int i) { return mode == 0 ? is_near(i) : true; };
 
-    // ---- K-th smallest key among the candidates: 4 rounds of 8-bit radix select ----------------------------------
-    unsigned prefix = 0, pmask = 0;
-    int remaining = K;                     // rank still to locate inside the current prefix bucket
-    if (K > 0) {
-        for (int round = 0; round < 4; ++round) {
-            const int shift = 24 - 8 * round;
-            for (int d = tid; d < 256; d += IP_THREADS) s_hist[d] = 0;
-            __syncthreads();
-            for (int i = tid; i < N; i += IP_THREADS) {
-                if (!candidate(i)) continue;
-                const unsigned k = ip_key(base1, (unsigned)i);
-                if ((k & pmask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid < 64) radix_pick256(s_hist, remaining, &s_digit, &s_before);
-            __syncthreads();
-            prefix |= (unsigned)s_digit << shift;
-            pmask |= 255u << shift;
-            remaining -= s_before;
-            __syncthreads();
-        }
-    }
-    const unsigned T = prefix;             // the K-th smallest key; `remaining` = how many keys == T are taken (by index)
+    // ---- T = K-th smallest key among the candidates (rank_select.h); `remaining` keys == T are taken, by index -----
+    unsigned T = 0;
+    int remaining = 0;
+    if (K > 0)
+        T = radix_kth_key(N, K, [&](int i, unsigned &k) {
+            if (!candidate(i)) return false;
+            k = ip_key(base1, (unsigned)i);
+            return true;
+        }, lds, &remaining);
 
     // ---- emission in index order: entry = (point i, copy) -> 8-byte sort item (key2 | i | copy) --------------------
     const int P2 = 1 << (32 - __builtin_clz(max(P, 2) - 1));
@@ -127,12 +86,12 @@ __global__ __launch_bounds__(IP_THREADS) void sample_points_kernel(int B, int P,
             }
         }
         int tot_eq;
-        const int eq_rank = block_scan(is_eq ? 1 : 0, s_wave, &tot_eq);
+        const int eq_rank = block_scan<IP_THREADS>(is_eq ? 1 : 0, lds.wave, &tot_eq);
         if (is_eq && eq_taken + eq_rank < remaining) drawn = true;
         eq_taken += tot_eq;
         const int n_here = (base_member ? 1 : 0) + (drawn ? 1 : 0);
         int tot;
-        const int pos = emitted + block_scan(n_here, s_wave, &tot);
+        const int pos = emitted + block_scan<IP_THREADS>(n_here, lds.wave, &tot);
         emitted += tot;
         if (i < N) {
             int p = pos;
@@ -151,19 +110,7 @@ __global__ __launch_bounds__(IP_THREADS) void sample_points_kernel(int B, int P,
     __syncthreads();
 
     // ---- shuffle = bitonic sort of the P2 items ------------------------------------------------------------------
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int q = tid; q < P2; q += IP_THREADS) {
-                const int partner = q ^ j;
-                if (partner > q) {
-                    const unsigned long long a = s_items[q], b = s_items[partner];
-                    const bool up = (q & k) == 0;
-                    if ((a > b) == up) { s_items[q] = b; s_items[partner] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_items(s_items, P2);
 
     // ---- rows out: [batch index, the C floats of the point] --------------------------------------------------------
     for (int r = tid; r < P; r += IP_THREADS) {

@@ -7,7 +7,7 @@
 // MI355X-first difference: the reference copies the N x N/64 suppression mask to the host and reduces it there
 // (cudaMemcpy + a CPU loop per call); here a one-wave kernel walks the mask on the device (each lane owns 64-box
 // words of the `removed` set), so a call enqueues two kernels and nothing synchronises until the caller reads the count.
-#include "box_geometry.h"
+#include "nms.h"
 
 namespace pdm {
 
@@ -41,52 +41,21 @@ __global__ __launch_bounds__(256) void boxes_aligned_overlap_kernel(int n, const
 // mask (n, ceil(n/64)) : bit j of word (i, cb) set iff box 64 cb + j (> i) overlaps box i above the threshold
 __global__ __launch_bounds__(64) void nms_mask_kernel(int n, float thresh, int normal, const float *__restrict__ boxes,
                                                       unsigned long long *__restrict__ mask) {
-    __shared__ float col[64 * 7];
     const int row_start = blockIdx.y, col_start = blockIdx.x;
-    const int row_size = min(n - row_start * 64, 64), col_size = min(n - col_start * 64, 64);
-    for (int e = threadIdx.x; e < col_size * 7; e += 64) col[e] = boxes[(size_t)col_start * 64 * 7 + e];
-    __syncthreads();
-    if ((int)threadIdx.x >= row_size) return;
     const int cur = row_start * 64 + threadIdx.x;
-    float me[7];
-#pragma unroll
-    for (int f = 0; f < 7; ++f) me[f] = boxes[(size_t)cur * 7 + f];
-    unsigned long long t = 0;
-    if (col_start >= row_start) {   // earlier columns never matter: only later boxes can be suppressed by this one
-        const int start = row_start == col_start ? threadIdx.x + 1 : 0;
-        for (int i = start; i < col_size; ++i) {
-            const float v = normal ? iou_normal(me, col + i * 7) : iou_bev(me, col + i * 7);
-            if (v > thresh) t |= 1ull << i;
-        }
+    if (col_start < row_start) {   // earlier columns never matter: only later boxes can be suppressed by this one
+        if (cur < n) mask[(size_t)cur * gridDim.x + col_start] = 0ull;
+        return;
     }
-    mask[(size_t)cur * gridDim.x + col_start] = t;
+    const unsigned long long t = nms_mask_tile(n, boxes, row_start, col_start, thresh, normal != 0, false);
+    if (cur < n) mask[(size_t)cur * gridDim.x + col_start] = t;
 }
 
-// one wave: lane l owns the `removed` words of 64-box blocks l, l + 64, ... ; boxes are visited in score order
+// one wave, boxes visited in score order (nms.h's walk without a keep limit)
 __global__ __launch_bounds__(64) void nms_scan_kernel(int n, int col_blocks, const unsigned long long *__restrict__ mask,
                                                       long long *__restrict__ keep, int *__restrict__ num_out) {
-    constexpr int WPL = 4;   // words per lane: up to 64 * 4 * 64 = 16384 boxes
-    const int lane = threadIdx.x;
-    unsigned long long remv[WPL] = {0ull, 0ull, 0ull, 0ull};
-    int kept = 0;
-    for (int i = 0; i < n; ++i) {
-        const int nblock = i >> 6, inblock = i & 63;
-        const int owner = nblock & 63, slot = nblock >> 6;
-        unsigned long long w = slot == 0 ? remv[0] : slot == 1 ? remv[1] : slot == 2 ? remv[2] : remv[3];
-        const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)w, owner);
-        const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(w >> 32), owner);
-        const unsigned long long word = ((unsigned long long)hi << 32) | lo;
-        if ((word >> inblock) & 1ull) continue;   // wave-uniform
-        if (lane == 0) keep[kept] = i;
-        ++kept;
-        const unsigned long long *row = mask + (size_t)i * col_blocks;
-#pragma unroll
-        for (int s_ = 0; s_ < WPL; ++s_) {
-            const int cb = s_ * 64 + lane;
-            if (cb < col_blocks && cb >= nblock) remv[s_] |= row[cb];
-        }
-    }
-    if (lane == 0) *num_out = kept;
+    const int kept = nms_walk(n, n, mask, col_blocks, [&](int k, int i) { keep[k] = i; });
+    if (threadIdx.x == 0) *num_out = kept;
 }
 
 // more than 16384 boxes: the same walk with the `removed` words in LDS (col_blocks <= 16384 words = 128 KB)

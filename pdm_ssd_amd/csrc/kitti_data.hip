@@ -113,10 +113,6 @@ __device__ __forceinline__ void kd_xyz(const float *row, int C, float &x, float 
     }
 }
 
-__device__ __forceinline__ int kd_lanes_below(unsigned long long mask, int lane) {
-    return __popcll(mask & ((1ull << lane) - 1ull));
-}
-
 // ---- FOV crop ----------------------------------------------------------------------------------------------------------
 struct KDFov {
     KDFrames f;
@@ -150,32 +146,6 @@ __global__ __launch_bounds__(KD_THREADS) void kd_fov_count_kernel(KDFov a) {
     if (lane == 0) a.seg_count[(size_t)b * a.f.S + seg] = cnt;
 }
 
-__global__ __launch_bounds__(1024) void kd_fov_scan_kernel(KDFov a) {
-    __shared__ long long s[1024];
-    const int b = threadIdx.x;
-    long long tot = 0;
-    if (b < a.f.B) {
-        for (int w = 0; w < a.f.S; ++w) {
-            a.seg_base[(size_t)b * a.f.S + w] = (int)tot;
-            tot += a.seg_count[(size_t)b * a.f.S + w];
-        }
-        a.out_counts[b] = (int)tot;
-    }
-    s[b] = tot;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
-        const long long v = b >= off ? s[b - off] : 0;
-        __syncthreads();
-        s[b] += v;
-        __syncthreads();
-    }
-    if (b < a.f.B) a.frame_off[b] = s[b] - tot;
-    if (b == 0) {
-        a.frame_off[a.f.B] = s[1023];
-        a.overflow[0] = s[1023] > a.capacity ? 1 : 0;
-    }
-}
-
 __global__ __launch_bounds__(KD_THREADS) void kd_fov_fill_kernel(KDFov a) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, seg = blockIdx.x * KD_WAVES + (threadIdx.x >> 6);
     const KDCalib cal = kd_calib(a.f, b);
@@ -195,7 +165,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_fov_fill_kernel(KDFov a) {
             keep = kd_in_fov(cal, x, y, z);
         }
         const unsigned long long mask = __ballot(keep);
-        const long long p = pos + kd_lanes_below(mask, lane);
+        const long long p = pos + lanes_below(mask, lane);
         if (keep && p < a.capacity) {
             float *o = a.out + (size_t)p * C;
             if (C == 4) {
@@ -400,7 +370,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_box_fill_kernel(KDBoxes a) {
                 const bool in_db = near && point_in_box_margin(dx, dy, z, bx, L.cs[2 * k], L.cs[2 * k + 1]);
                 const unsigned long long mask = __ballot(in_db);
                 if (mask == 0ull) continue;
-                const long long p = __shfl(run[j], kk, 64) + kd_lanes_below(mask, lane);
+                const long long p = __shfl(run[j], kk, 64) + lanes_below(mask, lane);
                 if (in_db && p < a.cap_points) {
                     const double *ctr = a.centres + ((size_t)b * a.M + k) * 3;
                     float *o = a.out_points + (size_t)p * C;
@@ -422,17 +392,15 @@ __global__ __launch_bounds__(KD_THREADS) void kd_box_fill_kernel(KDBoxes a) {
 
 static int kd_segments(int B) { return KD_WAVES * max(1, min(64, 2048 / max(B, 1))); }
 
-static size_t kd_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct KDFovLayout { size_t seg_count, seg_base, frame_off, total; };
 
 static KDFovLayout kd_fov_layout(int B) {
     KDFovLayout l;
     const size_t S = kd_segments(B);
     size_t o = 0;
-    l.seg_count = o; o += kd_align((size_t)B * S * sizeof(int));
-    l.seg_base = o; o += kd_align((size_t)B * S * sizeof(int));
-    l.frame_off = o; o += kd_align((size_t)(B + 1) * sizeof(long long));
+    l.seg_count = o; o += align256((size_t)B * S * sizeof(int));
+    l.seg_base = o; o += align256((size_t)B * S * sizeof(int));
+    l.frame_off = o; o += align256((size_t)(B + 1) * sizeof(long long));
     l.total = o;
     return l;
 }
@@ -443,13 +411,13 @@ static KDBoxLayout kd_box_layout(int B, int M) {
     KDBoxLayout l;
     const size_t S = kd_segments(B), slots = (size_t)B * S * M * sizeof(int);
     size_t o = 0;
-    l.seg_hull = o; o += kd_align(slots);
-    l.seg_db = o; o += kd_align(slots);
-    l.seg_base = o; o += kd_align(slots);
-    l.within = o; o += kd_align((size_t)B * M * sizeof(int));
-    l.frame_tot = o; o += kd_align((size_t)B * sizeof(long long));
-    l.frame_off = o; o += kd_align((size_t)B * sizeof(long long));
-    l.entry_start = o; o += kd_align((size_t)B * sizeof(int));
+    l.seg_hull = o; o += align256(slots);
+    l.seg_db = o; o += align256(slots);
+    l.seg_base = o; o += align256(slots);
+    l.within = o; o += align256((size_t)B * M * sizeof(int));
+    l.frame_tot = o; o += align256((size_t)B * sizeof(long long));
+    l.frame_off = o; o += align256((size_t)B * sizeof(long long));
+    l.entry_start = o; o += align256((size_t)B * sizeof(int));
     l.total = o;
     return l;
 }
@@ -539,8 +507,8 @@ extern "C" int pdm_kitti_data_fov_count(void *stream, int B, int C, long long to
     hipLaunchKernelGGL(kd_fov_count_kernel, dim3(a.f.S / KD_WAVES, B), dim3(KD_THREADS), 0, as_stream(stream), a);
     const int e = check_launch("kitti_data_fov_count(count)");
     if (e) return e;
-    hipLaunchKernelGGL(kd_fov_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), a);
-    return check_launch("kitti_data_fov_count(scan)");
+    return segment_scan_launch(stream, "kitti_data_fov_count(scan)", B, a.f.S, a.seg_count, a.seg_base, a.out_counts, a.frame_off,
+                               a.overflow, a.capacity);
 }
 
 extern "C" int pdm_kitti_data_fov_fill(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,

@@ -11,13 +11,13 @@
 //             device-side count and blocks below the diagonal exit at once.  For thresh >= 0 a pair whose BEV bounding
 //             circles are disjoint (inflated past inside_box's 1e-2 tolerance and the rounding of the corners) has
 //             overlap 0, hence IoU 0, and is not evaluated; every other pair runs the same iou_bev / iou_normal as
-//             pdm_nms (box_geometry.h), so each segment's keep list is bit-identical to pdm_nms on the same boxes.
-//   scan      one wave per segment (the register `removed` walk of nms_scan_kernel), stops at POST_MAX keeps.
+//             pdm_nms (nms_mask_tile, nms.h), so each segment's keep list is bit-identical to pdm_nms on the same boxes.
+//   scan      one wave per segment (the register `removed` walk of pdm_nms: nms_walk, nms.h), stops at POST_MAX keeps.
 //   finalize  one workgroup per sample: the sample's class segments one after another (class 0's survivors, then
 //             class 1's, ...) as padded rows / boxes / scores / labels and a count; with gt boxes, the 3-D IoU of every
 //             kept box against every gt row (trailing all-zero rows trimmed) in the operation order of
 //             iou3d_nms_utils._iou3d_from_overlap, and the recall counts [gt, rcnn_t0, ...] summed over the batch.
-#include "box_geometry.h"
+#include "nms.h"
 #include "rank_select.h"
 
 namespace pdm {
@@ -89,9 +89,8 @@ __device__ __forceinline__ unsigned pp_key(const PPArgs &a, long long r, int k) 
 
 __global__ __launch_bounds__(TK_THREADS) void pp_select_kernel(PPArgs a) {
     extern __shared__ unsigned long long s_items[];
-    __shared__ int s_hist[256];
-    __shared__ int s_wave[TK_THREADS / 64];
-    __shared__ int s_digit, s_before, s_cnt, s_bad;
+    __shared__ alignas(16) RankLds lds;
+    __shared__ int s_cnt, s_bad;
     const int s = blockIdx.x, tid = threadIdx.x;
     const int b = a.multi ? s / a.C : s, k = a.multi ? s % a.C : 0;
     long long lo, hi;
@@ -115,63 +114,8 @@ __global__ __launch_bounds__(TK_THREADS) void pp_select_kernel(PPArgs a) {
     if (tid == 0) a.seg_n[s] = K;
     if (K == 0) return;
 
-    unsigned prefix = 0, pmask = 0;
-    int remaining = K;
-    for (int round = 0; round < 4; ++round) {
-        const int shift = 24 - 8 * round;
-        for (int d = tid; d < 256; d += TK_THREADS) s_hist[d] = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += TK_THREADS) {
-            const unsigned key = pp_key(a, lo + i, k);
-            if ((key & pmask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid < 64) radix_pick256(s_hist, remaining, &s_digit, &s_before);
-        __syncthreads();
-        prefix |= (unsigned)s_digit << shift;
-        pmask |= 255u << shift;
-        remaining -= s_before;
-        __syncthreads();
-    }
-    const unsigned T = prefix;   // key of the K-th ranked candidate (K <= #candidates, so T is a candidate's key)
-
-    const int K2 = 1 << (32 - __builtin_clz(max(K, 2) - 1));
-    for (int q = tid; q < K2; q += TK_THREADS) s_items[q] = ~0ull;
-    __syncthreads();
-    int lt_seen = 0, eq_seen = 0;
-    for (int c0 = 0; c0 < n; c0 += TK_THREADS) {
-        const int i = c0 + tid;
-        unsigned key = 0xffffffffu;
-        bool is_lt = false, is_eq = false;
-        if (i < n) {
-            key = pp_key(a, lo + i, k);
-            is_lt = key < T;
-            is_eq = key == T;
-        }
-        int tot;
-        const int both = tk_block_scan((is_lt ? 1 : 0) | (is_eq ? 1 << 16 : 0), s_wave, &tot);
-        const int lt_rank = both & 0xffff, eq_rank = both >> 16;
-        const int eq_before = min(eq_seen + eq_rank, remaining);
-        const bool take = is_lt || (is_eq && eq_seen + eq_rank < remaining);
-        const int pos = lt_seen + lt_rank + eq_before;
-        if (take && pos < K) s_items[pos] = ((unsigned long long)key << 32) | (unsigned)i;
-        lt_seen += tot & 0xffff;
-        eq_seen += tot >> 16;
-    }
-    __syncthreads();
-    for (int kk = 2; kk <= K2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int q = tid; q < K2; q += TK_THREADS) {
-                const int partner = q ^ j;
-                if (partner > q) {
-                    const unsigned long long x = s_items[q], y = s_items[partner];
-                    const bool up = (q & kk) == 0;
-                    if ((x > y) == up) { s_items[q] = y; s_items[partner] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // K <= #candidates, so every selected key is a candidate's
+    rank_select(n, K, [&](int i) { return pp_key(a, lo + i, k); }, s_items, lds);
     const size_t base = (size_t)s * a.pre;
     for (int r = tid; r < K; r += TK_THREADS) {
         const long long row = lo + (long long)(unsigned)(s_items[r] & 0xffffffffull);
@@ -187,65 +131,22 @@ __global__ __launch_bounds__(TK_THREADS) void pp_select_kernel(PPArgs a) {
     }
 }
 
-__device__ __forceinline__ float pp_radius(const float *box) { return 0.5f * sqrtf(box[3] * box[3] + box[4] * box[4]); }
-
 __global__ __launch_bounds__(64) void pp_mask_kernel(PPArgs a) {
-    __shared__ float col[64 * 7];
-    __shared__ float crad[64];
     const int s = blockIdx.z, row_start = blockIdx.y, col_start = blockIdx.x;
     const int n = a.seg_n[s];
     if (col_start < row_start || col_start * 64 >= n) return;   // never read by the scan
-    const float *boxes = a.sel_boxes + (size_t)s * a.pre * 7;
-    const int row_size = min(n - row_start * 64, 64), col_size = min(n - col_start * 64, 64);
-    for (int e = threadIdx.x; e < col_size * 7; e += 64) col[e] = boxes[(size_t)col_start * 64 * 7 + e];
-    __syncthreads();
-    if ((int)threadIdx.x < col_size) crad[threadIdx.x] = pp_radius(col + threadIdx.x * 7);
-    __syncthreads();
-    if ((int)threadIdx.x >= row_size) return;
+    const unsigned long long t = nms_mask_tile(n, a.sel_boxes + (size_t)s * a.pre * 7, row_start, col_start, a.nms_thresh,
+                                               a.normal != 0, a.nms_thresh >= 0.f);
     const int cur = row_start * 64 + threadIdx.x;
-    float me[7];
-#pragma unroll
-    for (int f = 0; f < 7; ++f) me[f] = boxes[(size_t)cur * 7 + f];
-    const float mr = pp_radius(me);
-    const bool prefilter = a.nms_thresh >= 0.f;
-    unsigned long long t = 0;
-    const int start = row_start == col_start ? threadIdx.x + 1 : 0;
-    for (int i = start; i < col_size; ++i) {
-        const float *o = col + i * 7;
-        if (prefilter && bev_circles_disjoint(me[0], me[1], mr, o[0], o[1], crad[i])) continue;
-        const float v = a.normal ? iou_normal(me, o) : iou_bev(me, o);
-        if (v > a.nms_thresh) t |= 1ull << i;
-    }
-    a.mask[((size_t)s * a.pre + cur) * a.cb + col_start] = t;
+    if (cur < n) a.mask[((size_t)s * a.pre + cur) * a.cb + col_start] = t;
 }
 
-// one wave per segment: lane l owns the `removed` words of 64-box blocks l, l + 64, ... (nms_scan_kernel's walk)
+// one wave per segment: nms.h's walk, stops at POST_MAX keeps
 __global__ __launch_bounds__(64) void pp_scan_kernel(PPArgs a) {
-    constexpr int WPL = 4;   // 64 * 4 words of 64 boxes: PP_MAX_PRE
-    const int s = blockIdx.x, lane = threadIdx.x;
-    const int n = a.seg_n[s], ncb = (n + 63) / 64;
-    const unsigned long long *mask = a.mask + (size_t)s * a.pre * a.cb;
+    const int s = blockIdx.x;
     int *keep = a.keep + (size_t)s * a.postc;
-    unsigned long long remv[WPL] = {0ull, 0ull, 0ull, 0ull};
-    int kept = 0;
-    for (int i = 0; i < n && kept < a.post; ++i) {
-        const int nblock = i >> 6, inblock = i & 63;
-        const int owner = nblock & 63, slot = nblock >> 6;
-        const unsigned long long w = slot == 0 ? remv[0] : slot == 1 ? remv[1] : slot == 2 ? remv[2] : remv[3];
-        const unsigned wlo = __builtin_amdgcn_readlane((int)(unsigned)w, owner);
-        const unsigned whi = __builtin_amdgcn_readlane((int)(unsigned)(w >> 32), owner);
-        const unsigned long long word = ((unsigned long long)whi << 32) | wlo;
-        if ((word >> inblock) & 1ull) continue;   // wave-uniform
-        if (lane == 0) keep[kept] = i;
-        ++kept;
-        const unsigned long long *row = mask + (size_t)i * a.cb;
-#pragma unroll
-        for (int s_ = 0; s_ < WPL; ++s_) {
-            const int cb = s_ * 64 + lane;
-            if (cb < ncb && cb >= nblock) remv[s_] |= row[cb];
-        }
-    }
-    if (lane == 0) a.seg_kept[s] = kept;
+    const int kept = nms_walk(a.seg_n[s], a.post, a.mask + (size_t)s * a.pre * a.cb, a.cb, [&](int k, int i) { keep[k] = i; });
+    if (threadIdx.x == 0) a.seg_kept[s] = kept;
 }
 
 // iou3d_nms_utils._iou3d_from_overlap for one (box, gt) pair, operation for operation (-ffp-contract=off); torch.min /
@@ -348,8 +249,6 @@ __global__ __launch_bounds__(PP_FIN_THREADS) void pp_finalize_kernel(PPArgs a) {
     if (tid < a.nt && s_cnt[tid] > 0) atomicAdd(&a.recall[1 + tid], (unsigned long long)s_cnt[tid]);
 }
 
-static inline size_t pp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PPLayout {
     size_t mask, sel_boxes, sel_scores, sel_rows, sel_labels, seg_n, keep, seg_kept, total;
 };
@@ -358,14 +257,14 @@ static PPLayout pp_layout(int S, int pre, int post) {
     const size_t s = (size_t)S, p = (size_t)pre, cb = (size_t)((pre + 63) / 64), postc = (size_t)(post < pre ? post : pre);
     PPLayout l;
     size_t off = 0;
-    l.mask = off;       off += pp_align(s * p * cb * sizeof(unsigned long long));
-    l.sel_boxes = off;  off += pp_align(s * p * 7 * sizeof(float));
-    l.sel_scores = off; off += pp_align(s * p * sizeof(float));
-    l.sel_rows = off;   off += pp_align(s * p * sizeof(int));
-    l.sel_labels = off; off += pp_align(s * p * sizeof(int));
-    l.seg_n = off;      off += pp_align(s * sizeof(int));
-    l.keep = off;       off += pp_align(s * postc * sizeof(int));
-    l.seg_kept = off;   off += pp_align(s * sizeof(int));
+    l.mask = off;       off += align256(s * p * cb * sizeof(unsigned long long));
+    l.sel_boxes = off;  off += align256(s * p * 7 * sizeof(float));
+    l.sel_scores = off; off += align256(s * p * sizeof(float));
+    l.sel_rows = off;   off += align256(s * p * sizeof(int));
+    l.sel_labels = off; off += align256(s * p * sizeof(int));
+    l.seg_n = off;      off += align256(s * sizeof(int));
+    l.keep = off;       off += align256(s * postc * sizeof(int));
+    l.seg_kept = off;   off += align256(s * sizeof(int));
     l.total = off;
     return l;
 }

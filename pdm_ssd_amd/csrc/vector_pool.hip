@@ -17,8 +17,6 @@ __device__ __forceinline__ bool vp_in_range(int neighbor_type, float lx, float l
     return !(fabsf(lx) > r || fabsf(ly) > r || fabsf(lz) > r);
 }
 
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
 // ---- voxel query (voxel_query_gpu.cu:11-91): the window cells in the reference's order (z outer, x inner), 64 per
 // step; cells outside the volume or empty are simply not hits -------------------------------------------------------
 __global__ __launch_bounds__(256) void voxel_query_kernel(int M, int R1, int R2, int R3, int nsample, float radius, int z_range,
@@ -50,7 +48,7 @@ __global__ __launch_bounds__(256) void voxel_query_kernel(int M, int R1, int R2,
         const unsigned long long mask = __ballot(hit);
         if (mask == 0) continue;
         if (cnt == 0) first = __shfl(nb, __ffsll((long long)mask) - 1, 64);
-        const int rank = cnt + __popcll(mask & lanes_below(lane));
+        const int rank = cnt + lanes_below(mask, lane);
         if (hit && rank < nsample) out[rank] = nb;
         cnt += __popcll(mask);
     }
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(256) void local_neighbors_kernel(int B, int M, floa
             hit = vp_in_range(neighbor_type, src[(size_t)k * 3] - nx, src[(size_t)k * 3 + 1] - ny, src[(size_t)k * 3 + 2] - nz, r, r2);
         const unsigned long long mask = __ballot(hit);
         if (FILL) {
-            const int rank = cnt + __popcll(mask & lanes_below(lane));
+            const int rank = cnt + lanes_below(mask, lane);
             if (hit && rank < cap) stack[start + rank] = k + xstart;
         }
         cnt += __popcll(mask);
@@ -112,28 +110,18 @@ __global__ __launch_bounds__(256) void local_neighbors_kernel(int B, int M, floa
 __global__ __launch_bounds__(1024) void cursor_scan_kernel(const int *cnt, int cs, int *start, int ss, int M, int *cumsum) {
     __shared__ int s_wave[16];
     __shared__ int s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) s_carry = cumsum[0];
     __syncthreads();
+    int carry = s_carry;   // the same in every thread
     for (int base = 0; base < M; base += 1024) {
         const int i = base + tid;
-        const int v = i < M ? cnt[(size_t)i * cs] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < M) start[(size_t)i * ss] = before + incl - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = before + incl;
-        __syncthreads();
+        int tot;
+        const int before = block_scan<1024>(i < M ? cnt[(size_t)i * cs] : 0, s_wave, &tot);
+        if (i < M) start[(size_t)i * ss] = carry + before;
+        carry += tot;
     }
-    if (tid == 0) cumsum[0] = s_carry;
+    if (tid == 0) cumsum[0] = carry;
 }
 
 // ---- three nearest stacked neighbours of every local grid-cell centre (vector_pool_gpu.cu:19-87): lanes over the
@@ -231,7 +219,7 @@ __global__ __launch_bounds__(256) void vector_pool_kernel(VpArgs a) {
         unsigned long long mask = __ballot(hit);
         if (mask == 0) continue;
         if (a.pooling_type == 0) {
-            const int rank = __popcll(mask & lanes_below(lane));
+            const int rank = lanes_below(mask, lane);
             const bool take = hit && taken + rank < remaining;
             mask = __ballot(take);
             if (COUNT) { taken += __popcll(mask); continue; }

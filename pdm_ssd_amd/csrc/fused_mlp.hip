@@ -860,16 +860,17 @@ __global__ __launch_bounds__(64 * W * PSW) void fp_mlp_fused_kernel(MlpDesc d, F
 // (B1 + B2*B1 + B3*B2 float4 per lane), and because a wave owns every output block of its tiles the bias+ReLU'd
 // accumulator of block mb IS the next layer's B fragment of k-block mb: no LDS, no barriers, no weight traffic
 // after the first instruction — per tile only the index/neighbour gather, the MFMA chain and the DPP max-pool.
-template <int B1, int B2, int B3, bool SAME>   // SAME: nsample >= 32, the two tiles of a step share their centre
-__global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *__restrict__ wpack,
-                                                         const float *__restrict__ bias) {
-    constexpr int NT = 2;
-    const int lane = threadIdx.x & 63, pos = lane & 15, g = lane >> 4;
-    const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+// Two kernels walk their work differently (grouped neighbours / the compacted row list); these pieces are what a
+// step of either is made of, each once.  lane = (g, pos): position pos of a tile, channels 4g .. 4g + 3 of a block.
+
+// the register-resident weights, and the lane's bias pointers of block 0 of each layer
+template <int B1, int B2, int B3>
+__device__ __forceinline__ void sa_reg_weights(const float *__restrict__ wpack, const float *__restrict__ bias, int lane, int g,
+                                               f4 (&A1)[B1], f4 (&A2)[B2][B1], f4 (&A3)[B3][B2], const float *__restrict__ &bias1,
+                                               const float *__restrict__ &bias2, const float *__restrict__ &bias3) {
     const f4 *__restrict__ w1 = reinterpret_cast<const f4 *>(wpack) + lane;
     const f4 *__restrict__ w2 = w1 + 64 * B1;            // layer 1: B1 blocks x 1 k-block x 64 lanes
     const f4 *__restrict__ w3 = w2 + 64 * B2 * B1;
-    f4 A1[B1], A2[B2][B1], A3[B3][B2];
 #pragma unroll
     for (int mb = 0; mb < B1; ++mb) A1[mb] = w1[64 * mb];
 #pragma unroll
@@ -880,17 +881,73 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
     for (int mb = 0; mb < B3; ++mb)
 #pragma unroll
         for (int kb = 0; kb < B2; ++kb) A3[mb][kb] = w3[64 * (mb * B2 + kb)];
-    const float *__restrict__ bias1 = bias + 4 * g, *__restrict__ bias2 = bias1 + 16 * B1, *__restrict__ bias3 = bias2 + 16 * B2;
+    bias1 = bias + 4 * g; bias2 = bias1 + 16 * B1; bias3 = bias2 + 16 * B2;
+}
+
+// one position's B fragment: the features of source point `src` (row of xyz / feat), then its xyz relative to the centre at c3
+__device__ __forceinline__ f4 sa_reg_gather(const SaArgs &a, size_t src, const float *c3, int g) {
+    const float *p3 = a.xyz + src * 3;
+    const float rel[3] = {p3[0] - c3[0], p3[1] - c3[1], p3[2] - c3[2]};   // pointnet2_utils.py:252
+    float v[4];
+#pragma unroll
+    for (int s_ = 0; s_ < 4; ++s_) {
+        const int c = 4 * g + s_, e = c - a.cin;
+        v[s_] = c < a.cin ? a.feat[src * a.cin + c] : e == 0 ? rel[0] : e == 1 ? rel[1] : e == 2 ? rel[2] : 0.0f;
+    }
+    return f4{v[0], v[1], v[2], v[3]};
+}
+
+// layers 1 and 2 of NT tiles; h1 and h2 never leave the registers.  (Layer 3 stays written out in both kernels, six lines
+// each: as a function of its own, in every form tried, it changes whether the compiler unswitches the plain kernel's step.)
+template <int B1, int B2, int NT>
+__device__ __forceinline__ void sa_reg_hidden(const f4 (&A1)[B1], const f4 (&A2)[B2][B1], const float *__restrict__ bias1,
+                                              const float *__restrict__ bias2, const f4 (&in)[NT], f4 (&h2)[NT][B2]) {
+    f4 h1[NT][B1];
+#pragma unroll
+    for (int mb = 0; mb < B1; ++mb) {
+        const f4 bi = *reinterpret_cast<const f4 *>(bias1 + 16 * mb);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) h1[t][mb] = floor4(mfma4(bi, A1[mb], in[t]), 0.0f);
+    }
+#pragma unroll
+    for (int mb = 0; mb < B2; ++mb) {
+        const f4 bi = *reinterpret_cast<const f4 *>(bias2 + 16 * mb);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            f4 acc = bi;
+#pragma unroll
+            for (int kb = 0; kb < B1; ++kb) acc = mfma4(acc, A2[mb][kb], h1[t][kb]);
+            h2[t][mb] = floor4(acc, 0.0f);
+        }
+    }
+}
+
+// channels c0 .. c0 + 3 of an output row whose width need not be a multiple of 4
+__device__ __forceinline__ void sa_reg_store4(float *orow, int c0, int cout, f4 v) {
+    if (c0 + 4 <= cout) {
+        *reinterpret_cast<f4 *>(orow + c0) = v;
+    } else {
+        if (c0 < cout) orow[c0] = v.x;
+        if (c0 + 1 < cout) orow[c0 + 1] = v.y;
+        if (c0 + 2 < cout) orow[c0 + 2] = v.z;
+    }
+}
+
+// Grouped neighbours (B, M, nsample): a wave walks (unit, sub-step, tile) and pools across the sub-steps of a centre.
+template <int B1, int B2, int B3, bool SAME>   // SAME: nsample >= 32, the two tiles of a step share their centre
+__global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *__restrict__ wpack,
+                                                         const float *__restrict__ bias) {
+    constexpr int NT = 2;
+    const int lane = threadIdx.x & 63, pos = lane & 15, g = lane >> 4;
+    const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    f4 A1[B1], A2[B2][B1], A3[B3][B2];
+    const float *__restrict__ bias1, *__restrict__ bias2, *__restrict__ bias3;
+    sa_reg_weights<B1, B2, B3>(wpack, bias, lane, g, A1, A2, A3, bias1, bias2, bias3);
     const int tpc = a.ns >> 4;
     const int ncentres = a.b * a.m;
     const int cpu_ = SAME ? 1 : NT / tpc;               // centres per unit
     const int nsub = SAME ? (tpc + NT - 1) / NT : 1;
     const int nunits = (ncentres + cpu_ - 1) / cpu_;
-#define PDM_CHAIN(ACC, A, B)                                                          \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).x, (B).x, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).y, (B).y, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).z, (B).z, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).w, (B).w, ACC, 0, 0, 0);
     // (unit, sub-step) sequence of this wave in 32-bit arithmetic (the host checks b*m*nsample < 2^31); the
     // neighbour indices of the next step are requested before the current step's MFMA chain (deeper prefetching
     // costs registers, i.e. waves per SIMD: measured slower).
@@ -925,19 +982,8 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
         for (int t = 0; t < NT; ++t) {
             const Where wq = where(unit, sub, t);
             live[t] = wq.live;
-            const int nb = nb_next[t];
             const int b = (unsigned)wq.ctr / (unsigned)a.m;
-            const float *c3 = a.new_xyz + (size_t)wq.ctr * 3;
-            const size_t src = (size_t)b * a.n + nb;
-            const float *p3 = a.xyz + src * 3;
-            const float rel[3] = {p3[0] - c3[0], p3[1] - c3[1], p3[2] - c3[2]};   // pointnet2_utils.py:252
-            float v[4];
-#pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) {
-                const int c = 4 * g + s_, e = c - a.cin;
-                v[s_] = c < a.cin ? a.feat[src * a.cin + c] : e == 0 ? rel[0] : e == 1 ? rel[1] : e == 2 ? rel[2] : 0.0f;
-            }
-            in[t] = f4{v[0], v[1], v[2], v[3]};
+            in[t] = sa_reg_gather(a, (size_t)b * a.n + nb_next[t], a.new_xyz + (size_t)wq.ctr * 3, g);
         }
         {
             const bool wrap = sub + 1 == nsub;
@@ -949,28 +995,8 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
             }
         }
         {
-            f4 h1[NT][B1], h2[NT][B2];
-#pragma unroll
-            for (int mb = 0; mb < B1; ++mb) {
-                const f4 bi = *reinterpret_cast<const f4 *>(bias1 + 16 * mb);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    f4 acc = bi;
-                    PDM_CHAIN(acc, A1[mb], in[t])
-                    h1[t][mb] = floor4(acc, 0.0f);
-                }
-            }
-#pragma unroll
-            for (int mb = 0; mb < B2; ++mb) {
-                const f4 bi = *reinterpret_cast<const f4 *>(bias2 + 16 * mb);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    f4 acc = bi;
-#pragma unroll
-                    for (int kb = 0; kb < B1; ++kb) { PDM_CHAIN(acc, A2[mb][kb], h1[t][kb]) }
-                    h2[t][mb] = floor4(acc, 0.0f);
-                }
-            }
+            f4 h2[NT][B2];
+            sa_reg_hidden<B1, B2, NT>(A1, A2, bias1, bias2, in, h2);
 #pragma unroll
             for (int mb = 0; mb < B3; ++mb) {
                 const f4 bi = *reinterpret_cast<const f4 *>(bias3 + 16 * mb);
@@ -979,7 +1005,7 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
                 for (int t = 0; t < NT; ++t) {
                     f4 acc = bi;
 #pragma unroll
-                    for (int kb = 0; kb < B2; ++kb) { PDM_CHAIN(acc, A3[mb][kb], h2[t][kb]) }
+                    for (int kb = 0; kb < B2; ++kb) acc = mfma4(acc, A3[mb][kb], h2[t][kb]);
                     v[t] = floor4(acc, 0.0f);
                     if (!live[t]) v[t] = f4{0.f, 0.f, 0.f, 0.f};   // wave-uniform
                 }
@@ -1007,20 +1033,9 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
             if (ctr >= ncentres || pos != 0) continue;
             float *orow = a.out + (size_t)ctr * a.out_stride + a.out_coff;
 #pragma unroll
-            for (int mb = 0; mb < B3; ++mb) {
-                const f4 v = best[t][mb];
-                const int c0 = 16 * mb + 4 * g;
-                if (c0 + 4 <= a.cout) {
-                    *reinterpret_cast<f4 *>(orow + c0) = v;
-                } else {
-                    if (c0 < a.cout) orow[c0] = v.x;
-                    if (c0 + 1 < a.cout) orow[c0 + 1] = v.y;
-                    if (c0 + 2 < a.cout) orow[c0 + 2] = v.z;
-                }
-            }
+            for (int mb = 0; mb < B3; ++mb) sa_reg_store4(orow, 16 * mb + 4 * g, a.cout, best[t][mb]);
         }
     }
-#undef PDM_CHAIN
 }
 
 // Register-resident form over the compacted row list (sa_pack.hip): one wave = one aligned tile pair per step.
@@ -1035,26 +1050,9 @@ __global__ __launch_bounds__(256) void sa_reg_packed_kernel(SaArgs a, const int2
     const int m1 = meta[1], m2 = meta[2], m3 = meta[3], m4 = meta[4], m5 = meta[5];
     const int npairs = meta[6] >> 5;
     if (wave_id >= npairs) return;
-    const f4 *__restrict__ w1 = reinterpret_cast<const f4 *>(wpack) + lane;
-    const f4 *__restrict__ w2 = w1 + 64 * B1;
-    const f4 *__restrict__ w3 = w2 + 64 * B2 * B1;
     f4 A1[B1], A2[B2][B1], A3[B3][B2];
-#pragma unroll
-    for (int mb = 0; mb < B1; ++mb) A1[mb] = w1[64 * mb];
-#pragma unroll
-    for (int mb = 0; mb < B2; ++mb)
-#pragma unroll
-        for (int kb = 0; kb < B1; ++kb) A2[mb][kb] = w2[64 * (mb * B1 + kb)];
-#pragma unroll
-    for (int mb = 0; mb < B3; ++mb)
-#pragma unroll
-        for (int kb = 0; kb < B2; ++kb) A3[mb][kb] = w3[64 * (mb * B2 + kb)];
-    const float *__restrict__ bias1 = bias + 4 * g, *__restrict__ bias2 = bias1 + 16 * B1, *__restrict__ bias3 = bias2 + 16 * B2;
-#define PDM_CHAIN(ACC, A, B)                                                          \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).x, (B).x, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).y, (B).y, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).z, (B).z, ACC, 0, 0, 0);           \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).w, (B).w, ACC, 0, 0, 0);
+    const float *__restrict__ bias1, *__restrict__ bias2, *__restrict__ bias3;
+    sa_reg_weights<B1, B2, B3>(wpack, bias, lane, g, A1, A2, A3, bias1, bias2, bias3);
     int2 e_next[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) e_next[t] = pack[(wave_id * 2 + t) * 16 + pos];
@@ -1066,45 +1064,15 @@ __global__ __launch_bounds__(256) void sa_reg_packed_kernel(SaArgs a, const int2
             const int2 e = e_next[t];
             ctr[t] = e.y;
             L[t] = pack_tile_L((unit * 2 + t) * 16, m1, m2, m3, m4, m5);
-            const float *c3 = a.new_xyz + (size_t)(e.y >= 0 ? e.y : 0) * 3;
-            const size_t src = (size_t)e.x;
-            const float *p3 = a.xyz + src * 3;
-            const float rel[3] = {p3[0] - c3[0], p3[1] - c3[1], p3[2] - c3[2]};   // pointnet2_utils.py:252
-            float v[4];
-#pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) {
-                const int c = 4 * g + s_, e_ = c - a.cin;
-                v[s_] = c < a.cin ? a.feat[src * a.cin + c] : e_ == 0 ? rel[0] : e_ == 1 ? rel[1] : e_ == 2 ? rel[2] : 0.0f;
-            }
-            in[t] = f4{v[0], v[1], v[2], v[3]};
+            in[t] = sa_reg_gather(a, (size_t)e.x, a.new_xyz + (size_t)(e.y >= 0 ? e.y : 0) * 3, g);
         }
         {
             const int nunit = unit + nwaves;
 #pragma unroll
             for (int t = 0; t < NT; ++t) e_next[t] = pack[nunit < npairs ? (nunit * 2 + t) * 16 + pos : 0];
         }
-        f4 h1[NT][B1], h2[NT][B2];
-#pragma unroll
-        for (int mb = 0; mb < B1; ++mb) {
-            const f4 bi = *reinterpret_cast<const f4 *>(bias1 + 16 * mb);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                f4 acc = bi;
-                PDM_CHAIN(acc, A1[mb], in[t])
-                h1[t][mb] = floor4(acc, 0.0f);
-            }
-        }
-#pragma unroll
-        for (int mb = 0; mb < B2; ++mb) {
-            const f4 bi = *reinterpret_cast<const f4 *>(bias2 + 16 * mb);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                f4 acc = bi;
-#pragma unroll
-                for (int kb = 0; kb < B1; ++kb) { PDM_CHAIN(acc, A2[mb][kb], h1[t][kb]) }
-                h2[t][mb] = floor4(acc, 0.0f);
-            }
-        }
+        f4 h2[NT][B2];
+        sa_reg_hidden<B1, B2, NT>(A1, A2, bias1, bias2, in, h2);
         const bool pair = L[0] >= 32;   // wave-uniform: both tiles belong to one centre
         float *orow[NT];
 #pragma unroll
@@ -1121,7 +1089,7 @@ __global__ __launch_bounds__(256) void sa_reg_packed_kernel(SaArgs a, const int2
             for (int t = 0; t < NT; ++t) {
                 f4 acc = bi;
 #pragma unroll
-                for (int kb = 0; kb < B2; ++kb) { PDM_CHAIN(acc, A3[mb][kb], h2[t][kb]) }
+                for (int kb = 0; kb < B2; ++kb) acc = mfma4(acc, A3[mb][kb], h2[t][kb]);
                 v[t] = floor4(acc, 0.0f);
             }
             if (pair) {
@@ -1132,21 +1100,11 @@ __global__ __launch_bounds__(256) void sa_reg_packed_kernel(SaArgs a, const int2
 #pragma unroll
                 for (int t = 0; t < NT; ++t) v[t] = seg_max_nonneg4(v[t], L[t]);
             }
-            const int c0 = 16 * mb + 4 * g;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if (!orow[t]) continue;
-                if (c0 + 4 <= a.cout) {
-                    *reinterpret_cast<f4 *>(orow[t] + c0) = v[t];
-                } else {
-                    if (c0 < a.cout) orow[t][c0] = v[t].x;
-                    if (c0 + 1 < a.cout) orow[t][c0 + 1] = v[t].y;
-                    if (c0 + 2 < a.cout) orow[t][c0 + 2] = v[t].z;
-                }
-            }
+            for (int t = 0; t < NT; ++t)
+                if (orow[t]) sa_reg_store4(orow[t], 16 * mb + 4 * g, a.cout, v[t]);
         }
     }
-#undef PDM_CHAIN
 }
 
 int rows_gemm_launch(void *stream, int rows, int cin, const float *in_pm, int k0, int c1, const float *wpack,

@@ -413,7 +413,9 @@ struct TgNtTile {
                 for (int g = 0; g < 4; ++g) {
                     const int col = wn * JT * 32 + j * 32 + 8 * g + 4 * (lane >> 5);
                     float b4[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (XF != 2 && a.bias) {   // only the heads' last layers carry one: fetched here (L2) rather than held in 16 JT registers
+                    // only the heads' last layers carry one: fetched here (L2) rather than held in 16 JT registers.  It is added to EVERY
+                    // row of the tile: a row beyond R holds bf16(bias) from here on, not zero (nothing below may read it as data)
+                    if (XF != 2 && a.bias) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             if (col0 + col + e < a.N) b4[e] = tg_f32(tg_bf16(a.bias[col0 + col + e]));
@@ -445,7 +447,9 @@ struct TgNtTile {
             if constexpr (BS) {   // rows beyond R / columns beyond N hold zeros: g = 0
                 tg_bs_accum(v, bx[i], bcf, s1, s2);
             }
-            if (!BS && XF != 2 && a.stats) {   // rows beyond R were staged as zeros: they add nothing
+            // live rows only: a row beyond R was staged as zeros but carries the bias (above) — summed, every dead row of a ragged last
+            // tile added bias / bias^2 to the BatchNorm statistics of a biased layer
+            if (!BS && XF != 2 && a.stats && r < a.R) {
                 const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

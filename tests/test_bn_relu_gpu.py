@@ -468,3 +468,28 @@ def test_bn_relu_on_a_tensor_that_no_contraction_produced_rides_in_the_next_cont
     for k in ba:
         assert torch.equal(ba[k], bb[k]) and torch.equal(ba[k], bc[k]), k
     assert float((ga.float() - gc.float()).abs().max()) <= 2.0 ** -6 * float(ga.float().abs().max())
+
+
+@pytest.mark.gpu
+def test_biased_conv_in_front_of_batchnorm_counts_only_live_rows(dev):
+    """Conv2d(16, 32, 1, bias=True) -> BatchNorm2d -> ReLU through TrainSequential under bf16 autocast: the BatchNorm's statistics come
+    from the contraction's epilogue (train_gemm.gemm_nt(bias=, stats=True)), whose tile rows beyond R hold the bias.  3 x 50 x 16 =
+    2400 positions = 9 row tiles of 256 and one of 96: counted, its 160 dead rows would move every channel's mean by bias / 15 (bias
+    up to 1.5, outputs' standard deviation ~0.6: an error of ~0.17 in the normalised output).  Output and running statistics against
+    the same layers in torch fp32 on the CPU, weights and bias representable in bf16 so that both sides hold the same numbers."""
+    torch.manual_seed(41)
+    conv, bn = nn.Conv2d(16, 32, 1, bias=True), nn.BatchNorm2d(32)
+    with torch.no_grad():
+        conv.weight.copy_(conv.weight.bfloat16().float())
+        conv.bias.copy_(torch.linspace(-1.5, 1.5, 32).bfloat16().float())
+        bn.weight.uniform_(0.5, 1.5); bn.bias.normal_(0, 0.3)
+    x = torch.randn(3, 16, 50, 16).bfloat16()
+    ref = nn.Sequential(copy.deepcopy(conv), copy.deepcopy(bn), nn.ReLU()).train()
+    want = ref(x.float())
+    net = fused_bn.TrainSequential(conv, bn, nn.ReLU()).to(dev).train()
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        y = net(x.to(dev).contiguous(memory_format=torch.channels_last))
+    assert y.dtype == torch.bfloat16
+    torch.testing.assert_close(net[1].running_mean.cpu(), ref[1].running_mean, rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(net[1].running_var.cpu(), ref[1].running_var, rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(y.detach().float().cpu(), want.detach(), rtol=2e-2, atol=2e-2)

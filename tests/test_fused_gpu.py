@@ -23,41 +23,79 @@ def randomize_bn(module, seed):
             m.bias.data.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
 
 
-@pytest.mark.parametrize("cin,mlps,nsamples", [
-    (1, [[1, 16, 16, 32], [1, 32, 32, 64]], [16, 32]),            # SA1 shapes (K0 = 4)
-    (96, [[96, 64, 64, 128], [96, 64, 96, 128]], [16, 32]),       # SA2
-    (24, [[24, 128, 196, 256]], [48]),                            # 196 -> padded 208, 3 tiles per centre
-    (0, [[0, 20, 36]], [16]),                                     # no features, 2 layers, odd widths
-    (8, [[8, 64]], [32]),                                         # single layer
-    (12, [[12, 32, 48, 64, 32]], [16]),                           # four layers
-])
-def test_sa_fused_matches_cpu_graph(dev, cin, mlps, nsamples):
+def _sa_row(i, cin, mlps, nsamples):
+    """a row of the original table (batch 2, 1500 points, 200 centres) under the id it has always had"""
+    return pytest.param(cin, mlps, nsamples, 2, 1500, 200, False, id="%d-mlps%d-nsamples%d" % (cin, i, i))
+
+
+# The register-resident kernels (sa_reg_mlp_kernel / sa_reg_packed_kernel, fused_mlp.hip) are reached by construction: three layers,
+# 3 + cin <= 16 and padded widths (16, 16, 32) or (32, 32, 64).  A wave of the dense form takes a UNIT per step: two centres when
+# nsample is 16, one centre (nsample / 16 tiles, two per sub-step) otherwise; the grid is capped at 2048 blocks x 4 waves.
+SA_REG_EDGES = [
+    pytest.param(13, [[13, 16, 16, 32]], [16], 2, 1500, 200, True, id="reg-k0-full"),            # 3 + cin == 16: no zero padding in K0
+    pytest.param(0, [[0, 32, 32, 64]], [32], 2, 1500, 200, True, id="reg-xyz-only-wide"),        # <2, 2, 4>, SAME
+    # odd widths below the padded ones.  (cout = 30 would reach the guarded tail of sa_reg_store4, but the module only takes its fused
+    # path when cout % 4 == 0 — pointnet2_modules.py, _forward — so no width that is not a multiple of 4 gets there from Python.)
+    pytest.param(5, [[5, 12, 10, 28]], [16], 2, 1500, 200, True, id="reg-odd-widths"),
+    pytest.param(1, [[1, 16, 16, 32]], [48], 2, 1500, 200, True, id="reg-ns48"),                 # 3 tiles: the second sub-step's second tile is dead
+    pytest.param(1, [[1, 16, 16, 32]], [64], 2, 1500, 200, True, id="reg-ns64"),                 # nsub = 2, both tiles live
+    pytest.param(1, [[1, 16, 16, 32]], [16], 1, 1500, 201, True, id="reg-odd-centres"),          # 201 centres, 2 per unit: the last unit is half dead
+    pytest.param(1, [[1, 16, 16, 32]], [32], 2, 6000, 4200, True, id="reg-more-units-than-waves"),   # 8400 units, 8192 waves: `unit += nwaves`
+]
+
+
+@pytest.mark.parametrize("cin,mlps,nsamples,batch,n,npoint,reg_edges", [
+    _sa_row(0, 1, [[1, 16, 16, 32], [1, 32, 32, 64]], [16, 32]),            # SA1 shapes (K0 = 4)
+    _sa_row(1, 96, [[96, 64, 64, 128], [96, 64, 96, 128]], [16, 32]),       # SA2
+    _sa_row(2, 24, [[24, 128, 196, 256]], [48]),                            # 196 -> padded 208, 3 tiles per centre
+    _sa_row(3, 0, [[0, 20, 36]], [16]),                                     # no features, 2 layers, odd widths
+    _sa_row(4, 8, [[8, 64]], [32]),                                         # single layer
+    _sa_row(5, 12, [[12, 32, 48, 64, 32]], [16]),                           # four layers
+] + SA_REG_EDGES)
+def test_sa_fused_matches_cpu_graph(dev, cin, mlps, nsamples, batch, n, npoint, reg_edges):
     from oracle import cpu_backbone
     torch.manual_seed(cin + 1)
     radii = [0.9, 1.8][:len(mlps)]
-    sa = pm.PointnetSAModuleMSG(npoint=200, radii=radii, nsamples=nsamples, mlps=copy.deepcopy(mlps)).eval()
+    sa = pm.PointnetSAModuleMSG(npoint=npoint, radii=radii, nsamples=nsamples, mlps=copy.deepcopy(mlps)).eval()
     randomize_bn(sa, 5)
-    cl = synthetic.lidar_like_clouds(2, 1500, 11)
+    cl = synthetic.lidar_like_clouds(batch, n, 11)
     xyz = np.ascontiguousarray(cl[:, :, :3])
     rng = np.random.default_rng(0)
-    feat = rng.standard_normal((2, cin, 1500)).astype(np.float32) if cin else None
+    feat = rng.standard_normal((batch, cin, n)).astype(np.float32) if cin else None
     ref_xyz, ref_feat = cpu_backbone.sa_forward(sa, xyz, feat)
     sa_g = copy.deepcopy(sa).to(dev)
+    xyz_g, feat_g = torch.from_numpy(xyz).to(dev), None if feat is None else torch.from_numpy(feat).to(dev)
     with torch.no_grad():
-        nx, nf = sa_g(torch.from_numpy(xyz).to(dev), None if feat is None else torch.from_numpy(feat).to(dev))
+        nx, nf = sa_g(xyz_g, feat_g)
     assert '_pdm_fused_cache' in sa_g.__dict__ and all(v[1] is not None for v in sa_g._pdm_fused_cache.values())
     assert nf.stride(1) == 1, "fused output must be a view of point-major storage"
     np.testing.assert_array_equal(nx.cpu().numpy(), ref_xyz)
     np.testing.assert_allclose(nf.cpu().numpy(), ref_feat, rtol=1e-4, atol=1e-4)
     assert ('pre' in sa_g._pdm_fused_cache) == (cin >= pm.PRE_MIN_CIN)
+    if reg_edges:
+        from pdm_ssd_amd import _native
+        if all(ns in (16, 32) for ns in nsamples):
+            # `nf` came from the compacted neighbour list (sa_reg_packed_kernel); the dense list (sa_reg_mlp_kernel) gives the same bits
+            sa_g.use_pack = False
+            with torch.no_grad():
+                _, nf_dense = sa_g(xyz_g, feat_g)
+            sa_g.use_pack = True
+            assert torch.equal(nf, nf_dense)
+        old = _native.lib().pdm_tune_fused_reg(0)      # the LDS form of the same scale against the same reference
+        try:
+            with torch.no_grad():
+                _, nf_lds = sa_g(xyz_g, feat_g)
+            np.testing.assert_allclose(nf_lds.cpu().numpy(), ref_feat, rtol=1e-4, atol=1e-4)
+        finally:
+            _native.lib().pdm_tune_fused_reg(old)
     # first-layer hoisting switched off (features gathered and contracted per pair), then the whole fused path off
     sa_g.use_pre = False
     with torch.no_grad():
-        _, nf1 = sa_g(torch.from_numpy(xyz).to(dev), None if feat is None else torch.from_numpy(feat).to(dev))
+        _, nf1 = sa_g(xyz_g, feat_g)
     np.testing.assert_allclose(nf1.cpu().numpy(), ref_feat, rtol=1e-4, atol=1e-4)
     sa_g.use_fused = False
     with torch.no_grad():
-        _, nf2 = sa_g(torch.from_numpy(xyz).to(dev), None if feat is None else torch.from_numpy(feat).to(dev))
+        _, nf2 = sa_g(xyz_g, feat_g)
     np.testing.assert_allclose(nf.cpu().numpy(), nf2.cpu().numpy(), rtol=1e-4, atol=1e-4)
 
 

@@ -87,7 +87,7 @@ class _DepthwiseConv3x3(nn.Conv2d):
     def forward(self, x):
         if x.is_cuda and x.shape[1] % 4 == 0:
             from .. import fused_bn
-            bf = self.training and fused_bn.ENABLED and fused_bn._bf16_autocast() and x.shape[1] % 8 == 0 and DEPTHWISE_BF16_OUT
+            bf = self.training and fused_bn.ENABLED and fused_bn.bf16_autocast() and x.shape[1] % 8 == 0 and DEPTHWISE_BF16_OUT
             return _Depthwise3x3CL.apply(x, self.weight, bool(bf))
         return super().forward(x)
 

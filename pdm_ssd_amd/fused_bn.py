@@ -8,6 +8,15 @@ a drop-in `nn.Sequential` (same child indices, hence the same state_dict keys) t
 runs every (BatchNorm, ReLU) pair after a convolution / linear layer as one forward kernel pair and one backward
 kernel pair, statistics in fp32, activations fp32 or bf16 (autocast).  Anything it does not recognise — eval mode,
 CPU tensors, exotic shapes, `momentum=None`, `track_running_stats=False` — goes through the torch modules unchanged.
+
+The `link` dictionaries tie the autograd node that PRODUCES a tensor of bf16 rows to the one node that CONSUMES it.
+`TrainSequential._run_stack` creates a fresh one for every rows contraction and hands it to that node as its output link
+and to whatever reads the rows next (the next rows node's input link, `_BnRelu`'s link).  Two keys travel in it, both
+beside the autograd graph.  'pool': written by the producer's forward (`_rows_forward` with pool_ns: the group extremes
+its epilogue took), read by `forward_max_pooled`.  'lazy': written by the consumer's backward (`_bn_relu_backward_rows`,
+`_BnRelu.backward`) when it hands its gradient back UNFORMED — (x rows, coef, grads, address of the gradient rows) say
+how to form it — and popped by the producer's backward in `_take_lazy_bn_backward`, whose check of that address (and of
+shape and dtype) against the gradient autograd delivered is the guard: a gradient that took another way raises.
 """
 import os
 
@@ -16,8 +25,58 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _native
+from . import train_gemm as tg
 
 ENABLED = os.environ.get("PDM_FUSED_BN", "1") != "0"
+
+ROWS_GEMM = os.environ.get("PDM_ROWS_GEMM", "1") != "0"   # 0: the round-2 path (vendor GEMMs) for A/B measurements
+
+# 1 (default): BatchNorm + ReLU of an inner layer ride in the next contraction's load path (_BnReluRowsGemm; bit-identical results,
+# the normalised tensor is never stored).  Measured at bs = 32, A/B twice: 26.17 / 26.24 ms per step with, 26.79 / 26.87
+# without.  (An earlier A/B read 29.4-29.9 against 29.3-29.4 and kept the separate operator: the step was bound by the HOST
+# then — a pageable host-to-device copy and two boolean-mask indexings in the target assignment stalled the issue thread
+# every step — so device-side savings did not show.)
+BN_IN_GEMM = os.environ.get("PDM_BN_IN_GEMM", "1") == "1"
+
+# 1 (default): a BatchNorm + ReLU whose bf16 input does NOT come from a rows contraction (the heat-map head's first one, behind the
+# depthwise convolution) still rides in the next contraction's load path: its statistics pass runs alone (pdm_bn_forward_coef), the
+# apply pass and the normalised tensor (288 MB at bs = 32) disappear, and its gradient statistics come out of that contraction's data
+# gradient like everywhere else.
+BN_FROM_X = os.environ.get("PDM_BN_FROM_X", "1") == "1"
+
+# 1 (default): between two contractions of a stack the BatchNorm + ReLU backward's elementwise half rides in the data gradient of
+# the layer before (pdm_tg_gemm_nt_dy): no pass over (dZ, Y) of its own and one read of dY less.  Bit-identical gradients.
+LAZY_BN_BACKWARD = os.environ.get("PDM_LAZY_BN_BACKWARD", "1") == "1"
+
+# 1 (default): the statistics of a BatchNorm + ReLU backward between two contractions of a stack (sum g, sum g xhat over the gradient
+# the next layer's data gradient produces) are taken in THAT contraction's epilogue (pdm_tg_gemm_nt_bs / pdm_tg_gemm_nt_dy_bs): the
+# reduce pass over (gradient, x) — a second read of both — disappears; only the finalize launch is left.
+BWD_STATS_IN_GEMM = os.environ.get("PDM_BWD_STATS_IN_GEMM", "1") == "1"
+
+# 1: the last contraction of an SA scale leaves the pooled operator's statistics (column sums, group extremes + indices) in its
+# epilogue (pdm_tg_gemm_nt_pool): the operator's own pass over the (B M ns, C) tensor disappears.  Built, exact, measured and NOT
+# faster: 18.77-18.81 ms per step against 18.53-18.62 (A/B twice on one box) — the epilogue's compare / select work per element does
+# not overlap the tile's memory traffic at two workgroups per CU, and costs the eight widest-row contractions more than the 0.4 ms
+# pass it removes (with one thread per (group, chunk) instead of a quad: 18.88).  Off by default.
+POOL_IN_GEMM = os.environ.get("PDM_POOL_IN_GEMM", "0") == "1"
+
+
+def _round8(v):
+    return (v + 7) // 8 * 8
+
+
+def bf16_autocast():
+    return torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
+def _rows_to_layout(rows, like, channels, shape=None, dim=None):
+    """(R, ld) row storage -> the logical tensor of `like`'s layout with `channels` channels (a view)."""
+    shape = tuple(like.shape) if shape is None else shape
+    dim = like.dim() if dim is None else dim
+    if dim == 2:
+        return rows[:, :channels]
+    lead = (shape[0],) + tuple(shape[2:])
+    return rows.view(*lead, rows.shape[1])[..., :channels].movedim(-1, 1)
 
 
 def _layout(x):
@@ -51,7 +110,7 @@ class _BnRelu(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, relu, layout, n, L, stats=None, out_bf16=False, link=None):
-        ctx.link = link      # shared with the rows GEMM node that produced x (TrainSequential._run): see backward
+        ctx.link = link      # shared with the rows GEMM node that produced x (the module docstring's `link`): see backward
         C = x.shape[1]
         dtype = 1 if x.dtype == torch.bfloat16 else 0
         if out_bf16 and dtype == 0 and layout == 0:
@@ -92,7 +151,6 @@ class _BnRelu(Function):
         if ctx.link is not None and LAZY_BN_BACKWARD and dtype == 1 and layout == 0 and relu:
             # x came straight from a rows GEMM node: only the gradient statistics are taken here; that node's data gradient
             # forms dx while it reads dy and x (see _take_lazy_bn_backward — the same hand-over _BnReluRowsGemm uses)
-            from . import train_gemm as tg
             xr, dyr = tg.row_view(x), tg.row_view(dy)
             if xr is not None and dyr is not None and xr.shape == dyr.shape and xr.stride(0) == C and dyr.stride(0) == C:
                 _native.call("pdm_bn_relu_backward_stats", stream, 1, 0, n, C, 1, x.data_ptr(), dy.data_ptr(), coef.data_ptr(),
@@ -155,14 +213,6 @@ class _BnReluPool(Function):
         return dx, grads[0], grads[1], None, None, None, None, None, None, None
 
 
-# 1: the last contraction of an SA scale leaves the pooled operator's statistics (column sums, group extremes + indices) in its
-# epilogue (pdm_tg_gemm_nt_pool): the operator's own pass over the (B M ns, C) tensor disappears.  Built, exact, measured and NOT
-# faster: 18.77-18.81 ms per step against 18.53-18.62 (A/B twice on one box) — the epilogue's compare / select work per element does
-# not overlap the tile's memory traffic at two workgroups per CU, and costs the eight widest-row contractions more than the 0.4 ms
-# pass it removes (with one thread per (group, chunk) instead of a quad: 18.88).  Off by default.
-POOL_IN_GEMM = os.environ.get("PDM_POOL_IN_GEMM", "0") == "1"
-
-
 def pool_applies(x, bn):
     """the pooled operator takes channels-last (B, C, M, ns) tensors, ns <= 255"""
     v = 8 if x.dtype == torch.bfloat16 else 4
@@ -170,10 +220,14 @@ def pool_applies(x, bn):
             and not x.is_contiguous() and x.shape[1] % v == 0 and x.shape[1] // v <= 256)
 
 
-def applies(x, bn):
+def _bn_eligible(x, bn):
+    """a training-mode BatchNorm with affine parameters and running statistics in fp32, over a GPU tensor the kernels read"""
     return (ENABLED and bn.training and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and bn.affine
-            and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32
-            and x.dim() >= 2 and x.shape[1] == bn.num_features and _layout(x) is not None)
+            and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32 and x.dim() >= 2)
+
+
+def applies(x, bn):
+    return _bn_eligible(x, bn) and x.shape[1] == bn.num_features and _layout(x) is not None
 
 
 def _padded_applies(x, bn):
@@ -181,9 +235,20 @@ def _padded_applies(x, bn):
     rows that way, _RowsGemm): BatchNorm runs over the padded width with zero gamma / beta on the padding, which then
     stays zero forward and backward."""
     C = bn.num_features
-    return (ENABLED and bn.training and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and bn.affine
-            and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32
-            and x.dim() >= 2 and C % 8 != 0 and x.shape[1] == _round8(C) and _layout(x) is not None)
+    return _bn_eligible(x, bn) and C % 8 != 0 and x.shape[1] == _round8(C) and _layout(x) is not None
+
+
+def _padded_bn_params(bn, Cp):
+    """(gamma, beta, running mean, running variance) of `bn` at the zero-padded width Cp: zero gamma / beta on the padding (it
+    stays zero), TEMPORARY running statistics that _keep_running_stats copies back after the kernels have updated them."""
+    z = bn.weight.new_zeros(Cp - bn.num_features)
+    return torch.cat([bn.weight, z]), torch.cat([bn.bias, z]), torch.cat([bn.running_mean, z]), torch.cat([bn.running_var, z + 1.0])
+
+
+def _keep_running_stats(bn, rm, rv):
+    C = bn.num_features
+    with torch.no_grad():
+        bn.running_mean.copy_(rm[:C]); bn.running_var.copy_(rv[:C])
 
 
 # BatchNorm's num_batches_tracked += 1 is one tiny launch per layer and step; inside TrainSequential._run the layers of a stack
@@ -218,14 +283,12 @@ def batch_norm_relu(x, bn, relu=True, stats=None, out_bf16=False, link=None):
     """bn(x) followed by ReLU (relu=True), through the fused kernels when `applies`, else through torch.
     stats: the column sums the producing GEMM took of x ([tiles][C][2], rows_linear(..., want_stats=True)) or None."""
     if _padded_applies(x, bn):
-        C, Cp = bn.num_features, x.shape[1]
-        z = bn.weight.new_zeros(Cp - C)
-        rm, rv = torch.cat([bn.running_mean, z]), torch.cat([bn.running_var, z + 1.0])
+        gamma, beta, rm, rv = _padded_bn_params(bn, x.shape[1])
         layout, n, L = _layout(x)
-        y = _BnRelu.apply(x, torch.cat([bn.weight, z]), torch.cat([bn.bias, z]), rm, rv, bn.eps, bn.momentum, relu, layout, n, L,
+        y = _BnRelu.apply(x, gamma, beta, rm, rv, bn.eps, bn.momentum, relu, layout, n, L,
                           stats if layout == 0 else None, False, link if layout == 0 else None)
+        _keep_running_stats(bn, rm, rv)
         with torch.no_grad():
-            bn.running_mean.copy_(rm[:C]); bn.running_var.copy_(rv[:C])
             _bump(bn)
         return y
     if not applies(x, bn):
@@ -238,50 +301,121 @@ def batch_norm_relu(x, bn, relu=True, stats=None, out_bf16=False, link=None):
                          stats if layout == 0 else None, bool(out_bf16), link if layout == 0 else None)
 
 
-def _round8(v):
-    return (v + 7) // 8 * 8
-
-
-# 1 (default): between two contractions of a stack the BatchNorm + ReLU backward's elementwise half rides in the data gradient of
-# the layer before (pdm_tg_gemm_nt_dy): no pass over (dZ, Y) of its own and one read of dY less.  Bit-identical gradients.
-LAZY_BN_BACKWARD = os.environ.get("PDM_LAZY_BN_BACKWARD", "1") == "1"
-
-
-# 1 (default): the statistics of a BatchNorm + ReLU backward between two contractions of a stack (sum g, sum g xhat over the gradient
-# the next layer's data gradient produces) are taken in THAT contraction's epilogue (pdm_tg_gemm_nt_bs / pdm_tg_gemm_nt_dy_bs): the
-# reduce pass over (gradient, x) — a second read of both — disappears; only the finalize launch is left.
-BWD_STATS_IN_GEMM = os.environ.get("PDM_BWD_STATS_IN_GEMM", "1") == "1"
+def _bn_relu_backward_rows(in_link, xr, coef, grads, da):
+    """The elementwise half of a BatchNorm + ReLU backward over bf16 rows: da (R, K) = the gradient of relu(bn(xr)) -> the
+    gradient of xr, dx = scale (da [bn(x) > 0] - p - (x - mean) q).  With an input link under LAZY_BN_BACKWARD it is LEFT to the
+    producer of xr, whose data gradient forms dx while it reads da and xr (pdm_tg_gemm_nt_dy) and writes it out for its weight
+    gradient: what travels back through autograd is `da` itself, and in_link['lazy'] says how to read it (the module
+    docstring's `link`).  Otherwise the operator's apply half runs here."""
+    if LAZY_BN_BACKWARD and in_link is not None:
+        in_link['lazy'] = (xr, coef, grads, da.data_ptr())
+        return da
+    R, K = xr.shape
+    dx = torch.empty_like(xr)
+    _native.call("pdm_bn_relu_backward_apply", torch.cuda.current_stream(da.device).cuda_stream, 1, 0, R, K, 1, xr.data_ptr(),
+                 da.data_ptr(), dx.data_ptr(), coef.data_ptr(), grads.data_ptr(), 1)
+    return dx
 
 
 def _take_lazy_bn_backward(link, dyr, wt, want_dx, bs=None):
-    """The gradient rows `dyr` of a contraction's output may be UNFORMED: when the BatchNorm + ReLU behind it belongs to a
-    _BnReluRowsGemm, that node hands back the gradient of relu(bn(y)) as it is and leaves (y, coef, grads) in the link it shares
-    with the producer of y — this node.  Returns (dy rows formed, dx rows or None): with want_dx the data gradient forms dy on
-    the way (pdm_tg_gemm_nt_dy), otherwise the BatchNorm operator's apply half does.
+    """The gradient rows `dyr` of a contraction's output may be UNFORMED: when the node behind it left them so
+    (_bn_relu_backward_rows), link['lazy'] holds (y, coef, grads, address) of that BatchNorm + ReLU.  Returns (dy rows formed, dx
+    rows or None): with want_dx the data gradient forms dy on the way (pdm_tg_gemm_nt_dy), otherwise the operator's apply half does.
     bs = (x rows, coef) of the BatchNorm + ReLU in FRONT of this layer (its output gradient is this node's dx): when the data
     gradient is formed here, its epilogue takes that BatchNorm's gradient statistics; returned as a third value (or None)."""
     lazy = link.pop('lazy', None) if link is not None else None
     if lazy is None:
         return dyr, None, None
-    from . import train_gemm as tg
     y_rows, coef, grads, ptr = lazy
     if dyr.data_ptr() != ptr or dyr.shape != y_rows.shape or dyr.dtype != torch.bfloat16:
         raise RuntimeError("fused_bn: an unformed BatchNorm gradient did not reach the contraction it was left for "
                            f"(rows {tuple(dyr.shape)} at {dyr.data_ptr():#x}, expected {tuple(y_rows.shape)} at {ptr:#x})")
-    R, K = y_rows.shape
     # per shape (tools/diag/lazy_bn_rate.py): the fused form wins 1.1-1.5x where the data gradient has at most two column tiles
     # (N <= 256) and rows of >= 64 bytes; 16-channel rows (0.69x) and three or more column tiles (every tile re-reads and
     # re-forms the operand: 0.72-0.81x) take the apply half of the operator and the plain contraction
-    if want_dx and 32 <= K <= 512 and wt.shape[0] <= 256:
+    if want_dx and 32 <= y_rows.shape[1] <= 512 and wt.shape[0] <= 256:
         if bs is not None:
             dxr, dy_formed, partial = tg.gemm_nt_dy(dyr, y_rows, coef, grads, wt, bs=bs)
             return dy_formed, dxr, partial
         dxr, dy_formed = tg.gemm_nt_dy(dyr, y_rows, coef, grads, wt)
         return dy_formed, dxr, None
-    dy_formed = torch.empty_like(y_rows)
-    _native.call("pdm_bn_relu_backward_apply", torch.cuda.current_stream(dyr.device).cuda_stream, 1, 0, R, K, 1, y_rows.data_ptr(),
-                 dyr.data_ptr(), dy_formed.data_ptr(), coef.data_ptr(), grads.data_ptr(), 1)
-    return dy_formed, None, None
+    return _bn_relu_backward_rows(None, y_rows, coef, grads, dyr), None, None
+
+
+def _rows_forward(ctx, x, xr, weight, bias, x_bn_coef, want_stats, keep_pad, pool_ns, out_link):
+    """The forward shared by the three rows nodes: y = xr W^T [+ b] for xr = the (R, K) bf16 rows of x, read through BatchNorm + ReLU
+    with x_bn_coef when given.  K may exceed the layer's in-features up to the next multiple of 8 (zero padding by contract, it
+    meets zero weight columns); y is (R, round8(N)) storage.  Leaves ctx.link and ctx.geom for the backward and returns (y in x's
+    layout, stats or None, the packed transposed weight for the data gradient)."""
+    ctx.link = out_link
+    ctx.set_materialize_grads(False)     # no zero tensor (a fill launch per node and step) for the statistics output's gradient
+    R, K = xr.shape
+    N = weight.shape[0]
+    w2 = weight.reshape(N, -1)
+    Kw, Np = w2.shape[1], _round8(N)
+    assert xr.dtype == torch.bfloat16 and Kw <= K < Kw + 8 and K % 8 == 0
+    wb, wt = tg.pack_weight_pair(w2, Np, K)              # forward weights and their transpose (data gradient): one launch
+    if bias is not None and Np != N:
+        bias = torch.cat([bias.detach().float(), bias.new_zeros(Np - N, dtype=torch.float32)])
+    if pool_ns and want_stats and out_link is not None:
+        y, stats, out_link['pool'] = tg.gemm_nt(xr, wb, bias=bias, stats=True, x_bn_coef=x_bn_coef, pool_ns=pool_ns)
+    elif want_stats:
+        y, stats = tg.gemm_nt(xr, wb, bias=bias, stats=True, x_bn_coef=x_bn_coef)
+    else:
+        y, stats = tg.gemm_nt(xr, wb, bias=bias, x_bn_coef=x_bn_coef), None
+    ctx.geom = (tuple(x.shape), x.dim(), N, Np, K, Kw, bias is not None, x.dtype)
+    # keep_pad: the caller (a BatchNorm over the padded width follows) takes all round8(N) channels, the extra ones zero
+    out = _rows_to_layout(y, x, Np if keep_pad else N)
+    if stats is not None:
+        ctx.mark_non_differentiable(stats)
+    return out, stats, wt
+
+
+def _grad_rows(dy, R, Np, xdim):
+    """the output gradient as (R, Np) bf16 rows: a view when it arrives so, else ONE copy into that form"""
+    dyr = tg.row_view(dy)
+    if dyr is None or dyr.dtype != torch.bfloat16 or dyr.shape[1] != Np or dyr.stride(0) % 8:
+        nc = dy.shape[1]                                  # N, or Np when the forward kept the padding
+        src = dy.movedim(1, -1).reshape(R, nc) if xdim > 2 else dy
+        dyr = (torch.zeros if Np != nc else torch.empty)((R, Np), dtype=torch.bfloat16, device=dy.device)
+        dyr[:, :nc].copy_(src)
+    return dyr
+
+
+def _param_grads(dyr, xr, weight, geom, x_bn_coef=None):
+    """(dW, db or None) in the parameters' shapes, fp32: dW = dyr^T xr — with x_bn_coef the layer's input relu(bn(xr)) is
+    recomputed while xr is read — and db = the column sums of the gradient rows."""
+    _, _, N, Np, _, Kw, has_bias, _ = geom
+    dw = tg.wgrad(dyr, xr, x_bn_coef=x_bn_coef)[:N, :Kw].reshape(weight.shape)
+    db = None
+    if has_bias:   # (torch's strided reduction over 8 columns took 0.28 ms at 524288 rows)
+        db = tg.colsum(dyr)[:N] if Np <= 512 else dyr[:, :N].sum(0, dtype=torch.float32)
+    return dw, db
+
+
+def _act_rows_backward(ctx, dy, xr, coef, grads, weight, wt):
+    """The backward shared by _BnReluRowsGemm (grads None: the BatchNorm's gradient statistics are taken here) and _ReluRowsGemm
+    (grads = the zeros of _relu_coef: nothing to take): data gradient of the layer = the gradient `da` of relu(bn(x)), parameter
+    gradients, then the elementwise half of the BatchNorm + ReLU backward.  Returns (dx in x's layout, grads, dW, db)."""
+    xshape, xdim, _, Np, K, _, _, _ = ctx.geom
+    R = xr.shape[0]
+    dyr = _grad_rows(dy, R, Np, xdim)
+    # the gradient statistics of the BatchNorm in front (over da and x) come out of the contraction that forms da
+    bs = (xr, coef) if grads is None and BWD_STATS_IN_GEMM and xr.stride(0) % 8 == 0 else None
+    dyr, da, partial = _take_lazy_bn_backward(ctx.link, dyr, wt, True, bs)   # this layer's own output gradient may arrive unformed (see there)
+    if da is None:                                       # (R, K) bf16
+        da, partial = tg.gemm_nt_bs(dyr, wt, xr, coef) if bs is not None else (tg.gemm_nt(dyr, wt), None)
+    dw, db = _param_grads(dyr, xr, weight, ctx.geom, coef)
+    if grads is None:
+        if partial is not None:
+            grads = tg.bn_bwd_finalize(R, coef, partial)
+        else:
+            grads = torch.empty((4, K), dtype=torch.float32, device=dy.device)
+            scratch = torch.empty((_native.lib().pdm_bn_parts(0, R, K, 1), K, 2), dtype=torch.float32, device=dy.device)
+            _native.call("pdm_bn_relu_backward_stats", torch.cuda.current_stream(dy.device).cuda_stream, 1, 0, R, K, 1, xr.data_ptr(),
+                         da.data_ptr(), coef.data_ptr(), grads.data_ptr(), scratch.data_ptr(), 1)
+    dx = _bn_relu_backward_rows(ctx.in_link, xr, coef, grads, da)
+    return _rows_to_layout(dx, None, K, xshape, xdim), grads, dw, db
 
 
 class _RowsGemm(Function):
@@ -298,49 +432,22 @@ class _RowsGemm(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, weight, bias, want_stats, keep_pad=False, link=None, pool_ns=0):
-        from . import train_gemm as tg
-        ctx.link = link
-        ctx.set_materialize_grads(False)     # no zero tensor (a fill launch per node and step) for the statistics output's gradient
         xr = tg.row_view(x)
         assert xr is not None
         if xr.dtype != torch.bfloat16:
             xr = xr.to(torch.bfloat16)                       # autocast's rounding of an fp32 activation
-        R, K = xr.shape
-        N = weight.shape[0]
-        w2 = weight.reshape(N, -1)
-        Kw, Np = w2.shape[1], _round8(N)
-        assert Kw <= K < Kw + 8 and K % 8 == 0
-        wb, wt = tg.pack_weight_pair(w2, Np, K)              # forward weights and their transpose (data gradient): one launch
-        if bias is not None and Np != N:
-            bias = torch.cat([bias.detach().float(), bias.new_zeros(Np - N, dtype=torch.float32)])
-        if pool_ns and want_stats and link is not None:
-            y, stats, link['pool'] = tg.gemm_nt(xr, wb, bias=bias, stats=True, pool_ns=pool_ns)     # (keeps travel beside the autograd graph)
-        else:
-            y, stats = tg.gemm_nt(xr, wb, bias=bias, stats=True) if want_stats else (tg.gemm_nt(xr, wb, bias=bias), None)
+        out, stats, wt = _rows_forward(ctx, x, xr, weight, bias, None, want_stats, keep_pad, pool_ns, link)
         ctx.save_for_backward(xr, weight, wt)
-        ctx.geom = (tuple(x.shape), x.dim(), N, Np, K, Kw, bias is not None, x.dtype)
-        # keep_pad: the caller (a BatchNorm over the padded width follows) takes all round8(N) channels, the extra ones zero
-        out = _rows_to_layout(y, x, Np if keep_pad else N)
-        if stats is not None:
-            ctx.mark_non_differentiable(stats)
         return out, stats
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dstats=None):
-        from . import train_gemm as tg
         if dy is None:
             return None, None, None, None, None, None, None
         xr, weight, wt = ctx.saved_tensors
-        xshape, xdim, N, Np, K, Kw, has_bias, xdtype = ctx.geom
-        R = xr.shape[0]
-        dyr = tg.row_view(dy)
-        if dyr is None or dyr.dtype != torch.bfloat16 or dyr.shape[1] != Np or dyr.stride(0) % 8:
-            # a gradient that does not arrive as bf16 rows of the padded width: one copy into that form
-            nc = dy.shape[1]                                  # N, or Np when the forward kept the padding
-            src = dy.movedim(1, -1).reshape(R, nc) if xdim > 2 else dy
-            dyr = torch.zeros((R, Np), dtype=torch.bfloat16, device=dy.device) if Np != nc else torch.empty((R, Np), dtype=torch.bfloat16, device=dy.device)
-            dyr[:, :nc].copy_(src)
+        xshape, xdim, _, Np, K, _, _, xdtype = ctx.geom
+        dyr = _grad_rows(dy, xr.shape[0], Np, xdim)
         dx = None
         dyr, dxr, _ = _take_lazy_bn_backward(ctx.link, dyr, wt, ctx.needs_input_grad[0])
         if ctx.needs_input_grad[0]:
@@ -349,11 +456,7 @@ class _RowsGemm(Function):
             dx = _rows_to_layout(dxr, None, K, xshape, xdim)
             if xdtype != torch.bfloat16:
                 dx = dx.to(xdtype)
-        dw = tg.wgrad(dyr, xr)                               # (Np, K) fp32
-        dw = dw[:N, :Kw].reshape(weight.shape)
-        db = None
-        if has_bias:   # column sums of the gradient rows (torch's strided reduction over 8 of them took 0.28 ms at 524288 rows)
-            db = tg.colsum(dyr)[:N] if Np <= 512 else dyr[:, :N].sum(0, dtype=torch.float32)
+        dw, db = _param_grads(dyr, xr, weight, ctx.geom)
         return dx, dw, db, None, None, None, None
 
 
@@ -369,15 +472,10 @@ class _BnReluRowsGemm(Function):
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, stats, gamma, beta, running_mean, running_var, eps, momentum, weight, bias, want_stats, keep_pad,
                 in_link=None, out_link=None, pool_ns=0):
-        from . import train_gemm as tg
-        ctx.in_link, ctx.link = in_link, out_link
-        ctx.set_materialize_grads(False)
+        ctx.in_link = in_link
         xr = tg.row_view(x)
         R, K = xr.shape
-        N = weight.shape[0]
-        w2 = weight.reshape(N, -1)
-        Kw, Np = w2.shape[1], _round8(N)
-        assert xr.dtype == torch.bfloat16 and Kw <= K < Kw + 8 and K % 8 == 0 and (stats is None or stats.shape[1:] == (K, 2))
+        assert xr.dtype == torch.bfloat16 and (stats is None or stats.shape[1:] == (K, 2))
         coef = torch.empty((4, K), dtype=torch.float32, device=x.device)
         if stats is None:
             # x does not come from a contraction (the heat-map head's depthwise output): the statistics pass of the operator on its own,
@@ -391,67 +489,18 @@ class _BnReluRowsGemm(Function):
             _native.call("pdm_bn_finalize_stats", torch.cuda.current_stream(x.device).cuda_stream, R, K, gamma.data_ptr(), beta.data_ptr(),
                          float(eps), float(momentum), running_mean.data_ptr(), running_var.data_ptr(), coef.data_ptr(), stats.data_ptr(),
                          stats.shape[0])
-        wb, wt = tg.pack_weight_pair(w2, Np, K)
-        if bias is not None and Np != N:
-            bias = torch.cat([bias.detach().float(), bias.new_zeros(Np - N, dtype=torch.float32)])
-        if pool_ns and want_stats and out_link is not None:
-            y, st, out_link['pool'] = tg.gemm_nt(xr, wb, bias=bias, stats=True, x_bn_coef=coef, pool_ns=pool_ns)
-        elif want_stats:
-            y, st = tg.gemm_nt(xr, wb, bias=bias, stats=True, x_bn_coef=coef)
-        else:
-            y, st = tg.gemm_nt(xr, wb, bias=bias, x_bn_coef=coef), None
+        out, st, wt = _rows_forward(ctx, x, xr, weight, bias, coef, want_stats, keep_pad, pool_ns, out_link)
         ctx.save_for_backward(xr, coef, weight, wt)
-        ctx.geom = (tuple(x.shape), x.dim(), N, Np, K, Kw, bias is not None)
-        out = _rows_to_layout(y, x, Np if keep_pad else N)
-        if st is not None:
-            ctx.mark_non_differentiable(st)
         return out, st
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dstats=None):
-        from . import train_gemm as tg
         if dy is None:
             return (None,) * 15
         xr, coef, weight, wt = ctx.saved_tensors
-        xshape, xdim, N, Np, K, Kw, has_bias = ctx.geom
-        R = xr.shape[0]
-        dyr = tg.row_view(dy)
-        if dyr is None or dyr.dtype != torch.bfloat16 or dyr.shape[1] != Np or dyr.stride(0) % 8:
-            nc = dy.shape[1]
-            src = dy.movedim(1, -1).reshape(R, nc) if xdim > 2 else dy
-            dyr = torch.zeros((R, Np), dtype=torch.bfloat16, device=dy.device) if Np != nc else torch.empty((R, Np), dtype=torch.bfloat16, device=dy.device)
-            dyr[:, :nc].copy_(src)
-        # the gradient statistics of the BatchNorm in front (over da and x) come out of the contraction that forms da
-        bs = (xr, coef) if BWD_STATS_IN_GEMM and xr.stride(0) % 8 == 0 else None
-        dyr, da, partial = _take_lazy_bn_backward(ctx.link, dyr, wt, True, bs)   # this layer's own output gradient may arrive unformed (see there)
-        if da is None:                                       # gradient of relu(bn(x)), (R, K) bf16
-            da, partial = tg.gemm_nt_bs(dyr, wt, xr, coef) if bs is not None else (tg.gemm_nt(dyr, wt), None)
-        dw = tg.wgrad(dyr, xr, x_bn_coef=coef)[:N, :Kw].reshape(weight.shape)   # the layer's input recomputed while it is read
-        db = None
-        if has_bias:
-            db = tg.colsum(dyr)[:N] if Np <= 512 else dyr[:, :N].sum(0, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dy.device).cuda_stream
-        if partial is not None:
-            grads = tg.bn_bwd_finalize(R, coef, partial)
-        else:
-            grads = torch.empty((4, K), dtype=torch.float32, device=dy.device)
-            parts = _native.lib().pdm_bn_parts(0, R, K, 1)
-            scratch = torch.empty((parts, K, 2), dtype=torch.float32, device=dy.device)
-            _native.call("pdm_bn_relu_backward_stats", stream, 1, 0, R, K, 1, xr.data_ptr(), da.data_ptr(), coef.data_ptr(),
-                         grads.data_ptr(), scratch.data_ptr(), 1)
-        if LAZY_BN_BACKWARD and ctx.in_link is not None:
-            # The BatchNorm + ReLU backward's elementwise half is left to the producer of x: its data gradient forms
-            # dx = scale (da [bn(x) > 0] - p - (x - mean) q) while it reads da and x (pdm_tg_gemm_nt_dy) and writes it out for its
-            # weight gradient.  What travels back through autograd is `da` itself; the link says how to read it.
-            ctx.in_link['lazy'] = (xr, coef, grads, da.data_ptr())
-            dx = da
-        else:
-            dx = torch.empty_like(xr)
-            _native.call("pdm_bn_relu_backward_apply", stream, 1, 0, R, K, 1, xr.data_ptr(), da.data_ptr(), dx.data_ptr(), coef.data_ptr(),
-                         grads.data_ptr(), 1)
-        return (_rows_to_layout(dx, None, K, xshape, xdim), None, grads[0], grads[1], None, None, None, None, dw, db, None, None,
-                None, None, None)
+        dx, grads, dw, db = _act_rows_backward(ctx, dy, xr, coef, None, weight, wt)
+        return dx, None, grads[0], grads[1], None, None, None, None, dw, db, None, None, None, None, None
 
 
 _identity_coef = {}
@@ -470,84 +519,51 @@ def _relu_coef(K, device):
 
 class _ReluRowsGemm(Function):
     """layer(relu(x)) for x = the raw bf16 rows a _RowsGemm just produced (Conv -> ReLU -> Conv without a BatchNorm: the heat-map
-    head's output stack): the ReLU rides in the second contraction's load path and its backward in the first one's data gradient,
-    through the BatchNorm + ReLU forms of the kernels with identity coefficients (_relu_coef) — relu(x) is never written, its
-    gradient mask never applied in a pass of its own (72 M elements at bs = 32: ~0.13 ms of a step as torch kernels)."""
+    head's output stack): _BnReluRowsGemm's path with identity coefficients (_relu_coef) in place of the finalize step and of the
+    gradient statistics — the ReLU rides in the second contraction's load path and its backward in the first one's data gradient;
+    relu(x) is never written, its gradient mask never applied in a pass of its own (72 M elements at bs = 32: ~0.13 ms of a step
+    as torch kernels)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, weight, bias, want_stats, keep_pad, in_link=None, out_link=None):
-        from . import train_gemm as tg
-        ctx.in_link, ctx.link = in_link, out_link
-        ctx.set_materialize_grads(False)
+        ctx.in_link = in_link
         xr = tg.row_view(x)
-        R, K = xr.shape
-        N = weight.shape[0]
-        w2 = weight.reshape(N, -1)
-        Kw, Np = w2.shape[1], _round8(N)
-        assert xr.dtype == torch.bfloat16 and Kw <= K < Kw + 8 and K % 8 == 0
-        coef, _ = _relu_coef(K, x.device)
-        wb, wt = tg.pack_weight_pair(w2, Np, K)
-        if bias is not None and Np != N:
-            bias = torch.cat([bias.detach().float(), bias.new_zeros(Np - N, dtype=torch.float32)])
-        if want_stats:
-            y, st = tg.gemm_nt(xr, wb, bias=bias, stats=True, x_bn_coef=coef)
-        else:
-            y, st = tg.gemm_nt(xr, wb, bias=bias, x_bn_coef=coef), None
+        out, st, wt = _rows_forward(ctx, x, xr, weight, bias, _relu_coef(xr.shape[1], x.device)[0], want_stats, keep_pad, 0, out_link)
         ctx.save_for_backward(xr, weight, wt)
-        ctx.geom = (tuple(x.shape), x.dim(), N, Np, K, Kw, bias is not None)
-        out = _rows_to_layout(y, x, Np if keep_pad else N)
-        if st is not None:
-            ctx.mark_non_differentiable(st)
         return out, st
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dstats=None):
-        from . import train_gemm as tg
         if dy is None:
             return (None,) * 7
         xr, weight, wt = ctx.saved_tensors
-        xshape, xdim, N, Np, K, Kw, has_bias = ctx.geom
-        R = xr.shape[0]
-        coef, grads = _relu_coef(K, xr.device)
-        dyr = tg.row_view(dy)
-        if dyr is None or dyr.dtype != torch.bfloat16 or dyr.shape[1] != Np or dyr.stride(0) % 8:
-            nc = dy.shape[1]
-            src = dy.movedim(1, -1).reshape(R, nc) if xdim > 2 else dy
-            dyr = torch.zeros((R, Np), dtype=torch.bfloat16, device=dy.device) if Np != nc else torch.empty((R, Np), dtype=torch.bfloat16, device=dy.device)
-            dyr[:, :nc].copy_(src)
-        dyr, da, _ = _take_lazy_bn_backward(ctx.link, dyr, wt, True)
-        if da is None:
-            da = tg.gemm_nt(dyr, wt)                         # gradient of relu(x), (R, K) bf16
-        dw = tg.wgrad(dyr, xr, x_bn_coef=coef)[:N, :Kw].reshape(weight.shape)
-        db = None
-        if has_bias:
-            db = tg.colsum(dyr)[:N] if Np <= 512 else dyr[:, :N].sum(0, dtype=torch.float32)
-        if LAZY_BN_BACKWARD and ctx.in_link is not None:
-            ctx.in_link['lazy'] = (xr, coef, grads, da.data_ptr())     # the producer's data gradient applies the mask while it reads da and x
-            dx = da
-        else:
-            dx = torch.empty_like(xr)
-            _native.call("pdm_bn_relu_backward_apply", torch.cuda.current_stream(dy.device).cuda_stream, 1, 0, R, K, 1, xr.data_ptr(),
-                         da.data_ptr(), dx.data_ptr(), coef.data_ptr(), grads.data_ptr(), 1)
-        return _rows_to_layout(dx, None, K, xshape, xdim), dw, db, None, None, None, None
+        coef, grads = _relu_coef(xr.shape[1], xr.device)
+        dx, _, dw, db = _act_rows_backward(ctx, dy, xr, coef, grads, weight, wt)
+        return dx, dw, db, None, None, None, None
+
+
+def _contraction_width(layer, x):
+    """in-features of `layer` if it is a Linear, or a plain 1x1 Conv1d / Conv2d (stride 1, no padding, dilation or groups) of
+    x's rank, else None: the layers that are one contraction over the channel axis of x"""
+    if isinstance(layer, nn.Linear):
+        return layer.in_features
+    if (all(k == 1 for k in layer.kernel_size) and all(v == 1 for v in layer.stride) and all(v == 0 for v in layer.padding)
+            and all(v == 1 for v in layer.dilation) and layer.groups == 1 and isinstance(layer.padding, tuple)
+            and x.dim() == layer.weight.dim()):
+        return layer.in_channels
+    return None
 
 
 def relu_rows_linear(x, layer, want_stats=False, keep_pad=False, in_link=None, out_link=None):
     """layer(relu(x)) through _ReluRowsGemm for x fresh out of a rows contraction, or (None, None) when the form does not apply."""
-    from . import train_gemm as tg
-    if not (ENABLED and ROWS_GEMM and BN_IN_GEMM and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] <= 512 and _bf16_autocast()
+    if not (ENABLED and ROWS_GEMM and BN_IN_GEMM and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] <= 512 and bf16_autocast()
             and layer.weight.dtype == torch.float32 and x.dim() in (2, 3, 4) and in_link is not None):
         return None, None
-    if isinstance(layer, nn.Linear):
-        kin = layer.in_features
-    else:
-        if not (all(k == 1 for k in layer.kernel_size) and all(v == 1 for v in layer.stride) and all(v == 0 for v in layer.padding)
-                and all(v == 1 for v in layer.dilation) and layer.groups == 1 and isinstance(layer.padding, tuple)
-                and x.dim() == layer.weight.dim()):
-            return None, None
-        kin = layer.in_channels
+    kin = _contraction_width(layer, x)
+    if kin is None:
+        return None, None
     K = x.shape[1]
     xr = tg.row_view(x)
     if K != _round8(kin) or K % 8 or xr is None or xr.stride(0) != K:
@@ -558,84 +574,44 @@ def relu_rows_linear(x, layer, want_stats=False, keep_pad=False, in_link=None, o
 def bn_rows_linear(x, stats, bn, layer, want_stats=False, keep_pad=False, in_link=None, out_link=None, pool_ns=0):
     """layer(relu(bn(x))) through _BnReluRowsGemm, or (None, None) when the form does not apply (the caller then runs the
     BatchNorm operator and the layer one after the other)."""
-    from . import train_gemm as tg
-    if not (ENABLED and ROWS_GEMM and BN_IN_GEMM and x.is_cuda and x.shape[1] <= 512 and _bf16_autocast() and layer.weight.dtype == torch.float32
+    if not (ENABLED and ROWS_GEMM and BN_IN_GEMM and x.is_cuda and x.shape[1] <= 512 and bf16_autocast() and layer.weight.dtype == torch.float32
             and x.dtype == torch.bfloat16 and x.dim() in (2, 3, 4) and (applies(x, bn) or _padded_applies(x, bn))):
         return None, None
     if stats is None and (not BN_FROM_X or x.shape[1] != bn.num_features):     # (no statistics from a producer: see BN_FROM_X)
         return None, None
-    if isinstance(layer, nn.Linear):
-        kin = layer.in_features
-    else:
-        if not (all(k == 1 for k in layer.kernel_size) and all(v == 1 for v in layer.stride) and all(v == 0 for v in layer.padding)
-                and all(v == 1 for v in layer.dilation) and layer.groups == 1 and isinstance(layer.padding, tuple)
-                and x.dim() == layer.weight.dim()):
-            return None, None
-        kin = layer.in_channels
+    kin = _contraction_width(layer, x)
+    if kin is None:
+        return None, None
     C, K = bn.num_features, x.shape[1]
     xr = tg.row_view(x)
     if kin != C or K != _round8(C) or xr is None or xr.stride(0) != K or (stats is not None and stats.shape[1] != K) or _layout(x) is None \
             or _layout(x)[0] != 0:
         return None, None
     gamma, beta, rm, rv = bn.weight, bn.bias, bn.running_mean, bn.running_var
-    if K != C:   # zero-padded width: zero gamma / beta on the padding (it stays zero), temporary running statistics
-        z = bn.weight.new_zeros(K - C)
-        gamma, beta, rm, rv = torch.cat([gamma, z]), torch.cat([beta, z]), torch.cat([rm, z]), torch.cat([rv, z + 1.0])
+    if K != C:
+        gamma, beta, rm, rv = _padded_bn_params(bn, K)
     out = _BnReluRowsGemm.apply(x, stats, gamma, beta, rm, rv, bn.eps, bn.momentum, layer.weight, layer.bias, bool(want_stats), bool(keep_pad),
                                 in_link, out_link, int(pool_ns))
+    if K != C:
+        _keep_running_stats(bn, rm, rv)
     with torch.no_grad():
-        if K != C:
-            bn.running_mean.copy_(rm[:C]); bn.running_var.copy_(rv[:C])
         _bump(bn)
     return out
-
-
-# 1 (default): a BatchNorm + ReLU whose bf16 input does NOT come from a rows contraction (the heat-map head's first one, behind the
-# depthwise convolution) still rides in the next contraction's load path: its statistics pass runs alone (pdm_bn_forward_coef), the
-# apply pass and the normalised tensor (288 MB at bs = 32) disappear, and its gradient statistics come out of that contraction's data
-# gradient like everywhere else.
-BN_FROM_X = os.environ.get("PDM_BN_FROM_X", "1") == "1"
-
-# 1 (default): BatchNorm + ReLU of an inner layer ride in the next contraction's load path (_BnReluRowsGemm; bit-identical results,
-# the normalised tensor is never stored).  Measured at bs = 32, A/B twice: 26.17 / 26.24 ms per step with, 26.79 / 26.87
-# without.  (An earlier A/B read 29.4-29.9 against 29.3-29.4 and kept the separate operator: the step was bound by the HOST
-# then — a pageable host-to-device copy and two boolean-mask indexings in the target assignment stalled the issue thread
-# every step — so device-side savings did not show.)
-BN_IN_GEMM = os.environ.get("PDM_BN_IN_GEMM", "1") == "1"
-
-
-def _rows_to_layout(rows, like, channels, shape=None, dim=None):
-    """(R, ld) row storage -> the logical tensor of `like`'s layout with `channels` channels (a view)."""
-    shape = tuple(like.shape) if shape is None else shape
-    dim = like.dim() if dim is None else dim
-    if dim == 2:
-        return rows[:, :channels]
-    lead = (shape[0],) + tuple(shape[2:])
-    return rows.view(*lead, rows.shape[1])[..., :channels].movedim(-1, 1)
 
 
 def rows_linear(x, layer, want_stats=False, keep_pad=False, link=None, pool_ns=0):
     """layer(x) for a 1x1 convolution / Linear through _RowsGemm when x is (castable to) bf16 rows on the GPU under bf16
     autocast; returns (y, stats) — stats None when not requested or not taken; (None, None) when the form does not apply.
     keep_pad: y keeps round8(out_channels) channels (the extra ones zero) for a BatchNorm over the padded width."""
-    from . import train_gemm as tg
-    if not (ENABLED and ROWS_GEMM and x.is_cuda and _bf16_autocast() and layer.weight.dtype == torch.float32 and x.dim() in (2, 3, 4)):
+    if not (ENABLED and ROWS_GEMM and x.is_cuda and bf16_autocast() and layer.weight.dtype == torch.float32 and x.dim() in (2, 3, 4)):
         return None, None
-    if isinstance(layer, nn.Linear):
-        kin = layer.in_features
-    else:
-        if not (all(k == 1 for k in layer.kernel_size) and all(v == 1 for v in layer.stride) and all(v == 0 for v in layer.padding)
-                and all(v == 1 for v in layer.dilation) and layer.groups == 1 and isinstance(layer.padding, tuple)
-                and x.dim() == layer.weight.dim()):
-            return None, None
-        kin = layer.in_channels
+    kin = _contraction_width(layer, x)
+    if kin is None:
+        return None, None
     K = x.shape[1]
     if x.dtype not in (torch.bfloat16, torch.float32) or K != _round8(kin) or tg.row_view(x) is None:
         return None, None
     return _RowsGemm.apply(x, layer.weight, layer.bias, bool(want_stats), bool(keep_pad), link, int(pool_ns))
-
-
-ROWS_GEMM = os.environ.get("PDM_ROWS_GEMM", "1") != "0"   # 0: the round-2 path (vendor GEMMs) for A/B measurements
 
 
 class _LinearSplitK(Function):
@@ -670,14 +646,10 @@ class _LinearSplitK(Function):
 def tall_linear(x, lin):
     """lin(x) with the split-K weight gradient when x is a tall bf16-autocast matrix on the GPU."""
     if (ENABLED and x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] >= 8 * _LinearSplitK.SLAB
-            and x.shape[0] % _LinearSplitK.SLAB == 0 and _bf16_autocast() and lin.weight.requires_grad
+            and x.shape[0] % _LinearSplitK.SLAB == 0 and bf16_autocast() and lin.weight.requires_grad
             and lin.weight.dtype == torch.float32):
         return _LinearSplitK.apply(x, lin.weight, lin.bias)
     return lin(x)
-
-
-def _bf16_autocast():
-    return torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
 
 
 def _slab(rows):
@@ -742,11 +714,8 @@ class _Conv1x1SplitK(Function):
 
 def conv1x1(x, conv):
     """conv(x) for a plain 1x1 convolution, with the split-K weight gradient under bf16 autocast on the GPU."""
-    if (ENABLED and x.is_cuda and _bf16_autocast() and conv.bias is None and conv.weight.requires_grad
-            and conv.weight.dtype == torch.float32
-            and all(k == 1 for k in conv.kernel_size) and all(v == 1 for v in conv.stride) and all(v == 0 for v in conv.padding)
-            and all(v == 1 for v in conv.dilation) and conv.groups == 1 and isinstance(conv.padding, tuple)
-            and x.dim() == conv.weight.dim() and x.numel() >= (1 << 20)):
+    if (ENABLED and x.is_cuda and bf16_autocast() and conv.bias is None and conv.weight.requires_grad
+            and conv.weight.dtype == torch.float32 and _contraction_width(conv, x) is not None and x.numel() >= (1 << 20)):
         return _Conv1x1SplitK.apply(x, conv.weight)
     return conv(x)
 
@@ -832,7 +801,7 @@ class TrainSequential(nn.Sequential):
         pool_ns = tail['pool_ns'] if tail is not None else 0
         i = 0
         stats = None      # column sums of x taken by the GEMM that produced it, for the BatchNorm right behind it
-        link = None       # shared with the autograd node that produced x (a rows GEMM): see _take_lazy_bn_backward
+        link = None       # shared with the autograd node that produced x (a rows GEMM): the module docstring's `link`
         while i < len(mods):
             m = mods[i]
             if isinstance(m, _BN) and (applies(x, m) or _padded_applies(x, m)):
@@ -850,7 +819,7 @@ class TrainSequential(nn.Sequential):
                         i += 3
                         continue
                 # an fp32 map (the heat-map head's depthwise output) that a bf16 contraction reads next: the BatchNorm writes bf16
-                to_bf16 = (x.dtype == torch.float32 and ROWS_GEMM and nxt is not None and _bf16_autocast()
+                to_bf16 = (x.dtype == torch.float32 and ROWS_GEMM and nxt is not None and bf16_autocast()
                            and (isinstance(nxt, nn.Linear) or (type(nxt) in (nn.Conv1d, nn.Conv2d) and all(k == 1 for k in nxt.kernel_size)
                                                                and nxt.groups == 1)))
                 # (stats is not None: x is the direct output of a rows GEMM node, which shares `link` with this operator)

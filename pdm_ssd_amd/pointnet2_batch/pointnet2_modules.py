@@ -156,7 +156,7 @@ class _PointnetSAModuleBase(nn.Module):
             return self._forward_fused(packs, xyz, features, new_xyz, idx_list)
         from .. import fused_bn
         rows_path = (CHANNELS_LAST_TRAINING and fused_bn.ENABLED and fused_bn.ROWS_GEMM and xyz.is_cuda
-                     and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)
+                     and fused_bn.bf16_autocast())
         if features is not None and not rows_path:
             features = features.contiguous()
         pooled = []
@@ -286,8 +286,7 @@ class PointnetFPModule(nn.Module):
             from .. import fused_bn
             rows_path = (self.training and torch.is_grad_enabled() and CHANNELS_LAST_TRAINING and fused_bn.ENABLED and fused_bn.ROWS_GEMM
                          and known_feats.is_cuda and isinstance(self.mlp, TrainSequential)
-                         and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
-                         and known.shape[1] <= 16384 and unknown.shape[1] <= 65535)
+                         and fused_bn.bf16_autocast() and known.shape[1] <= 16384 and unknown.shape[1] <= 65535)
             if rows_path:
                 # interpolation + concat written once as the bf16 rows the MFMA layers read (zero channels up to a multiple
                 # of 8); the features arrive and leave as (B, C, n) VIEWS of point-major storage: nothing is transposed

@@ -493,3 +493,73 @@ def test_biased_conv_in_front_of_batchnorm_counts_only_live_rows(dev):
     torch.testing.assert_close(net[1].running_mean.cpu(), ref[1].running_mean, rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(net[1].running_var.cpu(), ref[1].running_var, rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(y.detach().float().cpu(), want.detach(), rtol=2e-2, atol=2e-2)
+
+
+def _integer_rows_case(N, R=200, K=16, _cache={}):
+    """rows x (R, K), weight (N, K), bias (N), output-gradient weights G (R, N), integers of {-2, ..., 2} in float64 on the CPU, and per
+    node the float64 results (y, dx, dW, db) of layer(x) and of layer(relu(x)): made once per N, shared by every case, never changed"""
+    if N not in _cache:
+        g = torch.Generator().manual_seed(100 + N)
+        x, w, b, G = (torch.randint(-2, 3, s, generator=g).double() for s in ((R, K), (N, K), (N,), (R, N)))
+        want = {}
+        for node, a, mask in (("_RowsGemm", x, torch.ones_like(x)), ("_ReluRowsGemm", torch.relu(x), (x > 0).double())):
+            want[node] = (a @ w.t() + b, (G @ w) * mask, G.t() @ a, G.sum(0))
+        _cache[N] = (x, w, b, G, want)
+    return _cache[N]
+
+
+def _to_form(rows, form):
+    """(R, C) rows -> the logical tensor of the input form over that very storage order (R = 200 = 2 x 100 = 2 x 25 x 4)"""
+    C = rows.shape[1]
+    if form == "rows":
+        return rows
+    lead = (2, 100) if form == "conv1d" else (2, 25, 4)
+    return rows.reshape(*lead, C).movedim(-1, 1)           # (2, C, 100) stored (2, 100, C) / channels-last (2, C, 25, 4)
+
+
+def _from_form(t):
+    return t if t.dim() == 2 else t.movedim(1, -1).reshape(-1, t.shape[1])
+
+
+def _run_rows_node(dev, node, form, grad_form, N):
+    """one node on the integer case: (y, dx, dW, db) as float64 rows / matrices on the CPU"""
+    x, w, b, G, _ = _integer_rows_case(N)
+    wshape = {"rows": (N, 16), "conv1d": (N, 16, 1), "conv2d": (N, 16, 1, 1)}[form]
+    xg = _to_form(x.to(dev).bfloat16(), form).detach().requires_grad_(True)
+    wg, bg = w.float().reshape(wshape).to(dev).requires_grad_(True), b.float().to(dev).requires_grad_(True)
+    if node == "_RowsGemm":
+        y, _ = fused_bn._RowsGemm.apply(xg, wg, bg, False, False, None, 0)
+    else:
+        y, _ = fused_bn._ReluRowsGemm.apply(xg, wg, bg, False, False, None, None)
+    assert y.dtype == torch.bfloat16 and y.shape == _to_form(G, form).shape
+    if grad_form == "backward":
+        (y.float() * _to_form(G.float().to(dev), form)).sum().backward()
+        dx, dw, db = xg.grad, wg.grad, bg.grad
+    else:
+        # an fp32 gradient in standard-contiguous memory: for the convolutions that is position-fastest, not rows; a contiguous (R, N)
+        # matrix IS rows (of the padded width when N = 8), so the 2-D form hands in the transpose of a contiguous (N, R) matrix
+        Gd = _to_form(G.float().to(dev), form)
+        Gd = Gd.t().contiguous().t() if form == "rows" else Gd.contiguous()
+        assert Gd.dtype == torch.float32 and (Gd.t() if form == "rows" else Gd).is_contiguous()
+        dx, dw, db = torch.autograd.grad(y, (xg, wg, bg), grad_outputs=Gd)
+    assert dx.dtype == torch.bfloat16 and dx.shape == xg.shape and dw.dtype == torch.float32 and dw.shape == wshape and db.shape == (N,)
+    return tuple(t.detach().double().cpu() for t in (_from_form(y), _from_form(dx), dw.reshape(N, 16), db))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grad_form", ["backward", "grad_outputs"])
+@pytest.mark.parametrize("form", ["rows", "conv1d", "conv2d"])
+def test_rows_nodes_are_exact_on_integer_data(dev, form, grad_form):
+    """The forward and backward bodies the rows nodes share (fused_bn._rows_forward, _grad_rows, _param_grads, the apply half of
+    _bn_relu_backward_rows), through _RowsGemm and _ReluRowsGemm on integers of {-2, ..., 2}: K = 16, N = 8 and 20 (storage padded
+    to 24: the zero-filled gradient rows and the [:N] slices), R = 200 rows (no multiple of the 128-row tile).  |y| <= 16 * 4 + 2 = 66
+    and |dx| <= 24 * 4 = 96 are exact in bf16, |dW| <= 800 and |db| <= 400 in fp32: everything EQUALS the float64 products on the CPU.
+    form: 2-D rows through a Linear / a (2, 16, 100) view of (2, 100, 16) storage through a Conv1d / channels-last (2, 16, 25, 4)
+    through a Conv2d.  grad_form: the gradient of `loss.backward()` as autograd hands it over (rows already when N = 8) / an fp32
+    tensor whose memory is not rows through torch.autograd.grad(grad_outputs=) — the engine casts it to bf16 and keeps its strides,
+    so every case of this form takes the one copy into (R, round8(N)) bf16 rows."""
+    for node in ("_RowsGemm", "_ReluRowsGemm"):
+        for N in (8, 20):
+            got = _run_rows_node(dev, node, form, grad_form, N)
+            for name, g, w in zip(("y", "dx", "dW", "db"), got, _integer_rows_case(N)[4][node]):
+                assert torch.equal(g, w), (node, N, name, float((g - w).abs().max()))

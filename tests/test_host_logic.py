@@ -132,3 +132,24 @@ def test_train_sequential_after_convert_sync_batchnorm():
         assert fused_bn._stats_wanted(list(conv), 0) == (False, False)
     finally:
         dist.is_initialized, dist.get_world_size = real
+
+
+@pytest.mark.parametrize("kind,args,kwargs,shape,want", [
+    ("Linear", (16, 8), {}, (5, 16), 16),
+    ("Conv1d", (16, 8, 1), {}, (2, 16, 7), 16),
+    ("Conv2d", (16, 8, 1), {}, (2, 16, 5, 3), 16),
+    ("Conv2d", (16, 8, 3), {}, (2, 16, 5, 3), None),
+    ("Conv2d", (16, 8, 1), {"stride": 2}, (2, 16, 5, 3), None),
+    ("Conv2d", (16, 8, 1), {"padding": "same"}, (2, 16, 5, 3), None),       # a string, not a tuple of zeros
+    ("Conv2d", (16, 8, 1), {"groups": 2}, (2, 16, 5, 3), None),
+    ("Conv2d", (16, 8, 1), {"dilation": 2}, (2, 16, 5, 3), None),
+    ("Conv2d", (16, 8, 1), {}, (2, 16, 7), None),                           # a Conv2d given a 3-D input
+])
+def test_contraction_width_takes_linear_and_plain_1x1_convolutions_only(kind, args, kwargs, shape, want):
+    """fused_bn._contraction_width: the in-features of a Linear or of a plain 1x1 Conv1d / Conv2d of the input's rank, None for
+    anything that is not ONE contraction over the channel axis — the condition rows_linear, bn_rows_linear, relu_rows_linear and
+    conv1x1 each spelled out before they shared it."""
+    import torch
+    from pdm_ssd_amd import fused_bn
+    layer = getattr(torch.nn, kind)(*args, **kwargs)
+    assert fused_bn._contraction_width(layer, torch.zeros(shape)) == want

@@ -543,6 +543,39 @@ int pdm_post_process(void *stream, int B, int C, int multi_class, long long rows
  * pts (B,M,3) -> box_idx (B,M) = first containing box of the sample's list, -1 for background (every entry written). */
 int pdm_points_in_boxes(void *stream, int B, int T, int M, const float *boxes, const float *pts, int *box_idx);
 
+/* ---- RoI point pooling and RoI-aware pooling (csrc/roi_pool.hip) -----------------------------------------------------------
+ * The reference's roipoint_pool3d_cuda.forward (pcdet/ops/roipoint_pool3d/src/roipoint_pool3d_kernel.cu:22-134): xyz (B,N,3),
+ * boxes (B,M,7) ALREADY enlarged, feats (B,N,C) -> pooled (B,M,S,3+C), empty_flag (B,M) int32.  Per (sample, box): the points
+ * inside (check_pt_in_box3d, the test of pdm_points_in_boxes) in ascending index, the first S of them; with 0 < cnt < S
+ * row k >= cnt repeats row k % cnt; a row is [x, y, z, feats...] copied bit for bit.  cnt == 0: flag 1 and the box's S rows
+ * are NOT written (the caller zero-fills, as the reference's); every flag is written.  One launch, no (B,N,M) intermediate,
+ * nothing allocated.  B, N, M or S == 0: success, nothing written. */
+int pdm_roipoint_pool3d(void *stream, int B, int N, int M, int C, int S, const float *xyz, const float *boxes, const float *feats,
+                        float *pooled, int *empty_flag);
+/* The same with the PointRCNN head's epilogue (pcdet/models/roi_heads/pointrcnn_head.py:121-129) in the launch: rois
+ * (B,M,roi_stride >= 7 floats per row) NOT enlarged — their three sizes grow by (extra_x, extra_y, extra_z) here —, the pooled
+ * coordinates minus the RoI centre and rotated by -heading about z (fp32, one rounding per operation:
+ * x' = x cos a + y (-sin a), y' = x sin a + y cos a, a = -heading), and ZEROS in all S rows of an empty box: no caller fill. */
+int pdm_roipoint_pool3d_canonical(void *stream, int B, int N, int M, int C, int S, const float *xyz, const float *rois, int roi_stride,
+                                  float extra_x, float extra_y, float extra_z, const float *feats, float *pooled, int *empty_flag);
+/* The reference's roiaware_pool3d_cuda.forward / backward (pcdet/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu:39-307).
+ * rois (K,7), pts (P,3), feats (P,C), pool_method 0 = max, 1 = avg -> pts_idx_of_voxels (K,ox,oy,oz,max_pts) int32 (slot 0 the
+ * count capped at max_pts - 1, then the voxel's first max_pts - 1 point indices ascending, zeros behind: FULLY written), argmax
+ * (K,ox,oy,oz,C) int32 (max only: always written, -1 = no winner) and pooled (K,ox,oy,oz,C) (NOT written for a voxel without
+ * winner / without points: the caller zero-fills).  Max is a strict > from -inf (first index wins ties, NaN never wins); avg adds
+ * in list order and divides once by float(count).  Each out size 1 .. 256, max_pts >= 2.  workspace: K * ox * oy * oz ints when
+ * the voxel grid of a box exceeds 8192 cells, else none (pdm_roiaware_pool3d_workspace_bytes).
+ * backward: grad_out (K,ox,oy,oz,C) -> grad_in (P,C), FULLY written and deterministic (terms added in ascending (box, voxel)
+ * order): max, grad_out to the argmax point; avg, grad_out * (1 / max(count, 1)) to every listed point.  It gathers per point, so
+ * it takes rois and pts as well; argmax is read for max only, pts_idx_of_voxels for avg only. */
+size_t pdm_roiaware_pool3d_workspace_bytes(int K, int out_x, int out_y, int out_z);
+int pdm_roiaware_pool3d_forward(void *stream, int K, int P, int C, int max_pts, int out_x, int out_y, int out_z, const float *rois,
+                                const float *pts, const float *feats, int pool_method, void *workspace, size_t workspace_bytes,
+                                int *pts_idx_of_voxels, int *argmax, float *pooled);
+int pdm_roiaware_pool3d_backward(void *stream, int K, int P, int C, int max_pts, int out_x, int out_y, int out_z, const float *rois,
+                                 const float *pts, const int *pts_idx_of_voxels, const int *argmax, const float *grad_out,
+                                 int pool_method, float *grad_in);
+
 /* ---- input path -------------------------------------------------------
  * sample_points (pcdet/datasets/processor/data_processor.py:182-212) + the batch-index column of collate_batch
  * (pcdet/datasets/dataset.py:237-244) for B raw clouds resident in HBM: raw (sum counts, C) rows [x, y, z, ...],

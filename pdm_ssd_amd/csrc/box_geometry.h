@@ -2,6 +2,8 @@
 //   box_overlap_bev / iou_bev / iou_normal   iou3d_nms.hip, post_process.hip (through nms.h), augment.hip
 //   bev_radius / bev_circles_disjoint        the bounding-circle prefilter of those
 //   box_cos_sin / box_reach2 / point_in_box_margin   the point-in-box test of augment.hip and kitti_data.hip
+//   box_cos_sin_f / point_in_box3d / box_reach2_pool / roiaware_voxel   check_pt_in_box3d and the voxel of a point, shared by
+//                                                      points_in_boxes (iou3d_nms.hip) and the RoI pooling of roi_pool.hip
 // Boxes are 7 floats [x, y, z, dx, dy, dz, heading]; see iou3d_nms.hip for the geometry.
 #pragma once
 #include "common.h"
@@ -140,6 +142,57 @@ __device__ __forceinline__ bool point_in_box_margin(float dx, float dy, float pz
     const float lx = __fadd_rn(__fmul_rn(dx, c), __fmul_rn(dy, -s));
     const float ly = __fadd_rn(__fmul_rn(dx, s), __fmul_rn(dy, c));
     return (double)fabsf(lx) < (double)bx[3] / 2.0 + (double)1e-2f && (double)fabsf(ly) < (double)bx[4] / 2.0 + (double)1e-2f;
+}
+
+// ---- check_pt_in_box3d (roipoint_pool3d_kernel.cu:22-35, roiaware_pool3d_kernel.cu:23-36), one definition for
+// points_in_boxes (iou3d_nms.hip) and the RoI point / RoI-aware pooling (roi_pool.hip): |z - cz| > dz / 2 rejects (compared
+// in double), the local coordinates are fp32 from cosf(-rz) / sinf(-rz), one rounding per operation, then
+// |local| < d / 2 + 1e-5 compared in double.  lx, ly are written only when the height test passes.
+__device__ __forceinline__ void box_cos_sin_f(float rz, float *c, float *s) {
+    *c = cosf(-rz);
+    *s = sinf(-rz);
+}
+
+__device__ __forceinline__ bool point_in_box3d_cs(float x, float y, float z, const float *bx, float c, float s, float *lx, float *ly) {
+    if ((double)fabsf(z - bx[2]) > (double)bx[5] / 2.0) return false;
+    const float sx = x - bx[0], sy = y - bx[1];
+    *lx = sx * c + sy * (-s);
+    *ly = sx * s + sy * c;
+    return fabs((double)*lx) < (double)bx[3] / 2.0 + (double)1e-5f && fabs((double)*ly) < (double)bx[4] / 2.0 + (double)1e-5f;
+}
+
+__device__ __forceinline__ bool point_in_box3d(float x, float y, float z, const float *bx, float *lx, float *ly) {
+    if ((double)fabsf(z - bx[2]) > (double)bx[5] / 2.0) return false;   // before the trigonometry, as the reference
+    float c, s;
+    box_cos_sin_f(bx[6], &c, &s);
+    return point_in_box3d_cs(x, y, z, bx, c, s, lx, ly);
+}
+
+// squared bounding-circle reject radius of point_in_box3d, compared with sx * sx + sy * sy of the fp32 shifts sx = x - cx,
+// sy = y - cy.  A point that passes lies within sqrt((dx/2 + 1e-5)^2 + (dy/2 + 1e-5)^2) <= r + 1.42e-5 of the centre in
+// the ROUNDED local frame; the local coordinates differ from an exact rotation of (sx, sy) by at most ~4 * 2^-24 relative
+// (two products, a sum, cosf / sinf a few ulp off the unit circle) and sx * sx + sy * sy by 3 * 2^-24 relative: r * 1.001
+// covers both a thousand times over, 1e-4 covers the margin seven times, the last term is box_reach2's (NaN: never rejected).
+__device__ __forceinline__ float box_reach2_pool(const float *bx) {
+    const float r = bev_radius(bx);
+    const float lim = r * 1.001f + 1e-4f + 4e-5f * (fabsf(bx[0]) + fabsf(bx[1]) + r + 1.f);
+    return lim * lim;
+}
+
+// voxel of an in-box point (roiaware_pool3d_kernel.cu:57-73), all fp32: res = d / out, idx = int((local + d / 2) / res)
+// truncated toward zero, then the reference's clamp, which runs on `unsigned`: a negative index and an index >= out both
+// land in out - 1.  The quotient is first limited to [-1, 256] (out <= 256), which changes none of that and keeps the
+// conversion in range for a box of zero size (result unspecified there, but always a voxel of the grid).
+__device__ __forceinline__ unsigned roiaware_axis(float local, float d, int out) {
+    const float res = d / out;
+    const float q = fminf(fmaxf((local + d / 2) / res, -1.f), 256.f);
+    const unsigned i = (unsigned)(int)q;
+    return i < (unsigned)(out - 1) ? i : (unsigned)(out - 1);
+}
+
+__device__ __forceinline__ int roiaware_voxel(float lx, float ly, float z, const float *bx, int ox, int oy, int oz) {
+    const unsigned xi = roiaware_axis(lx, bx[3], ox), yi = roiaware_axis(ly, bx[4], oy), zi = roiaware_axis(z - bx[2], bx[5], oz);
+    return (int)((xi * oy + yi) * oz + zi);
 }
 
 }  // namespace pdm

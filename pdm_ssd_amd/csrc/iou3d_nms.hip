@@ -167,11 +167,8 @@ __global__ __launch_bounds__(256) void points_in_boxes_kernel(int T, int M, cons
         if (!live || found >= 0) continue;
         for (int k = 0; k < nk; ++k) {
             const float *bx = sb + k * 7;
-            if ((double)fabsf(z - bx[2]) > (double)bx[5] / 2.0) continue;
-            const float sx = x - bx[0], sy = y - bx[1];
-            const float c = cosf(-bx[6]), s = sinf(-bx[6]);
-            const float lx = sx * c + sy * (-s), ly = sx * s + sy * c;
-            if (fabs((double)lx) < (double)bx[3] / 2.0 + (double)1e-5f && fabs((double)ly) < (double)bx[4] / 2.0 + (double)1e-5f) {
+            float lx, ly;
+            if (point_in_box3d(x, y, z, bx, &lx, &ly)) {   // box_geometry.h, shared with roi_pool.hip
                 found = k0 + k;
                 break;
             }

@@ -32,6 +32,29 @@ PDM_SSD_CFG = {
                                        'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
 }
 
+# PointRCNN: the upstream project's published settings (its tools/cfgs/kitti_models/pointrcnn.yaml) restated as a dict — the
+# snapshot this repository was modelled on holds no YAML.  First stage = the backbone and point head above;
+# the second stage runs in eval mode only, so of TARGET_CONFIG only the box coder is read (the proposal-target sampler's
+# and the rcnn losses' settings are left out with the code that would read them).
+POINT_RCNN_CFG = {
+    'NAME': 'PointRCNN',
+    'BACKBONE_3D': dict(POINTRCNN_MSG_CFG),
+    'POINT_HEAD': dict(PDM_SSD_CFG['POINT_HEAD']),
+    'ROI_HEAD': {'NAME': 'PointRCNNHead', 'CLASS_AGNOSTIC': True,
+                 'ROI_POINT_POOL': {'POOL_EXTRA_WIDTH': [0.0, 0.0, 0.0], 'NUM_SAMPLED_POINTS': 512, 'DEPTH_NORMALIZER': 70.0},
+                 'XYZ_UP_LAYER': [128, 128], 'CLS_FC': [256, 256], 'REG_FC': [256, 256], 'DP_RATIO': 0.0, 'USE_BN': False,
+                 'SA_CONFIG': {'NPOINTS': [128, 32, -1], 'RADIUS': [0.2, 0.4, 100], 'NSAMPLE': [16, 16, 16],
+                               'MLPS': [[128, 128, 128], [128, 128, 256], [256, 256, 512]]},
+                 'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                                          'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                                'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                                         'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.85}},
+                 'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}},
+    'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False,
+                        'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.1,
+                                       'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
+}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -43,4 +66,13 @@ def synthetic_dataset(num_point_features=4):
 def build_pdm_ssd(model_cfg=None, num_point_features=4):
     from .detectors import build_network
     cfg = cfg_from_dict(PDM_SSD_CFG if model_cfg is None else model_cfg)
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))
+
+
+def build_point_rcnn(model_cfg=None, num_point_features=4):
+    """PointRCNN (eval mode: the second stage's training half is not built) from POINT_RCNN_CFG or a dict like it."""
+    import copy
+
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(POINT_RCNN_CFG if model_cfg is None else model_cfg))   # (the SA constructors edit MLPS)
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))

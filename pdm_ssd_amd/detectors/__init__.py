@@ -4,10 +4,12 @@ from collections import namedtuple
 
 from .detector3d_template import BACKBONES_3D, MAP_TO_BEV, Detector3DTemplate
 from .pdm_ssd import PDMSSD
+from .point_rcnn import PointRCNN
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'PDMSSD': PDMSSD,
+    'PointRCNN': PointRCNN,
 }
 
 

@@ -4,13 +4,14 @@ Contract restated from /root/reference/pcdet/models/detectors/detector3d_templat
 `build_<slot>` per slot, modules chosen by `NAME` from registry dicts, `model_info_dict` threading channel counts),
 :178-263 (post_processing: per-sample class-agnostic NMS over the head's boxes) and :330-359 (shape-filtered
 checkpoint loading).  The reference's template cannot be imported on this platform (it pulls in spconv,
-pcdet/utils/spconv_utils.py:3); the slots that only exist for voxel models (vfe, pfe, backbone_2d, roi_head) are kept
-as names so reference configs read naturally, and build nothing here.
+pcdet/utils/spconv_utils.py:3); the slots that only exist for voxel models (vfe, pfe, backbone_2d) are kept as names so
+reference configs read naturally, and build nothing here.  The roi_head slot builds the point-based RoI heads of
+roi_heads/ (PointRCNN's second stage), which need no spconv.
 """
 import torch
 import torch.nn as nn
 
-from .. import dense_heads
+from .. import dense_heads, roi_heads
 from ..iou3d_nms import iou3d_nms_utils
 from ..pdm_neck import PDMNeck
 from ..pointnet2_backbone import PointNet2MSG
@@ -72,7 +73,15 @@ class Detector3DTemplate(nn.Module):
         return self._unsupported('BACKBONE_2D', model_info_dict)
 
     def build_roi_head(self, model_info_dict):
-        return self._unsupported('ROI_HEAD', model_info_dict)
+        """ref :159-176: the point-based RoI heads need no spconv; built by NAME from roi_heads.__all__."""
+        cfg = _get(self.model_cfg, 'ROI_HEAD', None)
+        if cfg is None:
+            return None, model_info_dict
+        module = roi_heads.__all__[_get(cfg, 'NAME')](
+            model_cfg=cfg, input_channels=model_info_dict['num_point_features'],
+            num_class=self.num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1)
+        model_info_dict['module_list'].append(module)
+        return module, model_info_dict
 
     def build_backbone_3d(self, model_info_dict):
         cfg = _get(self.model_cfg, 'BACKBONE_3D', None)

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from .detector3d_template import Detector3DTemplate
+from .detector3d_template import Detector3DTemplate, _get
 
 # 1: in TRAINING the dense (heat-map) half of the hybrid head — forward, targets, loss and, because autograd runs a node's backward
 # on the stream of its forward, its whole backward — runs on a stream of its own beside the point half: two independent chains of
@@ -31,6 +31,7 @@ def _branch_stream(device):
 class PDMSSD(Detector3DTemplate):
     def __init__(self, model_cfg, num_class, dataset):
         super().__init__(model_cfg=model_cfg, num_class=num_class, dataset=dataset)
+        assert _get(model_cfg, 'ROI_HEAD', None) is None, 'ROI_HEAD: PDM-SSD is a one-stage detector (see detectors/point_rcnn.py)'
         self.module_list = self.build_networks()
         self._dense_loss = None
 

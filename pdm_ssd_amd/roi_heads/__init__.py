@@ -1,0 +1,8 @@
+"""RoI (second-stage) heads, registered by NAME as /root/reference/pcdet/models/roi_heads/__init__.py does."""
+from .pointrcnn_head import PointRCNNHead
+from .roi_head_template import RoIHeadTemplate
+
+__all__ = {
+    'RoIHeadTemplate': RoIHeadTemplate,
+    'PointRCNNHead': PointRCNNHead,
+}

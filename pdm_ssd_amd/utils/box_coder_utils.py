@@ -65,3 +65,50 @@ class PointResidualCoder(object):
             dxg, dyg, dzg = torch.split(torch.exp(box_encodings[..., 3:6]), 1, dim=-1)
         rg = torch.atan2(sint, cost)
         return torch.cat([xg, yg, zg, dxg, dyg, dzg, rg, *cts], dim=-1)
+
+
+
+class ResidualCoder(object):
+    """Anchor-relative box code of the RoI heads; behaviour of /root/reference/pcdet/utils/box_coder_utils.py:5-77.
+
+    code = [centre offset / (d, d, dz_a), log(size / size_a), heading - heading_a, extra columns - anchor's], d the
+    anchor's BEV diagonal.  encode_angle_by_sincos codes the heading as the two differences (cos - cos_a, sin - sin_a)
+    instead, which makes the code one column longer (code_size 8)."""
+
+    def __init__(self, code_size=7, encode_angle_by_sincos=False, **kwargs):
+        super().__init__()
+        self.encode_angle_by_sincos = bool(encode_angle_by_sincos)
+        self.code_size = code_size + (1 if self.encode_angle_by_sincos else 0)
+
+    @staticmethod
+    def _centre_scale(anchors):
+        """(.., 3): what the three centre offsets are measured in"""
+        diagonal = torch.sqrt(anchors[..., 3:4] ** 2 + anchors[..., 4:5] ** 2)
+        return torch.cat([diagonal, diagonal, anchors[..., 5:6]], dim=-1)
+
+    def encode_torch(self, boxes, anchors):
+        """boxes (N, 7 + C), anchors (N, 7 + C) -> codes (N, code_size + C).  Like the reference (:22-23) this clamps the
+        sizes of BOTH arguments to >= 1e-5 IN PLACE."""
+        for t in (anchors, boxes):
+            t[:, 3:6] = t[:, 3:6].clamp_min(1e-5)
+        centre = (boxes[..., 0:3] - anchors[..., 0:3]) / self._centre_scale(anchors)
+        size = torch.log(boxes[..., 3:6] / anchors[..., 3:6])
+        rg, ra = boxes[..., 6:7], anchors[..., 6:7]
+        if self.encode_angle_by_sincos:
+            angle = torch.cat([torch.cos(rg) - torch.cos(ra), torch.sin(rg) - torch.sin(ra)], dim=-1)
+        else:
+            angle = rg - ra
+        return torch.cat([centre, size, angle, boxes[..., 7:] - anchors[..., 7:]], dim=-1)
+
+    def decode_torch(self, box_encodings, anchors):
+        """codes (.., code_size + C), anchors (.., 7 + C) of the same leading shape -> boxes (.., 7 + C)."""
+        centre = box_encodings[..., 0:3] * self._centre_scale(anchors) + anchors[..., 0:3]
+        size = torch.exp(box_encodings[..., 3:6]) * anchors[..., 3:6]
+        ra = anchors[..., 6:7]
+        if self.encode_angle_by_sincos:
+            heading = torch.atan2(box_encodings[..., 7:8] + torch.sin(ra), box_encodings[..., 6:7] + torch.cos(ra))
+            extra = box_encodings[..., 8:]
+        else:
+            heading = box_encodings[..., 6:7] + ra
+            extra = box_encodings[..., 7:]
+        return torch.cat([centre, size, heading, extra + anchors[..., 7:]], dim=-1)

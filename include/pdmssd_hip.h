@@ -628,6 +628,44 @@ int pdm_augment_scene_fill(void *stream, int B, int C, const float *raw, const i
                            const float *point_cloud_range, const float *extra_width, long long capacity, int *out_counts,
                            int *overflow, float *out_rows, void *workspace, size_t workspace_bytes);
 
+/* ---- second-stage training: proposal targets and rcnn losses (csrc/roi_targets.hip) -------------
+ * pdm_proposal_targets: ProposalTargetLayer.forward + RoIHeadTemplate.assign_targets of the reference
+ * (roi_heads/target_assigner/proposal_target_layer.py:13-228, roi_head_template.py:104-134) for the whole batch: per
+ * sample the trailing zero-sum ground-truth rows are dropped (no row left: one all-zero box), every RoI gets its best 3-D
+ * IoU and the ground truth that gives it (by_class: among the ground truth of the RoI's own label only; ties to the
+ * lowest index), the RoIs split into fg / hard bg / easy bg, S = ROI_PER_IMAGE of them are drawn (fg first, then hard bg,
+ * then easy bg) and the targets of the drawn RoIs are formed.  rois (B, R, 7), roi_scores (B, R), roi_labels (B, R)
+ * int64, gt_boxes (B, M, 8) [box7, class].  fg_per_image = int(round(FG_RATIO * S)) and hard_bg_ratio (a double, used
+ * as int(n_bg * ratio)) come from the host; the four thresholds are the configuration's doubles, compared as fp32 (the
+ * 'roi_iou' ramp divides by fp32(CLS_FG_THRESH - CLS_BG_THRESH), the difference formed in double).  score_type 0 ('cls'): cls_labels (B, S) int64 in {1, 0, -1 = ignore};
+ * 1 ('roi_iou'): cls_labels (B, S) float.  state: 2 int32 [step, error flag]; the step is advanced by the call, the
+ * flag is OR-ed with 1 when a sample has neither fg nor bg (NaN overlaps; its slots then hold RoI 0).  Outputs, all
+ * written in full: out_rois (B, S, 7), out_labels (B, S) int64, out_scores (B, S), out_iou (B, S), out_gt_src (B, S, 8),
+ * out_gt_canon (B, S, 8) the ground truth in the RoI's frame with the heading folded into [-pi/2, pi/2],
+ * reg_valid_mask (B, S) int64, sampled_inds (B, S) and gt_assignment (B, S) int32.  Limits: R <= 1024, M <= 256
+ * (PDM_E_TOOLARGE), B <= 65535.  The draws are build-defined functions of (seed, step, sample, purpose, slot) written
+ * down in roi_targets.hip.  Two launches, no workspace, no atomics on floats: a captured graph replays the same bits.
+ *
+ * pdm_rcnn_loss: get_box_cls_layer_loss (BinaryCrossEntropy) + get_box_reg_layer_loss (smooth-l1 with
+ * CORNER_LOSS_REGULARIZATION) of roi_head_template.py:136-218 and their gradients over n = B S rows.  rcnn_cls (n),
+ * rcnn_reg (n, 7), rois (n, 7), gt_of_rois / gt_of_rois_src (n, 8), reg_valid_mask (n) int64, cls_labels (n) int64
+ * (labels_float 0) or float (1); code_weights: 7 floats on the HOST.  dcls (n) = d L_cls / d rcnn_cls, dreg (n, 7) =
+ * d L_reg / d rcnn_reg, dcorner (n, 7) = d L_corner / d rcnn_reg, every row written.  loss_cls, loss_reg, loss_corner, fg_count: one float each (four separate
+ * buffers), the losses already multiplied by their weights; use_corner 0 leaves L_corner 0.  workspace >=
+ * pdm_rcnn_loss_workspace_bytes(n).  n <= 262144.  Two launches, fixed-order sums: bit-reproducible. */
+int pdm_proposal_targets(void *stream, int B, int R, int M, int S, const float *rois, const float *roi_scores,
+                         const long long *roi_labels, const float *gt_boxes, int by_class, int fg_per_image,
+                         double hard_bg_ratio, double reg_fg_thresh, double cls_fg_thresh, double cls_bg_thresh,
+                         double cls_bg_thresh_lo, int score_type, unsigned seed, int *state, float *out_rois,
+                         long long *out_labels, float *out_scores, float *out_iou, float *out_gt_src, float *out_gt_canon,
+                         long long *reg_valid_mask, void *cls_labels, int *sampled_inds, int *gt_assignment);
+size_t pdm_rcnn_loss_workspace_bytes(long long n);
+int pdm_rcnn_loss(void *stream, long long n, const float *rcnn_cls, const float *rcnn_reg, const float *rois,
+                  const float *gt_of_rois, const float *gt_of_rois_src, const long long *reg_valid_mask,
+                  const void *cls_labels, int labels_float, const float *code_weights, float beta, float cls_weight,
+                  float reg_weight, float corner_weight, int use_corner, float *dcls, float *dreg, float *dcorner,
+                  float *loss_cls, float *loss_reg, float *loss_corner, float *fg_count, void *workspace, size_t workspace_bytes);
+
 /* ---- KITTI object evaluation (csrc/kitti_eval.hip) ---------------------------------------------
  * From the padded detections of pdm_post_process to the counts behind KITTI's AP, restating
  * pcdet/datasets/kitti/kitti_dataset.py:277-330, pcdet/utils/box_utils.py:203-288, pcdet/utils/calibration_kitti.py:65-84 and

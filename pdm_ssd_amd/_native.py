@@ -61,6 +61,8 @@ _SIGNATURES = {
     "pdm_roipoint_pool3d_canonical": [_i, _i, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp],
     "pdm_roiaware_pool3d_forward": [_i] * 7 + [_vp, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp],
     "pdm_roiaware_pool3d_backward": [_i] * 7 + [_vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "pdm_proposal_targets": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i] + [ctypes.c_double] * 5 + [_i, ctypes.c_uint] + [_vp] * 11,
+    "pdm_rcnn_loss": [ctypes.c_longlong] + [_vp] * 7 + [_i, _vp, _f, _f, _f, _f, _i] + [_vp] * 7 + [_vp, ctypes.c_size_t],
     "pdm_post_process": [_i, _i, _i, ctypes.c_longlong, _vp, _i, _vp, _i, _vp, _vp, _f, _i, _i, _f, _i, _i, _i, _vp, _i, _vp,
                          _vp, ctypes.c_size_t] + [_vp] * 7,
     "pdm_bev_depthwise3x3": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i],
@@ -191,7 +193,7 @@ _SIGNATURES = {
 EXPORTS = ["pdm_abi_version", "pdm_last_error", "pdm_ball_query_grid_workspace_bytes",
            "pdm_three_nn_grid_workspace_bytes", "pdm_furthest_point_sampling_ws_bytes",
            "pdm_fps_max_coresident_workgroups",
-           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_roiaware_pool3d_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_kitti_eval_workspace_bytes", "pdm_kitti_data_fov_workspace_bytes",
+           "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_roiaware_pool3d_workspace_bytes", "pdm_rcnn_loss_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_kitti_eval_workspace_bytes", "pdm_kitti_data_fov_workspace_bytes",
            "pdm_kitti_data_boxes_workspace_bytes", "pdm_sa_pack_workspace_bytes",
            "pdm_sa_pack_rows", "pdm_rows_mlp_x3_stream_bytes", "pdm_point_head_loss_workspace_bytes", "pdm_heatmap_focal_loss_workspace_bytes", "pdm_three_interpolate_grad_ws_bytes",
            "pdm_group_points_grad_ws_bytes", "pdm_group_concat_cl_grad_ws_bytes", "pdm_bn_parts", "pdm_bn_pool_parts",
@@ -244,6 +246,8 @@ def lib():
         l.pdm_nms_workspace_bytes.argtypes = [_i]
         l.pdm_roiaware_pool3d_workspace_bytes.restype = ctypes.c_size_t
         l.pdm_roiaware_pool3d_workspace_bytes.argtypes = [_i, _i, _i, _i]
+        l.pdm_rcnn_loss_workspace_bytes.restype = ctypes.c_size_t
+        l.pdm_rcnn_loss_workspace_bytes.argtypes = [ctypes.c_longlong]
         l.pdm_post_process_workspace_bytes.restype = ctypes.c_size_t
         l.pdm_post_process_workspace_bytes.argtypes = [_i, _i, _i]
         l.pdm_augment_workspace_bytes.restype = ctypes.c_size_t

@@ -16,10 +16,10 @@
 //
 // Draws (the reference's numpy global RNG cannot be replayed; these are build-defined, as N1's):
 //   fmix32 = the murmur3 finaliser;  u24(k) = (k >> 8) * 2^-24;  uniform(lo, hi, k) = lo + u24(k) * (hi - lo) in fp32
-//   scene key  K(s, b) = fmix32(fmix32(seed ^ step * 0x85EBCA6B) ^ b * 0x9E3779B1 ^ s * 0x7F4A7C15), step = state[0]
+//   scene key  K(s, b) = draw_key (draws.h) = fmix32(fmix32(seed ^ step * 0x85EBCA6B) ^ b * 0x9E3779B1 ^ s * 0x7F4A7C15), step = state[0]
 //     flip bit x = K(1, b) & 1, flip bit y = K(2, b) & 1, angle = uniform(rot, K(3, b)), scale = uniform(scale, K(4, b))
-//   class permutation of epoch e for group g over [0, n): a 4-round balanced Feistel network on 2w bits (2^(2w) >= n,
-//     w >= 1) keyed by kp = fmix32(fmix32(seed ^ 0x5BD1E995 ^ g * 0x9E3779B1) + e * 0x85EBCA6B), round r:
+//   class permutation of epoch e for group g over [0, n): feistel_perm (draws.h), a 4-round balanced Feistel network on 2w bits
+//     (2^(2w) >= n, w >= 1) keyed by kp = fmix32(fmix32(seed ^ 0x5BD1E995 ^ g * 0x9E3779B1) + e * 0x85EBCA6B), round r:
 //     (L, R) -> (R, L ^ (fmix32(kp ^ R * 0x9E3779B1 ^ (r + 1) * 0x7F4A7C15) & (2^w - 1))), cycle-walked into [0, n).
 //   pointer rule (sample_with_fixed_number): per group, the scenes in order; num = SAMPLE_NUM (minus the scene's boxes
 //     of the class with LIMIT_WHOLE_SCENE; skipped when <= 0); if pointer >= n: epoch += 1, pointer = 0; the slice is
@@ -36,6 +36,7 @@
 // Every output entry is written by a kernel (no memset, no atomics): the results are deterministic and a captured
 // graph replays them exactly.
 #include "box_geometry.h"
+#include "draws.h"
 
 namespace pdm {
 
@@ -62,31 +63,10 @@ struct AGWorld {          // the per-scene transform: ops = up to 4 nibbles (1 f
     float extra[3];
 };
 
-__device__ __forceinline__ unsigned ag_scene_key(unsigned seed, unsigned step, unsigned b, unsigned s) {
-    return fmix32(fmix32(seed ^ step * 0x85EBCA6Bu) ^ b * 0x9E3779B1u ^ s * 0x7F4A7C15u);
-}
 __device__ __forceinline__ float ag_uniform(float lo, float hi, unsigned k) {
     const float u = (float)(k >> 8) * 0x1p-24f;
     return __fadd_rn(lo, __fmul_rn(u, __fsub_rn(hi, lo)));
 }
-__device__ __forceinline__ unsigned ag_perm(unsigned i, unsigned n, unsigned kp) {
-    int w = 1;
-    while ((1ull << (2 * w)) < (unsigned long long)n) ++w;
-    const unsigned mask = (1u << w) - 1u;
-    unsigned x = i;
-    do {
-        unsigned L = x >> w, R = x & mask;
-        for (unsigned r = 0; r < 4; ++r) {
-            const unsigned f = fmix32(kp ^ R * 0x9E3779B1u ^ (r + 1u) * 0x7F4A7C15u) & mask;
-            const unsigned t = L ^ f;
-            L = R;
-            R = t;
-        }
-        x = (L << w) | R;
-    } while (x >= n);
-    return x;
-}
-
 // (x, y, z) through the scene's transform list (points: h == nullptr, dims == nullptr)
 __device__ __forceinline__ void ag_world(unsigned ops, int flip, float c, float s, float angle, float scale, float &x,
                                          float &y, float &z, float *h, float *dims) {
@@ -126,11 +106,11 @@ __global__ __launch_bounds__(1024) void ag_draw_kernel(int B, AGGroups g, int li
     const unsigned step = (unsigned)state[0];
     for (int b = tid; b < B; b += blockDim.x) {
         int f = 0;
-        if (flip_axes & 1) f |= (int)(ag_scene_key(seed, step, b, 1) & 1u);
-        if (flip_axes & 2) f |= (int)(ag_scene_key(seed, step, b, 2) & 1u) << 1;
+        if (flip_axes & 1) f |= (int)(draw_key(seed, step, b, 1) & 1u);
+        if (flip_axes & 2) f |= (int)(draw_key(seed, step, b, 2) & 1u) << 1;
         flip[b] = f;
-        angle[b] = use_rot ? ag_uniform(rlo, rhi, ag_scene_key(seed, step, b, 3)) : 0.f;
-        scale[b] = use_scale ? ag_uniform(slo, shi, ag_scene_key(seed, step, b, 4)) : 1.f;
+        angle[b] = use_rot ? ag_uniform(rlo, rhi, draw_key(seed, step, b, 3)) : 0.f;
+        scale[b] = use_scale ? ag_uniform(slo, shi, draw_key(seed, step, b, 4)) : 1.f;
     }
     if (tid < g.n) {   // the pointer rule: one lane per group walks the scenes in order
         int epoch = state[1 + 2 * tid], ptr = state[2 + 2 * tid];
@@ -163,7 +143,7 @@ __global__ __launch_bounds__(1024) void ag_draw_kernel(int B, AGGroups g, int li
             const int *w = walk + ((size_t)b * AG_MAXG + t) * 3;
             if (j < w[2]) {
                 const unsigned kp = fmix32(fmix32(seed ^ 0x5BD1E995u ^ (unsigned)t * 0x9E3779B1u) + (unsigned)w[0] * 0x85EBCA6Bu);
-                out = g.first[t] + (int)ag_perm((unsigned)(w[1] + j), (unsigned)g.len[t], kp);
+                out = g.first[t] + (int)feistel_perm((unsigned)(w[1] + j), (unsigned)g.len[t], kp);
             }
         }
         sampled[e] = out;

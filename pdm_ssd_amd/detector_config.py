@@ -1,6 +1,7 @@
 """The PDM-SSD model configuration the benchmark and tests build (key names as an OpenPCDet YAML would hold them; the
 reference's own YAML files are git-ignored and absent).  Backbone = upstream pointrcnn.yaml's
 PointNet2MSG; point head = its PointHeadBox settings; neck / heat-map head = this repo's spec."""
+import copy
 from types import SimpleNamespace
 
 from . import synthetic
@@ -34,8 +35,8 @@ PDM_SSD_CFG = {
 
 # PointRCNN: the upstream project's published settings (its tools/cfgs/kitti_models/pointrcnn.yaml) restated as a dict — the
 # snapshot this repository was modelled on holds no YAML.  First stage = the backbone and point head above;
-# the second stage runs in eval mode only, so of TARGET_CONFIG only the box coder is read (the proposal-target sampler's
-# and the rcnn losses' settings are left out with the code that would read them).
+# a second stage built from this dict runs in eval mode only: of TARGET_CONFIG it holds the box coder alone, and a RoI head
+# without the proposal-target sampler's settings has no training half (POINT_RCNN_TRAIN_CFG below adds them).
 POINT_RCNN_CFG = {
     'NAME': 'PointRCNN',
     'BACKBONE_3D': dict(POINTRCNN_MSG_CFG),
@@ -55,6 +56,16 @@ POINT_RCNN_CFG = {
                                        'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
 }
 
+# POINT_RCNN_CFG plus the upstream file's proposal-target sampler (TARGET_CONFIG) and rcnn loss settings (LOSS_CONFIG),
+# restated: a RoI head built from this dict has the training half (ProposalTargetLayer, assign_targets, get_loss).
+POINT_RCNN_TRAIN_CFG = copy.deepcopy(POINT_RCNN_CFG)
+POINT_RCNN_TRAIN_CFG['ROI_HEAD']['TARGET_CONFIG'].update(
+    ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE='cls', CLS_FG_THRESH=0.6, CLS_BG_THRESH=0.45,
+    CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
+POINT_RCNN_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
+    'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
+    'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0, 'code_weights': [1.0] * 7}}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -70,9 +81,8 @@ def build_pdm_ssd(model_cfg=None, num_point_features=4):
 
 
 def build_point_rcnn(model_cfg=None, num_point_features=4):
-    """PointRCNN (eval mode: the second stage's training half is not built) from POINT_RCNN_CFG or a dict like it."""
-    import copy
-
+    """PointRCNN from POINT_RCNN_CFG (eval mode only), POINT_RCNN_TRAIN_CFG (with the second stage's training half) or a
+    dict like them."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(POINT_RCNN_CFG if model_cfg is None else model_cfg))   # (the SA constructors edit MLPS)
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))

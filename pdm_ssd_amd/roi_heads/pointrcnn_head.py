@@ -6,8 +6,9 @@ Per RoI: 512 pooled points [x, y, z in the RoI's frame, point score, depth, C fe
 lifted by `xyz_up_layer` and merged with the C features by `merge_down_layer` -> PointNet++ set-abstraction levels
 (`SA_modules`, the last one grouping all points) -> `cls_layers` and `reg_layers` on the one remaining feature vector.
 
-Training is not built: in training mode forward raises NotImplementedError (ProposalTargetLayer and the rcnn losses do
-not exist here).
+Training mode (ref :140-179): proposals with NMS_CONFIG.TRAIN -> assign_targets (pdm_proposal_targets) -> the sampled
+rois replace the proposals -> pooling under no_grad -> rcnn_cls / rcnn_reg into forward_ret_dict for get_loss().  A head
+whose TARGET_CONFIG holds no sampler settings (POINT_RCNN_CFG) has no training half and raises NotImplementedError there.
 """
 import torch
 import torch.nn as nn
@@ -33,7 +34,7 @@ def _pointwise_stack(widths, use_bn):
 
 class PointRCNNHead(RoIHeadTemplate):
     def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
-        super().__init__(num_class=num_class, model_cfg=model_cfg)
+        super().__init__(num_class=num_class, model_cfg=model_cfg, **kwargs)
         cfg = self.model_cfg
         use_bn = cfg.USE_BN
         self.num_prefix_channels = 3 + 2          # canonical xyz, first-stage score, normalised depth
@@ -111,13 +112,26 @@ class PointRCNNHead(RoIHeadTemplate):
     def forward(self, batch_dict):
         """Eval mode (behaviour of ref :132-179): proposals (unless rois are given) -> pooled canonical points -> RoI
         features -> rcnn_cls (R, num_class), rcnn_reg (R, code_size) -> batch_cls_preds / batch_box_preds (refined boxes)
-        with cls_preds_normalized = False.  Training mode raises NotImplementedError."""
+        with cls_preds_normalized = False.
+        Training mode: proposals with NMS_CONFIG.TRAIN, the sampled rois and roi_labels of assign_targets replace them in
+        batch_dict, and forward_ret_dict = the targets + rcnn_cls / rcnn_reg (fp32) for get_loss(); needs gt_boxes.  A head
+        without the sampler's settings raises NotImplementedError."""
+        if self.training and not self.has_training_half:
+            self._require_training_half('PointRCNNHead')
+        self.proposal_layer(batch_dict, nms_config=self.model_cfg.NMS_CONFIG['TRAIN' if self.training else 'TEST'])
+        targets_dict = None
         if self.training:
-            raise NotImplementedError('PointRCNNHead training: ProposalTargetLayer and the rcnn losses are not built')
-        self.proposal_layer(batch_dict, nms_config=self.model_cfg.NMS_CONFIG['TEST'])
+            targets_dict = self.assign_targets(batch_dict)
+            batch_dict['rois'] = targets_dict['rois']
+            batch_dict['roi_labels'] = targets_dict['roi_labels']
         shared = self._roi_features(self.roipool3d_gpu(batch_dict))
         rcnn_cls = self.cls_layers(shared).squeeze(2)
         rcnn_reg = self.reg_layers(shared).squeeze(2)
+        if self.training:
+            targets_dict['rcnn_cls'] = rcnn_cls.float()
+            targets_dict['rcnn_reg'] = rcnn_reg.float()
+            self.forward_ret_dict = targets_dict
+            return batch_dict
         cls, boxes = self.generate_predicted_boxes(batch_size=batch_dict['batch_size'], rois=batch_dict['rois'],
                                                    cls_preds=rcnn_cls, box_preds=rcnn_reg)
         batch_dict.update(rcnn_cls=rcnn_cls, rcnn_reg=rcnn_reg, batch_cls_preds=cls, batch_box_preds=boxes,

@@ -2,12 +2,15 @@
 
 SigmoidFocalClassificationLoss, WeightedSmoothL1Loss: behaviour of /root/reference/pcdet/utils/loss_utils.py:10-74,
 76-141 (point head).  FocalLossCenterNet: :266-345 (heat-map head; the CornerNet penalty-reduced focal loss).
+get_corner_loss_lidar: :211-234 (the RoI heads' corner regularisation).
 Code weights follow the device of the input instead of being moved to the GPU at construction.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import box_utils
 
 
 class SigmoidFocalClassificationLoss(nn.Module):
@@ -86,3 +89,16 @@ def neg_loss_cornernet(pred, gt, mask=None):
 class FocalLossCenterNet(nn.Module):
     def forward(self, out, target, mask=None):
         return neg_loss_cornernet(out, target, mask=mask)
+
+
+def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
+    """pred_bbox3d, gt_bbox3d (N, 7) -> (N): per box the mean over its 8 corners of smooth_l1(distance, beta = 1), the
+    distance of a predicted corner being the lesser of those to the ground truth's corner and to the corner of the
+    ground truth turned by pi (a box and its half-turn are the same solid)."""
+    assert pred_bbox3d.shape[0] == gt_bbox3d.shape[0]
+    pred = box_utils.boxes_to_corners_3d(pred_bbox3d)
+    turned = gt_bbox3d.clone()
+    turned[:, 6] += np.pi
+    dist = torch.min(torch.norm(pred - box_utils.boxes_to_corners_3d(gt_bbox3d), dim=2),
+                     torch.norm(pred - box_utils.boxes_to_corners_3d(turned), dim=2))
+    return WeightedSmoothL1Loss.smooth_l1_loss(dist, beta=1.0).mean(dim=1)

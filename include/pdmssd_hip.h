@@ -275,6 +275,44 @@ int pdm_heatmap_focal_loss(void *stream, int B, int C, int H, int W, const void 
                            long long sh, long long sw, const float *heatmap, float weight, float *dlogits, float *out,
                            void *workspace, size_t workspace_bytes);
 
+/* ---- CenterHead (csrc/center_head.hip): targets, heat-map box decode and the L1 regression loss of
+ * the reference's pcdet/models/dense_heads/center_head.py, model_utils/centernet_utils.py:155-241 and
+ * utils/loss_utils.py:347-419, one launch chain per head for the whole batch.  Nothing synchronises, no float atomics on
+ * results or gradients, safe to capture in a graph after one warm-up call.
+ *
+ * pdm_center_targets: gt_boxes (B, M, cols) fp32, cols = 7 + E + 1, global class (1-based, 0 = padding) last, NOT modified.
+ *   local_of: HOST array of num_global + 1 ints, the head's 1-based class of each global class or 0.  A sample's boxes of the
+ *   head's classes are compacted in their order; slot k < num_max_objs gets inds = cy * W + cx, mask = 1,
+ *   target_boxes = [frac x, frac y, z, log dx, log dy, log dz, cos r, sin r, extras], target_boxes_src = the box with the
+ *   head's class; a slot whose dx <= 0 or dy <= 0 stays used and zero (mask 0).  heatmap (B, C, H, W) = the gaussians of
+ *   pdm_heatmap_targets (the same device code) with the window never clipped short of the map.  Every element is written.
+ * pdm_center_decode: maps = HOST array of 6 device pointers [hm logits (C), center (2), center_z (1), dim (3), rot (2: cos,
+ *   sin), vel (2) | NULL], bf16 = HOST array of 6 flags, strides = HOST array of 6 x 4 element strides (b, c, y, x).  Per
+ *   sample the K <= H * W (K <= 16384) highest sigmoid(hm) over (class, y, x), ties by lower flat index (rank_select.h); per
+ *   rank x = ((cx + center_x) * stride) * vx + x0 (each step one fp32 rounding), likewise y, z = center_z, dims = exp(dim),
+ *   angle = atan2(sin, cos); kept iff x, y, z within limit_range (HOST [lo3, hi3], inclusive) and score > score_thresh;
+ *   survivors compacted in rank order: boxes (B, K, 7 + E), scores (B, K), labels (B, K) int64 = global_of[class] + 1
+ *   (global_of: HOST array of C ints), count (B) int32, padding rows zero.
+ * pdm_center_reg_loss: chans = HOST array of D = 8 + E device pointers, the (B, H, W) plane of each regression channel in
+ *   code order, bf16 / strides (D x 3: b, y, x) HOST arrays; inds, mask (B, num_max_objs) int64; target (B, num_max_objs, D);
+ *   code_weights HOST array of D floats.  loss_per_code (D) = sum |pred m - gt m| / max(num, 1), m = mask * !isnan(target),
+ *   num = sum(mask); out = [loc_loss = loc_weight * sum(loss_per_code * code_weights), max(num, 1), num]; grad (B, D, H, W) =
+ *   d loc_loss / d map, slots of one cell added in slot order by the one thread that owns the cell, other cells exact zeros.
+ *   workspace >= pdm_center_reg_loss_workspace_bytes(B, D), 8-byte aligned.  num_max_objs <= 8192, D <= 16. */
+int pdm_center_targets(void *stream, int B, int M, int cols, int C, int H, int W, const float *gt_boxes, int num_global,
+                       const int *local_of, float x0, float y0, float vx, float vy, float stride, int num_max_objs,
+                       double min_overlap, int min_radius, float *heatmap, float *target_boxes, long long *inds,
+                       long long *mask, float *target_boxes_src);
+int pdm_center_decode(void *stream, int B, int C, int H, int W, int K, const void *const *maps, const int *bf16,
+                      const long long *strides, float score_thresh, const float *limit_range, float x0, float y0,
+                      float vx, float vy, float stride, const int *global_of, float *boxes, float *scores,
+                      long long *labels, int *count);
+size_t pdm_center_reg_loss_workspace_bytes(int B, int D);
+int pdm_center_reg_loss(void *stream, int B, int num_max_objs, int D, int H, int W, const void *const *chans, const int *bf16,
+                        const long long *strides, const long long *inds, const long long *mask, const float *target,
+                        const float *code_weights, float loc_weight, float *loss_per_code, float *out, float *grad,
+                        void *workspace, size_t workspace_bytes);
+
 /* OPT-IN: the same three-layer per-row MLP with fp32 EMULATED on the bf16 matrix pipe — every fp32 operand split into three
  * bf16 pieces (8 + 8 + 8 significand bits), a product formed from the six leading partial products on
  * v_mfma_f32_16x16x32_bf16 with fp32 accumulation (3/8 of the fp32-MFMA pipe time; dropped terms <= 2^-24 |a b|).

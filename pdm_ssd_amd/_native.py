@@ -121,6 +121,9 @@ _SIGNATURES = {
     "pdm_heatmap_targets": [_i, _i, _i, _i, _i, _vp, _f, _f, _f, _f, _f, ctypes.c_double, _i, _i, _vp],
     "pdm_heatmap_focal_loss": [_i, _i, _i, _i, _vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _f, _vp, _vp,
                                _vp, ctypes.c_size_t],
+    "pdm_center_targets": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _f, _f, _f, _f, _f, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp],
+    "pdm_center_decode": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    "pdm_center_reg_loss": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, ctypes.c_size_t],
     "pdm_rows_mlp_x3": [_i, _i, _vp, _i, _vp, _vp, ctypes.c_size_t, _vp, _i, _vp, _i, _i],
     "pdm_rows_mlp_fused_pair": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i],
     "pdm_fp_head_fused": [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
@@ -195,7 +198,7 @@ EXPORTS = ["pdm_abi_version", "pdm_last_error", "pdm_ball_query_grid_workspace_b
            "pdm_fps_max_coresident_workgroups",
            "pdm_gather_bev_workspace_bytes", "pdm_nms_workspace_bytes", "pdm_roiaware_pool3d_workspace_bytes", "pdm_rcnn_loss_workspace_bytes", "pdm_post_process_workspace_bytes", "pdm_augment_workspace_bytes", "pdm_kitti_eval_workspace_bytes", "pdm_kitti_data_fov_workspace_bytes",
            "pdm_kitti_data_boxes_workspace_bytes", "pdm_sa_pack_workspace_bytes",
-           "pdm_sa_pack_rows", "pdm_rows_mlp_x3_stream_bytes", "pdm_point_head_loss_workspace_bytes", "pdm_heatmap_focal_loss_workspace_bytes", "pdm_three_interpolate_grad_ws_bytes",
+           "pdm_sa_pack_rows", "pdm_rows_mlp_x3_stream_bytes", "pdm_point_head_loss_workspace_bytes", "pdm_heatmap_focal_loss_workspace_bytes", "pdm_center_reg_loss_workspace_bytes", "pdm_three_interpolate_grad_ws_bytes",
            "pdm_group_points_grad_ws_bytes", "pdm_group_concat_cl_grad_ws_bytes", "pdm_bn_parts", "pdm_bn_pool_parts",
            "pdm_tg_stats_parts", "pdm_tg_dy_stats_parts", "pdm_tg_wgrad_ws_bytes", "pdm_tg_colsum_ws_floats"] + list(_SIGNATURES)
 
@@ -239,6 +242,8 @@ def lib():
         l.pdm_point_head_loss_workspace_bytes.argtypes = [ctypes.c_longlong]
         l.pdm_heatmap_focal_loss_workspace_bytes.restype = ctypes.c_size_t
         l.pdm_heatmap_focal_loss_workspace_bytes.argtypes = [ctypes.c_longlong]
+        l.pdm_center_reg_loss_workspace_bytes.restype = ctypes.c_size_t
+        l.pdm_center_reg_loss_workspace_bytes.argtypes = [_i, _i]
         l.pdm_rows_mlp_x3_stream_bytes.restype = ctypes.c_size_t
         l.pdm_rows_mlp_x3_stream_bytes.argtypes = [_i, _vp]
         l.pdm_sa_pack_rows.restype = ctypes.c_size_t

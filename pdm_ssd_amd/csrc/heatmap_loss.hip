@@ -16,27 +16,11 @@
 // order like the values).  Launch 2 forms per-workgroup partial sums of the two terms and the peak count, and d S / d x per
 // element; launch 3 (one workgroup) folds the partials in double in a fixed order (bit-reproducible), leaving L and the factor
 // - weight / max(#peaks, 1) that backward() multiplies the stored d S / d x by.
-#include "common.h"
+#include "heatmap_draw.h"
 
 namespace pdm {
 
 constexpr int HM_T = 256;
-
-// centernet_utils.gaussian_radius in torch's fp32 evaluation order: the python scalars (1 - o, 1 + o, -2 o, o - 1, 4 (4 o)) are
-// formed in double and enter the tensor arithmetic as fp32 factors
-__device__ __forceinline__ float hm_gaussian_radius(float height, float width, double o) {
-    const float k1m = (float)(1.0 - o), k1p = (float)(1.0 + o), kn2 = (float)(-2.0 * o), km1 = (float)(o - 1.0), k16 = (float)(4.0 * (4.0 * o));
-    const float b1 = height + width;
-    const float c1 = __fmul_rn(__fmul_rn(__fmul_rn(width, height), k1m), __fdiv_rn(1.0f, k1p));   // (tensor / python scalar = tensor * (1 / scalar) in torch's kernel)
-    const float r1 = __fmul_rn(__fadd_rn(b1, __fsqrt_rn(__fsub_rn(__fmul_rn(b1, b1), __fmul_rn(4.0f, c1)))), 0.5f);
-    const float b2 = __fmul_rn(2.0f, height + width);
-    const float c2 = __fmul_rn(__fmul_rn(k1m, width), height);
-    const float r2 = __fmul_rn(__fadd_rn(b2, __fsqrt_rn(__fsub_rn(__fmul_rn(b2, b2), __fmul_rn(16.0f, c2)))), 0.5f);
-    const float b3 = __fmul_rn(kn2, height + width);
-    const float c3 = __fmul_rn(__fmul_rn(km1, width), height);
-    const float r3 = __fmul_rn(__fadd_rn(b3, __fsqrt_rn(__fsub_rn(__fmul_rn(b3, b3), __fmul_rn(k16, c3)))), 0.5f);
-    return fminf(fminf(r1, r2), r3);
-}
 
 struct HmTargetArgs {
     int B, M, C, H, W;
@@ -47,38 +31,12 @@ struct HmTargetArgs {
     float *heatmap;                 // (B, C, H, W), zero on entry
 };
 
-// one workgroup per box; thread = cell of the (2 max_radius + 1)^2 window
+// one workgroup per box; the threads share the cells of its window (heatmap_draw.h)
 __global__ __launch_bounds__(HM_T) void hm_target_kernel(HmTargetArgs a) {
     const int bm = blockIdx.x, b = bm / a.M;
     const float *g = a.gt_boxes + (size_t)bm * 8;
-    const float cls = g[7];
-    // (division of a tensor by a python scalar is a multiplication by the scalar's fp32 reciprocal in torch's kernel: the same here,
-    //  so that the integer cell and radius of a box come out the same)
-    const float ivx = __fdiv_rn(1.0f, a.vx), ivy = __fdiv_rn(1.0f, a.vy), is = __fdiv_rn(1.0f, a.stride);
-    const float dxc = __fmul_rn(__fmul_rn(g[3], ivx), is), dyc = __fmul_rn(__fmul_rn(g[4], ivy), is);
-    if (!(dxc > 0.0f) || !(dyc > 0.0f) || !(cls >= 1.0f)) return;   // padding / degenerate box (uniform over the workgroup)
-    const int c = (int)cls - 1;
-    if (c >= a.C) return;
-    const float cx = fminf(fmaxf(__fmul_rn(__fmul_rn(g[0] - a.x0, ivx), is), 0.0f), (float)a.W - 0.5f);
-    const float cy = fminf(fmaxf(__fmul_rn(__fmul_rn(g[1] - a.y0, ivy), is), 0.0f), (float)a.H - 0.5f);
-    const int ix = (int)cx, iy = (int)cy;
-    int r = (int)hm_gaussian_radius(dxc, dyc, a.min_overlap);     // (height, width) = (dx, dy) cells as the head passes them
-    if (r < a.min_radius) r = a.min_radius;
-    const float rt = (float)r;
-    const int rw = r < a.max_radius ? r : a.max_radius;          // the window is clipped at max_radius, sigma keeps the true radius
-    const float sigma = __fmul_rn(__fadd_rn(__fmul_rn(2.0f, rt), 1.0f), __fdiv_rn(1.0f, 6.0f));
-    const float den = __fmul_rn(__fmul_rn(2.0f, sigma), sigma);
-    const int K = 2 * a.max_radius + 1;
-    int *map = reinterpret_cast<int *>(a.heatmap + ((size_t)b * a.C + c) * a.H * a.W);
-    for (int e = threadIdx.x; e < K * K; e += HM_T) {
-        const int dy = e / K - a.max_radius, dx = e % K - a.max_radius;
-        if (abs(dx) > rw || abs(dy) > rw) continue;
-        const int x = ix + dx, y = iy + dy;
-        if (x < 0 || x >= a.W || y < 0 || y >= a.H) continue;
-        const float v = expf(-__fdiv_rn((float)(dx * dx + dy * dy), den));
-        if (v < 1.1920928955078125e-07f) continue;               // h[h < eps * h.max()] = 0 (the window's maximum is 1)
-        atomicMax(map + (size_t)y * a.W + x, __float_as_int(v));
-    }
+    const HmGrid grid{a.C, a.H, a.W, a.x0, a.y0, a.vx, a.vy, a.stride, a.min_overlap, a.min_radius, a.max_radius};
+    hm_draw_box<HM_T>(grid, g[0], g[1], g[3], g[4], g[7], a.heatmap + (size_t)b * a.C * a.H * a.W);
 }
 
 struct HmLossArgs {

@@ -66,6 +66,32 @@ POINT_RCNN_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
     'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
     'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0, 'code_weights': [1.0] * 7}}
 
+# CenterPoint on the PDM neck: PointNet2MSG -> PDMNeck -> CenterHead.  The head and post-processing values are the upstream
+# project's published KITTI settings (the dense head of its tools/cfgs/kitti_models/centerpoint.yaml) restated as a dict;
+# the neck's map (128 channels, 200 x 176 cells of 0.4 m) stands where that file's 2-D backbone would.
+CENTER_PDM_CFG = {
+    'NAME': 'CenterPoint',
+    'BACKBONE_3D': dict(POINTRCNN_MSG_CFG),
+    'MAP_TO_BEV': dict(PDM_SSD_CFG['MAP_TO_BEV']),
+    'DENSE_HEAD': {'NAME': 'CenterHead', 'CLASS_AGNOSTIC': False, 'CLASS_NAMES_EACH_HEAD': [['Car', 'Pedestrian', 'Cyclist']],
+                   'SHARED_CONV_CHANNEL': 64, 'USE_BIAS_BEFORE_NORM': True, 'NUM_HM_CONV': 2,
+                   'SEPARATE_HEAD_CFG': {'HEAD_ORDER': ['center', 'center_z', 'dim', 'rot'],
+                                         'HEAD_DICT': {'center': {'out_channels': 2, 'num_conv': 2},
+                                                       'center_z': {'out_channels': 1, 'num_conv': 2},
+                                                       'dim': {'out_channels': 3, 'num_conv': 2},
+                                                       'rot': {'out_channels': 2, 'num_conv': 2}}},
+                   'TARGET_ASSIGNER_CONFIG': {'FEATURE_MAP_STRIDE': 8, 'NUM_MAX_OBJS': 500, 'GAUSSIAN_OVERLAP': 0.1, 'MIN_RADIUS': 2},
+                   'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0,
+                                                    'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}},
+                   'POST_PROCESSING': {'SCORE_THRESH': 0.1, 'POST_CENTER_LIMIT_RANGE': [-75.2, -75.2, -2, 75.2, 75.2, 4],
+                                       'MAX_OBJ_PER_SAMPLE': 500,
+                                       'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.01,
+                                                      'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}}},
+    'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False, 'EVAL_METRIC': 'kitti',
+                        'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.01,
+                                       'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
+}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -85,4 +111,11 @@ def build_point_rcnn(model_cfg=None, num_point_features=4):
     dict like them."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(POINT_RCNN_CFG if model_cfg is None else model_cfg))   # (the SA constructors edit MLPS)
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))
+
+
+def build_center_pdm(model_cfg=None, num_point_features=4):
+    """CenterPoint from CENTER_PDM_CFG (or a dict like it): PointNet2MSG -> PDMNeck -> CenterHead."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(CENTER_PDM_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))

@@ -3,6 +3,7 @@ detectors/__init__.py:19-46: build_detector / build_network by NAME, model_fn_de
 from collections import namedtuple
 
 from .detector3d_template import BACKBONES_3D, MAP_TO_BEV, Detector3DTemplate
+from .centerpoint import CenterPoint
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 
@@ -10,6 +11,7 @@ __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'PDMSSD': PDMSSD,
     'PointRCNN': PointRCNN,
+    'CenterPoint': CenterPoint,
 }
 
 

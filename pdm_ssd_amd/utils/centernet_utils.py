@@ -52,3 +52,59 @@ def draw_gaussians(heatmap, cls_idx, centers_int, radius, valid, max_radius=8):
     vals = torch.where(ok, g, torch.zeros_like(g))
     heatmap.view(-1).scatter_reduce_(0, flat.reshape(-1), vals.reshape(-1), reduce="amax", include_self=True)
     return heatmap
+
+
+def _gather_feat(feat, ind):
+    """feat (B, N, D), ind (B, K) -> (B, K, D): row ind[b, k] of sample b."""
+    return feat.gather(1, ind.unsqueeze(2).expand(ind.size(0), ind.size(1), feat.size(2)))
+
+
+def _transpose_and_gather_feat(feat, ind):
+    """feat (B, D, H, W), ind (B, K) flat cells y * W + x -> (B, K, D): the channels at those cells."""
+    B, D = feat.size(0), feat.size(1)
+    return _gather_feat(feat.permute(0, 2, 3, 1).reshape(B, -1, D), ind)
+
+
+def _topk(scores, K=40):
+    """scores (B, C, H, W) -> the K best over (class, y, x) per sample in two stages, as the reference's
+    centernet_utils.py:155-170: the K best cells of every class, then the K best of those C * K.  Returns score (B, K),
+    flat cell y * W + x (B, K), class (B, K) int32, y and x (B, K) as floats.  K > H * W is torch.topk's error.
+    Equal scores fall in whatever order torch.topk leaves them; the fused operator (center_head_ops.center_decode) takes
+    the lower flat index c * H * W + y * W + x."""
+    B, C, H, W = scores.size()
+    per_class_score, per_class_cell = torch.topk(scores.flatten(2, 3), K)            # (B, C, K)
+    best_score, best = torch.topk(per_class_score.view(B, -1), K)                       # (B, K) into (C * K)
+    classes = (best // K).int()
+    cells = per_class_cell.view(B, -1).gather(1, best)
+    ys = (cells // W).float()
+    xs = (cells % W).int().float()
+    return best_score, cells, classes, ys, xs
+
+
+def decode_bbox_from_heatmap(heatmap, rot_cos, rot_sin, center, center_z, dim, point_cloud_range=None, voxel_size=None,
+                             feature_map_stride=None, vel=None, iou=None, K=100, circle_nms=False, score_thresh=None,
+                             post_center_limit_range=None):
+    """The torch formulation of the heat-map decode (the reference's centernet_utils.py:173-241): heatmap (B, C, H, W)
+    scores, the regression maps with dim already exponentiated -> a list of per-sample dicts pred_boxes (n, 7 | 9),
+    pred_scores (n), pred_labels (n) int32 (the head's 0-based class), the K best candidates that lie within
+    post_center_limit_range (inclusive) and above score_thresh (strict), in rank order.  circle_nms is unsupported, as
+    in the reference; an iou map is not part of this build."""
+    assert not circle_nms, 'circle_nms: not checked in the reference (centernet_utils.py:178-180), not supported here'
+    assert iou is None, 'an iou head is out of scope'
+    assert post_center_limit_range is not None
+    B = heatmap.size(0)
+    scores, cells, classes, ys, xs = _topk(heatmap, K=K)
+    center = _transpose_and_gather_feat(center, cells)
+    angle = torch.atan2(_transpose_and_gather_feat(rot_sin, cells), _transpose_and_gather_feat(rot_cos, cells))
+    xs = (xs.view(B, K, 1) + center[:, :, 0:1]) * feature_map_stride * voxel_size[0] + point_cloud_range[0]
+    ys = (ys.view(B, K, 1) + center[:, :, 1:2]) * feature_map_stride * voxel_size[1] + point_cloud_range[1]
+    parts = [xs, ys, _transpose_and_gather_feat(center_z, cells), _transpose_and_gather_feat(dim, cells), angle]
+    if vel is not None:
+        parts.append(_transpose_and_gather_feat(vel, cells))
+    boxes = torch.cat(parts, dim=-1)
+    limit = torch.as_tensor(post_center_limit_range, dtype=boxes.dtype, device=boxes.device)
+    keep = (boxes[..., :3] >= limit[:3]).all(2) & (boxes[..., :3] <= limit[3:]).all(2)
+    if score_thresh is not None:
+        keep &= scores > score_thresh
+    return [{'pred_boxes': boxes[b, keep[b]], 'pred_scores': scores[b, keep[b]], 'pred_labels': classes[b, keep[b]]}
+            for b in range(B)]

@@ -102,3 +102,24 @@ def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
     dist = torch.min(torch.norm(pred - box_utils.boxes_to_corners_3d(gt_bbox3d), dim=2),
                      torch.norm(pred - box_utils.boxes_to_corners_3d(turned), dim=2))
     return WeightedSmoothL1Loss.smooth_l1_loss(dist, beta=1.0).mean(dim=1)
+
+
+def _reg_loss(regr, gt_regr, mask):
+    """L1 regression loss of the centre head (the reference's loss_utils.py:347-376): regr / gt_regr (B, M, D), mask
+    (B, M) -> (D): sum over batch and slots of |regr m - gt m| / max(sum(mask), 1), m = mask * !isnan(gt) per element.
+    A NaN target element contributes zero (the reference multiplies the NaN by its zero mask, which stays NaN and
+    poisons that code's loss; the evident intent, an element left out, is implemented here and in pdm_center_reg_loss)."""
+    num = mask.float().sum()
+    m = mask.unsqueeze(2).expand_as(gt_regr).float() * (~torch.isnan(gt_regr)).float()
+    gt = torch.where(torch.isnan(gt_regr), torch.zeros_like(gt_regr), gt_regr)
+    loss = torch.abs(regr * m - gt * m)
+    return loss.sum(dim=(0, 1)) / torch.clamp_min(num, min=1.0)
+
+
+class RegLossCenterNet(nn.Module):
+    def forward(self, output, mask, ind=None, target=None):
+        """output (B, D, H, W) maps (gathered at ind (B, M) flat cells) or (B, M, D) predictions; mask (B, M);
+        target (B, M, D) -> (D) per-code loss."""
+        from .centernet_utils import _transpose_and_gather_feat
+        pred = output if ind is None else _transpose_and_gather_feat(output, ind)
+        return _reg_loss(pred, target, mask)

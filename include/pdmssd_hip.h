@@ -886,6 +886,11 @@ int pdm_tune_fp_head_tiles(int n);           /* pdm_fp_head_fused: consecutive 6
 int pdm_tune_rows_chain_dw_wg_per_cu(int n); /* the same for pdm_bev_head_fused (default 2: every workgroup resident from the start) */
 int pdm_tune_rows_chain_xcd(int on);   /* heat-map chain kernel: contiguous patch range per XCD (default) / launch order */
 int pdm_tune_fp_chain_pad_lds(int bytes); /* diagnostic: extra LDS per workgroup of the FP chain kernel (occupancy experiments) */
+int pdm_tune_fp_chain_nt(int on);      /* FP chain kernel: non-temporal output stores (default off) */
+int pdm_tune_fp_chain_mask(int m);     /* which FP shapes take the register-resident chain kernel: bits 0-1 (default 2); m < 0 only reads */
+int pdm_tune_group_nt(int on);         /* non-temporal stores of the grouped outputs (default on) */
+int pdm_tune_copy_variant(int v);      /* pdm_copy_many: -1 by size (default); bit 0 non-temporal stores, bit 1 eight loads in flight per lane, bit 2 non-temporal loads */
+int pdm_tune_copy_max_wg(int n);       /* pdm_copy_many: grid cap in workgroups per buffer (default 8192) */
 
 /* count device-to-device copies dst[k] <- src[k] (bytes[k] each; host arrays) in one launch per 48 buffers.
  * Plumbing for the stream pipeline's hand-over buffers, not a reference operator. */

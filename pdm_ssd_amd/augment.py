@@ -38,15 +38,6 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _host_ints(values):
-    n = max(len(values), 1)
-    return (ctypes.c_int * n)(*[int(v) for v in values])
-
-
-def _host_floats(values):
-    return (ctypes.c_float * len(values))(*[float(v) for v in values])
-
-
 class GTDatabase:
     """Device-resident ground-truth database: object points (P, C) fp32 relative to their box centre, offsets (N + 1)
     int64 (entry i owns rows offsets[i]:offsets[i + 1]), boxes (N, 7) fp32, class ids (N) int (0-based into
@@ -255,8 +246,8 @@ class BatchAugmentor:
         rot = self.plan['rot'] or (0.0, 0.0)
         sc = self.plan['scale'] or (1.0, 1.0)
         G = len(self.g_num)
-        _native.call("pdm_augment_draw", torch.cuda.current_stream(dev).cuda_stream, B, G, _host_ints(self.g_cls),
-                     _host_ints(self.g_num), _host_ints(self.g_len), _host_ints(self.g_first), 1 if self.limit else 0, M,
+        g_cls, g_num, g_len, g_first = (_native.host_array(ctypes.c_int, v) for v in (self.g_cls, self.g_num, self.g_len, self.g_first))
+        _native.call("pdm_augment_draw", _native.stream(dev), B, G, g_cls, g_num, g_len, g_first, 1 if self.limit else 0, M,
                      gt_boxes.data_ptr(), self.seed, self.state.data_ptr(), self.plan['flip_axes'],
                      1 if self.plan['rot'] else 0, rot[0], rot[1], 1 if self.plan['scale'] else 0, sc[0], sc[1], self.K,
                      _ptr(p['sampled']) if self.K else None, p['flip'].data_ptr(), p['angle'].data_ptr(),
@@ -273,11 +264,12 @@ class BatchAugmentor:
                'num_accepted': torch.empty((B,), dtype=torch.int32, device=dev)}
         ws = self.workspace(B)
         pts, offs, boxes, n = self._db
-        _native.call("pdm_augment_select", torch.cuda.current_stream(dev).cuda_stream, B, M, gt_boxes.data_ptr(),
-                     len(self.g_num), _host_ints(self.g_cls), _host_ints(self.g_num), n, boxes.data_ptr(), offs.data_ptr(),
+        _native.call("pdm_augment_select", _native.stream(dev), B, M, gt_boxes.data_ptr(),
+                     len(self.g_num), _native.host_array(ctypes.c_int, self.g_cls), _native.host_array(ctypes.c_int, self.g_num), n,
+                     boxes.data_ptr(), offs.data_ptr(),
                      self.K, _ptr(params['sampled']) if self.K else None, params['flip'].data_ptr(),
                      params['angle'].data_ptr(), params['scale'].data_ptr(), self.plan['ops_code'],
-                     _host_floats(self.range), 1 if self.remove_outside else 0, M_out, out['boxes'].data_ptr(),
+                     _native.host_array(ctypes.c_float, self.range), 1 if self.remove_outside else 0, M_out, out['boxes'].data_ptr(),
                      out['box_counts'].data_ptr(), _ptr(out['accepted']) if self.K else None,
                      out['num_accepted'].data_ptr(), ws.data_ptr(), ws.numel())
         return out
@@ -286,11 +278,12 @@ class BatchAugmentor:
         B = counts.numel()
         ws = self.workspace(B)
         pts, offs, boxes, _ = self._db
-        _native.call(fn, torch.cuda.current_stream(raw.device).cuda_stream, B, raw.shape[1], raw.data_ptr(),
+        _native.call(fn, _native.stream(raw.device), B, raw.shape[1], raw.data_ptr(),
                      counts.data_ptr(), pts.data_ptr(), offs.data_ptr(), boxes.data_ptr(), self.K,
                      _ptr(out['accepted']) if self.K else None, out['num_accepted'].data_ptr(),
                      out['params']['flip'].data_ptr(), out['params']['angle'].data_ptr(), out['params']['scale'].data_ptr(),
-                     self.plan['ops_code'], _host_floats(self.range), _host_floats(self.extra), int(capacity),
+                     self.plan['ops_code'], _native.host_array(ctypes.c_float, self.range),
+                     _native.host_array(ctypes.c_float, self.extra), int(capacity),
                      out['counts'].data_ptr(), out['overflow'].data_ptr(), _ptr(rows), ws.data_ptr(), ws.numel())
 
     def _front(self, raw, counts, gt_boxes, params):

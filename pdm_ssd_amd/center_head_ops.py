@@ -18,15 +18,6 @@ _HEAD_ORDER = ('center', 'center_z', 'dim', 'rot', 'vel')
 _CHANNELS = {'center': 2, 'center_z': 1, 'dim': 3, 'rot': 2, 'vel': 2}
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _host(ctype, values):
-    arr = (ctype * max(len(values), 1))(*values)
-    return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-
 @torch.no_grad()
 def center_targets(gt_boxes, local_of, num_head_classes, H, W, x0, y0, vx, vy, stride, num_max_objs, gaussian_overlap,
                    min_radius):
@@ -43,8 +34,8 @@ def center_targets(gt_boxes, local_of, num_head_classes, H, W, x0, y0, vx, vy, s
     src = torch.empty((B, N, cols), dtype=torch.float32, device=dev)
     inds = torch.empty((B, N), dtype=torch.int64, device=dev)
     mask = torch.empty((B, N), dtype=torch.int64, device=dev)
-    keep, table = _host(ctypes.c_int, [int(v) for v in local_of])
-    _native.call("pdm_center_targets", _stream(dev), B, M, cols, int(num_head_classes), int(H), int(W), gt.data_ptr(),
+    table = _native.host_array(ctypes.c_int, local_of)
+    _native.call("pdm_center_targets", _native.stream(dev), B, M, cols, int(num_head_classes), int(H), int(W), gt.data_ptr(),
                  len(local_of) - 1, table, float(x0), float(y0), float(vx), float(vy), float(stride), N, float(gaussian_overlap),
                  int(min_radius), hm.data_ptr(), tb.data_ptr(), inds.data_ptr(), mask.data_ptr(), src.data_ptr())
     return hm, tb, inds, mask, src
@@ -77,13 +68,13 @@ def center_decode(hm, center, center_z, dim, rot, vel, K, score_thresh, post_cen
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     labels = torch.empty((B, K), dtype=torch.int64, device=dev)
     count = torch.empty((B,), dtype=torch.int32, device=dev)
-    k1, ptrs = _host(ctypes.c_void_p, [t.data_ptr() for t in maps] + [None] * (6 - len(maps)))
-    k2, bf = _host(ctypes.c_int, [1 if t.dtype == torch.bfloat16 else 0 for t in maps] + [0] * (6 - len(maps)))
-    k3, st = _host(ctypes.c_longlong, [s for t in maps for s in t.stride()] + [0] * (4 * (6 - len(maps))))
-    k4, lim = _host(ctypes.c_float, [float(v) for v in post_center_limit_range])
-    k5, gl = _host(ctypes.c_int, [int(v) for v in global_of])
+    ptrs = _native.host_array(ctypes.c_void_p, [t.data_ptr() for t in maps] + [None] * (6 - len(maps)))
+    bf = _native.host_array(ctypes.c_int, [1 if t.dtype == torch.bfloat16 else 0 for t in maps] + [0] * (6 - len(maps)))
+    st = _native.host_array(ctypes.c_longlong, [s for t in maps for s in t.stride()] + [0] * (4 * (6 - len(maps))))
+    lim = _native.host_array(ctypes.c_float, post_center_limit_range)
+    gl = _native.host_array(ctypes.c_int, global_of)
     assert len(global_of) == C and len(post_center_limit_range) == 6
-    _native.call("pdm_center_decode", _stream(dev), B, C, H, W, int(K), ptrs, bf, st,
+    _native.call("pdm_center_decode", _native.stream(dev), B, C, H, W, int(K), ptrs, bf, st,
                  float('-inf') if score_thresh is None else float(score_thresh), lim, float(x0), float(y0), float(vx), float(vy),
                  float(stride), gl, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr())
     return boxes, scores, labels, count
@@ -112,16 +103,16 @@ class _CenterRegLoss(Function):
                 ptrs.append(t.data_ptr() + c * sc * t.element_size())
                 bf.append(1 if t.dtype == torch.bfloat16 else 0)
                 st += [sb, sh, sw]
-        k1, ptrs = _host(ctypes.c_void_p, ptrs)
-        k2, bf = _host(ctypes.c_int, bf)
-        k3, st = _host(ctypes.c_longlong, st)
-        k4, cw = _host(ctypes.c_float, [float(v) for v in code_weights])
+        ptrs = _native.host_array(ctypes.c_void_p, ptrs)
+        bf = _native.host_array(ctypes.c_int, bf)
+        st = _native.host_array(ctypes.c_longlong, st)
+        cw = _native.host_array(ctypes.c_float, code_weights)
         nbytes = _native.lib().pdm_center_reg_loss_workspace_bytes(B, D)
         ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
         per_code = torch.empty(D, dtype=torch.float32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
         grad = torch.empty((B, D, H, W), dtype=torch.float32, device=dev)
-        _native.call("pdm_center_reg_loss", _stream(dev), B, N, D, H, W, ptrs, bf, st, inds.data_ptr(), mask.data_ptr(),
+        _native.call("pdm_center_reg_loss", _native.stream(dev), B, N, D, H, W, ptrs, bf, st, inds.data_ptr(), mask.data_ptr(),
                      target.data_ptr(), cw, float(loc_weight), per_code.data_ptr(), out.data_ptr(), grad.data_ptr(), ws.data_ptr(), nbytes)
         ctx.save_for_backward(grad)
         ctx.split = [t.shape[1] for t in maps]

@@ -28,6 +28,32 @@ int check_launch(const char *what) {
     return (int)e;
 }
 
+// 16 bytes per lane over the aligned middle of the range; the first 16 threads clear the unaligned head and the tail by bytes.
+typedef unsigned zf_u4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void zero_fill_kernel(char *__restrict__ p, unsigned head, size_t n16, unsigned tail) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    zf_u4 *__restrict__ mid = reinterpret_cast<zf_u4 *>(p + head);
+    if (tid < head) p[tid] = 0;
+    if (tid < tail) p[head + (n16 << 4) + tid] = 0;
+    for (size_t i = tid; i < n16; i += (size_t)gridDim.x * 256) mid[i] = zf_u4{0u, 0u, 0u, 0u};
+}
+
+// Every buffer the library clears goes through here.  A kernel rather than the runtime's memset, so that a captured graph clears
+// the buffer on every replay: a captured 4-byte memset node was seen (once, on the MI355X, in pdm_post_process) to leave the
+// byte pattern 0x08 in its word instead of zeros when the graph was replayed; the kernel form has not shown it.  The launch
+// check also reports the runtime's message and leaves no sticky error for the next entry point to report again.
+int zero_fill(void *stream, const char *who, void *p, size_t bytes) {
+    if (bytes == 0) return 0;
+    const size_t to_aligned = (size_t)(-reinterpret_cast<uintptr_t>(p) & 15);
+    const unsigned head = (unsigned)(to_aligned < bytes ? to_aligned : bytes);
+    const size_t n16 = (bytes - head) >> 4;
+    const unsigned tail = (unsigned)((bytes - head) & 15);
+    const size_t want = (n16 + 256 * 2 - 1) / (256 * 2);       // 32 bytes per lane, at most 8192 workgroups
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)(want < 1 ? 1 : want > 8192 ? 8192 : want)), dim3(256), 0, as_stream(stream),
+                       static_cast<char *>(p), head, n16, tail);
+    return check_launch(who);
+}
+
 int grant_lds(const void *fn, size_t bytes) {
     static std::mutex mu;
     static std::set<std::pair<const void *, int>> done;

@@ -31,19 +31,6 @@ __device__ __forceinline__ float ch_load(const void *p, int bf16, long long i) {
     return bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(p)[i] << 16) : static_cast<const float *>(p)[i];
 }
 
-// Zero fill by a kernel rather than hipMemsetAsync, so that a captured graph clears the buffer on every replay (a captured
-// memset node was seen to leave a byte pattern instead of zeros, see post_process.hip)
-__global__ __launch_bounds__(CT_T) void ch_zero_kernel(float *__restrict__ p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * CT_T + threadIdx.x; i < n; i += (size_t)gridDim.x * CT_T) p[i] = 0.0f;
-}
-
-static int ch_zero(void *stream, const char *what, float *p, size_t n) {
-    if (n == 0) return 0;
-    const size_t want = (n + CT_T * 8 - 1) / (CT_T * 8);
-    hipLaunchKernelGGL(ch_zero_kernel, dim3((unsigned)(want > 8192 ? 8192 : want)), dim3(CT_T), 0, as_stream(stream), p, n);
-    return check_launch(what);
-}
-
 // ---- targets -------------------------------------------------------------------------------------------------------------
 struct CtArgs {
     int B, M, cols, nmax;            // gt_boxes (B, M, cols), cols = 7 + E + 1, class last
@@ -349,7 +336,7 @@ extern "C" int pdm_center_targets(void *stream, int B, int M, int cols, int C, i
     }
     a.local_of[0] = 0;
     a.heatmap = heatmap; a.target = target_boxes; a.src = target_boxes_src; a.inds = inds; a.mask = mask;
-    if (int rc = ch_zero(stream, "center_targets(zero)", heatmap, (size_t)B * C * H * W)) return rc;
+    if (int rc = zero_fill(stream, "center_targets(zero)", heatmap, sizeof(float) * (size_t)B * C * H * W)) return rc;
     hipLaunchKernelGGL(ct_assign_kernel, dim3((unsigned)B), dim3(CT_T), 0, as_stream(stream), a);
     if (int rc = check_launch("center_targets(assign)")) return rc;
     hipLaunchKernelGGL(ct_draw_kernel, dim3((unsigned)(B * num_max_objs)), dim3(CT_T), 0, as_stream(stream), a);
@@ -426,7 +413,7 @@ extern "C" int pdm_center_reg_loss(void *stream, int B, int num_max_objs, int D,
     hipLaunchKernelGGL(rl_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), a);
     if (int rc = check_launch("center_reg_loss(finalize)")) return rc;
     if (B == 0) return 0;
-    if (int rc = ch_zero(stream, "center_reg_loss(zero)", grad, (size_t)B * D * H * W)) return rc;
+    if (int rc = zero_fill(stream, "center_reg_loss(zero)", grad, sizeof(float) * (size_t)B * D * H * W)) return rc;
     hipLaunchKernelGGL(rl_grad_kernel, dim3((unsigned)B), dim3(CT_T), sizeof(int) * (size_t)num_max_objs, as_stream(stream), a);
     return check_launch("center_reg_loss(grad)");
 }

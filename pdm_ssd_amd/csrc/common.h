@@ -12,6 +12,8 @@ namespace pdm {
 // Thread-local error text behind pdm_last_error().
 void set_error(const char *fmt, ...);
 int check_launch(const char *what);
+// Clears `bytes` bytes at p (any alignment) on the stream with a kernel; 0 bytes launch nothing.  Returns check_launch(who).
+int zero_fill(void *stream, const char *who, void *p, size_t bytes);
 // More than 64 KB of dynamic LDS has to be granted per kernel function AND per device (hipFuncSetAttribute acts on the
 // CURRENT device's copy of the function; entry points may be called for any device).  Remembers (function, device)
 // pairs, thread-safe; returns hipSuccess (0) or the runtime's error code.

@@ -439,12 +439,9 @@ extern "C" int pdm_query_and_group(void *stream, int b, int n, int m, int c, flo
                 "query_and_group: null pointer");
     PDM_REQUIRE(n >= 1, PDM_E_BADARG, "query_and_group: n=%d", n);
     // pointnet2_utils.py:218 — rows of empty balls are zeros
-    hipError_t e = hipMemsetAsync(idx, 0, sizeof(int) * (size_t)b * L, as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("query_and_group: memset failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    int rc = pdm_ball_query(stream, b, n, m, radius, nsample, new_xyz, xyz, idx);
+    int rc = zero_fill(stream, "query_and_group(zero)", idx, sizeof(int) * (size_t)b * L);
+    if (rc != 0) return rc;
+    rc = pdm_ball_query(stream, b, n, m, radius, nsample, new_xyz, xyz, idx);
     if (rc != 0) return rc;
     return pdm_group_concat(stream, b, n, m, c, nsample, xyz, new_xyz, features, idx, out);
 }

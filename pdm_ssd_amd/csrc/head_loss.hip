@@ -192,8 +192,7 @@ extern "C" int pdm_point_head_loss(void *stream, long long n_total, int n_per_sa
     a.labels = labels; a.dcls = dcls; a.dbox = dbox; a.out = out;
     a.counts = static_cast<int *>(workspace);
     a.partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + 16);
-    hipError_t e = hipMemsetAsync(workspace, 0, 16, as_stream(stream));
-    PDM_REQUIRE(e == hipSuccess, PDM_E_BADARG, "point_head_loss: memset failed");
+    if (int rc = zero_fill(stream, "point_head_loss(zero)", workspace, 16)) return rc;
     const long long blocks = (n_total + HL_T - 1) / HL_T;
     if (blocks > 0) {
         const int cgrid = (int)(blocks < 1024 ? blocks : 1024);

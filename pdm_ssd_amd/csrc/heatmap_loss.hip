@@ -124,8 +124,7 @@ extern "C" int pdm_heatmap_targets(void *stream, int B, int M, int C, int H, int
                 PDM_E_BADARG, "heatmap_targets: bad size");
     if (B == 0) return 0;
     PDM_REQUIRE(heatmap && (M == 0 || gt_boxes), PDM_E_BADARG, "heatmap_targets: null pointer");
-    const hipError_t e = hipMemsetAsync(heatmap, 0, sizeof(float) * (size_t)B * C * H * W, as_stream(stream));
-    PDM_REQUIRE(e == hipSuccess, PDM_E_BADARG, "heatmap_targets: memset failed");
+    if (int rc = zero_fill(stream, "heatmap_targets(zero)", heatmap, sizeof(float) * (size_t)B * C * H * W)) return rc;
     if (M == 0) return 0;
     PDM_REQUIRE((long long)B * M <= 0x7fffffffll, PDM_E_TOOLARGE, "heatmap_targets: %lld boxes", (long long)B * M);
     HmTargetArgs a{B, M, C, H, W, gt_boxes, x0, y0, vx, vy, stride, min_overlap, min_radius, max_radius, heatmap};

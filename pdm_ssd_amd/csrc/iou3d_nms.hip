@@ -120,11 +120,7 @@ extern "C" int pdm_nms(void *stream, int n, const float *boxes, float thresh, in
                        size_t workspace_bytes, long long *keep, int *num_out) {
     PDM_REQUIRE(n >= 0 && n <= 16384 * 64, PDM_E_TOOLARGE, "nms: n=%d (at most 1048576 boxes)", n);
     PDM_REQUIRE(num_out, PDM_E_BADARG, "nms: null pointer");
-    if (n == 0) {
-        const hipError_t e = hipMemsetAsync(num_out, 0, sizeof(int), as_stream(stream));
-        if (e != hipSuccess) { set_error("nms: memset failed"); return (int)e; }
-        return 0;
-    }
+    if (n == 0) return zero_fill(stream, "nms(zero)", num_out, sizeof(int));
     PDM_REQUIRE(boxes && keep && workspace && workspace_bytes >= pdm_nms_workspace_bytes(n), PDM_E_BADARG,
                 "nms: null pointer or workspace of %zu bytes, need %zu", workspace_bytes, pdm_nms_workspace_bytes(n));
     const int cb = (n + 63) / 64;

@@ -433,7 +433,7 @@ static int pg_span(int k) { return (k / 2 * 2 + PG_TS - 1) / PG_TS + 1; }  // ti
 extern "C" size_t pdm_gather_bev_workspace_bytes(int B, int P, int W, int H, int kx, int ky) {
     // P = 0 still needs the per-tile list starts (zeroed; the gather kernel reads them to write empty tiles).  (Until round 4 this returned
     // 0 for P = 0: the caller's 16-byte stand-in was then overrun by B (ntiles + 1) ints — unnoticed inside the allocator's 2 MB segment
-    // until the block happened to be the last of one, where hipMemsetAsync refused the range.)
+    // until the block happened to be the last of one, where the runtime's memset refused the range.)
     if (B <= 0 || P < 0 || W <= 0 || H <= 0) return 0;
     const long long ntiles = (long long)((W + PG_TS - 1) / PG_TS) * ((H + PG_TS - 1) / PG_TS);
     const long long cap = (long long)P * pg_span(kx) * pg_span(ky);
@@ -467,18 +467,14 @@ extern "C" int pdm_gather_bev(void *stream, int B, int P, int C, int degree, con
                                 : ((size_t)ncell * C + ncell + (size_t)ncell * PG_CHUNK + (size_t)PG_CHUNK * C +
                                    PG_CHUNK * (4 + PG_MAXSH)) * sizeof(float) + PG_CHUNK * 3 * sizeof(int);
     PDM_REQUIRE(lds <= 64 * 1024, PDM_E_TOOLARGE, "pdm_gather_bev: C=%d D=%d need %zu bytes of LDS (use pdm_scatter_bev)", C, D, lds);
-    if (P > 0)
+    int rc;
+    if (P > 0) {
         hipLaunchKernelGGL(pdm_bin_kernel, dim3(B), dim3(PG_THREADS), (size_t)ntiles * sizeof(int), as_stream(stream), P, g,
                            ntiles, (int)cap, xyz, tile_start, tile_pts);
-    else {
-        hipError_t e = hipMemsetAsync(tile_start, 0, (size_t)B * (ntiles + 1) * sizeof(int), as_stream(stream));
-        if (e != hipSuccess) {
-            set_error("pdm_gather_bev: memset of %zu bytes at %p failed: %s", (size_t)B * (ntiles + 1) * sizeof(int), (void *)tile_start, hipGetErrorString(e));
-            (void)hipGetLastError();      // (not to be reported again by the next entry point's launch check)
-            return (int)e;
-        }
+        rc = check_launch("pdm_gather_bev(bin)");
+    } else {
+        rc = zero_fill(stream, "pdm_gather_bev(zero)", tile_start, (size_t)B * (ntiles + 1) * sizeof(int));
     }
-    int rc = check_launch("pdm_gather_bev(bin)");
     if (rc) return rc;
 #define PG_LAUNCH(K) hipLaunchKernelGGL(K, dim3(ntiles, B), dim3(PG_THREADS), lds, as_stream(stream), P, C, degree, g, ntiles, \
                                         (int)cap, normalize, eps, xyz, feat, sh, inv2s2, tile_start, tile_pts, tile_sorted, grid, wsum)

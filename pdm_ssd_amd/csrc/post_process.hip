@@ -269,8 +269,8 @@ static PPLayout pp_layout(int S, int pre, int post) {
     return l;
 }
 
-// the error flag and the recall counts start at 0 on every call: a kernel rather than hipMemsetAsync, so that a captured
-// graph resets them on every replay (a captured 4-byte memset node was seen to leave a byte pattern instead of zeros)
+// the error flag and the recall counts start at 0 on every call: two unrelated buffers in one launch, by a kernel for the
+// reason told at pdm::zero_fill (api.hip)
 __global__ __launch_bounds__(64) void pp_zero_kernel(int *__restrict__ err, unsigned long long *__restrict__ recall, int nr) {
     if (threadIdx.x == 0) *err = 0;
     if (recall && (int)threadIdx.x < nr) recall[threadIdx.x] = 0ull;

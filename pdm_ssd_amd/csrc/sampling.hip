@@ -972,11 +972,7 @@ extern "C" int pdm_furthest_point_sampling_jobs(void *stream, int njobs, int b, 
             seg.xch[q] = reinterpret_cast<unsigned long long *>(workspace[q]);
             seg.status[q] = reinterpret_cast<unsigned *>(static_cast<char *>(workspace[q]) + ws_need - 64);
             // stale tags from an earlier segment must not look like iteration numbers of this one
-            hipError_t e = hipMemsetAsync(workspace[q], 0, ws_need, as_stream(stream));
-            if (e != hipSuccess) {
-                set_error("fps_jobs: memset failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
+            if (int rc = zero_fill(stream, "fps_jobs(zero)", workspace[q], ws_need)) return rc;
         }
     }
     if (G == 1)
@@ -1069,11 +1065,7 @@ extern "C" int pdm_furthest_point_sampling_ws(void *stream, int b, int n, int m,
                 PDM_E_BADARG, "fps_ws: workspace of %zu bytes, need %zu (8-byte aligned)", workspace_bytes,
                 pdm_furthest_point_sampling_ws_bytes(b, n));
     // stale tags from an earlier use of the workspace must not look like iteration numbers
-    hipError_t e = hipMemsetAsync(workspace, 0, pdm_furthest_point_sampling_ws_bytes(b, n), as_stream(stream));
-    if (e != hipSuccess) {
-        set_error("fps_ws: memset failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    if (int rc = zero_fill(stream, "fps_ws(zero)", workspace, pdm_furthest_point_sampling_ws_bytes(b, n))) return rc;
     // all G workgroups of a cloud must be co-resident (they wait for each other): the launch is cut into chunks of
     // clouds that the device holds at once; a device that cannot hold even one cloud's workgroups takes the
     // single-workgroup streaming kernel

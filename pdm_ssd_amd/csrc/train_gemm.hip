@@ -1134,11 +1134,7 @@ extern "C" int pdm_tg_wgrad(void *stream, long long R, int K, int N, const void 
     if (K == 0 || N == 0) return 0;
     PDM_REQUIRE(dW, PDM_E_BADARG, "tg_wgrad: null pointer");
     if (R == 0) {
-        if (!accumulate) {
-            const hipError_t e = hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, as_stream(stream));
-            PDM_REQUIRE(e == hipSuccess, PDM_E_BADARG, "tg_wgrad: memset failed");
-        }
-        return 0;
+        return accumulate ? 0 : zero_fill(stream, "tg_wgrad(zero)", dW, sizeof(float) * (size_t)N * K);
     }
     PDM_REQUIRE(dY && X && workspace, PDM_E_BADARG, "tg_wgrad: null pointer");
     PDM_REQUIRE(K % 8 == 0 && N % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= K && ldy >= N, PDM_E_BADARG,
@@ -1185,11 +1181,7 @@ extern "C" int pdm_tg_colsum(void *stream, long long R, int N, const void *Y, lo
     PDM_REQUIRE(R >= 0 && N >= 0, PDM_E_BADARG, "tg_colsum: negative size");
     if (N == 0) return 0;
     PDM_REQUIRE(out, PDM_E_BADARG, "tg_colsum: null pointer");
-    if (R == 0) {
-        const hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)N, as_stream(stream));
-        PDM_REQUIRE(e == hipSuccess, PDM_E_BADARG, "tg_colsum: memset failed");
-        return 0;
-    }
+    if (R == 0) return zero_fill(stream, "tg_colsum(zero)", out, sizeof(float) * (size_t)N);
     PDM_REQUIRE(Y && scratch && N % 8 == 0 && N <= 512 && ld % 8 == 0 && ld >= N && tg_al16(Y), PDM_E_BADARG,
                 "tg_colsum: N=%d (multiple of 8, <= 512), ld=%lld (multiple of 8), 16-byte aligned rows", N, ld);
     int chp = 1;

@@ -49,7 +49,7 @@ class _Depthwise3x3CL(torch.autograd.Function):
         w9 = weight.reshape(C, 9).t().contiguous()                 # (9, C) tap-major
         out = torch.empty_like(rows, dtype=torch.bfloat16) if out_bf16 else torch.empty_like(rows)
         zero = torch.zeros(C, dtype=torch.float32, device=x.device)
-        _native.call("pdm_bev_depthwise3x3_t", torch.cuda.current_stream(x.device).cuda_stream, B, H, W, C, rows.data_ptr(), 0,
+        _native.call("pdm_bev_depthwise3x3_t", _native.stream(x.device), B, H, W, C, rows.data_ptr(), 0,
                      w9.data_ptr(), zero.data_ptr(), out.data_ptr(), 1 if out_bf16 else 0, 0)
         ctx.save_for_backward(rows, w9)
         ctx.out_bf16 = bool(out_bf16)
@@ -65,7 +65,7 @@ class _Depthwise3x3CL(torch.autograd.Function):
         gr = (g.to(torch.bfloat16) if gb else g.float()).permute(0, 2, 3, 1)
         if not gr.is_contiguous():
             gr = gr.contiguous()
-        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        stream = _native.stream(rows.device)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx_rows = torch.empty_like(rows)
@@ -197,12 +197,12 @@ class PDMHeatmapHead(nn.Module):
         _, w, shift = cache['dw']
         pk = fused.cached_layers(self, 'pw', self, lambda: [(mods[3], mods[4]), (self.hm[0], None), (self.hm[2], None)], x.device)
         out = torch.empty((B, H, W, (self.num_class + 3) // 4 * 4), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        stream = _native.stream(x.device)
         if getattr(self, 'use_one_kernel', True) and pk.dims == [128, 64, 64, 16]:
             # the depthwise stage as the prologue of the per-cell MLP: the map is read once, nothing in between is written
             fused._count(f"pdm_bev_head_fused", B * H * W, pk)
             _native.call("pdm_bev_head_fused", stream, B, H, W, C, rows.data_ptr(), w.data_ptr(), shift.data_ptr(), pk.nlayers,
-                         pk.dims_ptr, pk.wpack.data_ptr(), pk.bias.data_ptr(), 0, out.data_ptr(), out.shape[-1], self.num_class)
+                         pk.dims_c, pk.wpack.data_ptr(), pk.bias.data_ptr(), 0, out.data_ptr(), out.shape[-1], self.num_class)
         else:
             mid = torch.empty_like(rows)
             _native.call("pdm_bev_depthwise3x3", stream, B, H, W, C, rows.data_ptr(), w.data_ptr(), shift.data_ptr(),

@@ -193,7 +193,7 @@ class PointHeadBox(PointHeadTemplate):
         boxes = torch.empty((n, 7), dtype=torch.float32, device=cls.device)
         scores = torch.empty((n,), dtype=torch.float32, device=cls.device)
         pts = coords[:, 1:4]
-        _native.call("pdm_point_head_decode", torch.cuda.current_stream(cls.device).cuda_stream, n, self.num_class, cls.data_ptr(),
+        _native.call("pdm_point_head_decode", _native.stream(cls.device), n, self.num_class, cls.data_ptr(),
                      cls.stride(0), box.data_ptr(), box.stride(0), pts.data_ptr(), coords.stride(0),
                      coder.mean_size.contiguous().data_ptr(), boxes.data_ptr(), scores.data_ptr())
         batch_dict['point_cls_scores'] = scores

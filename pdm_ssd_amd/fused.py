@@ -101,10 +101,6 @@ class PackedMLP:
         self.wpack = torch.from_numpy(np.concatenate(ws)).to(device)
         self.bias = torch.from_numpy(np.concatenate(bs)).to(device)
 
-    @property
-    def dims_ptr(self):
-        return ctypes.cast(self.dims_c, ctypes.c_void_p)
-
 
 class PackedPre:
     """First-layer column blocks of several MLPs stacked into one linear map: z = [W_a f | W_b f | ...] (no bias,
@@ -132,10 +128,6 @@ class PackedPre:
         self.bias = torch.from_numpy(pb).to(device)
         self.nlayers = 1
         self.cout = o
-
-    @property
-    def dims_ptr(self):
-        return ctypes.cast(self.dims_c, ctypes.c_void_p)
 
 
 def _state_key(module):
@@ -231,10 +223,6 @@ class PackedMLPx3:
         self.wstream = torch.from_numpy(np.concatenate(chunks).view(np.int16)).to(device)
         self.bias = torch.from_numpy(np.concatenate(biases)).to(device)
 
-    @property
-    def dims_ptr(self):
-        return ctypes.cast(self.dims_c, ctypes.c_void_p)
-
 
 def rows_forward_x3(pk, in_pm, out_pm, relu_last=False):
     """Per-row three-layer MLP with fp32 emulated by three bf16 pieces per operand (six partial products, fp32 accumulation)."""
@@ -242,7 +230,7 @@ def rows_forward_x3(pk, in_pm, out_pm, relu_last=False):
     rows = in_pm.numel() // cin
     assert pk.cin == cin and in_pm.is_contiguous() and out_pm.is_contiguous() and in_pm.dtype == torch.float32
     _count(f"pdm_rows_mlp_x3[{pk.nlayers} layers, {cin} in, {rows} rows]", rows, pk)
-    _native.call("pdm_rows_mlp_x3", _stream(in_pm), rows, cin, in_pm.data_ptr(), pk.nlayers, pk.dims_ptr, pk.wstream.data_ptr(),
+    _native.call("pdm_rows_mlp_x3", _native.stream(in_pm), rows, cin, in_pm.data_ptr(), pk.nlayers, pk.dims_c, pk.wstream.data_ptr(),
                  pk.wstream.numel() * 2, pk.bias.data_ptr(), 1 if relu_last else 0, out_pm.data_ptr(), out_pm.shape[-1], pk.cout)
 
 
@@ -288,10 +276,6 @@ def cached_pre_packs(owner, slot, seqs, device, pre_cols, keep_cols, min_in=0):
     return pre, packs
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def sa_scale_forward(pk, xyz, new_xyz, feat_pm, idx, out_pm, out_coff):
     """One SA scale: xyz (B,N,3), new_xyz (B,M,3), feat_pm (B,N,Cin)|None, idx (B,M,ns) int32 ->
     out_pm[:, :, out_coff:out_coff+pk.cout] (B,M,stride)."""
@@ -300,8 +284,8 @@ def sa_scale_forward(pk, xyz, new_xyz, feat_pm, idx, out_pm, out_coff):
     cin = 0 if feat_pm is None else feat_pm.shape[2]
     assert pk.cin == cin + 3
     _count("pdm_sa_mlp_fused", B * M * ns, pk)
-    _native.call("pdm_sa_mlp_fused", _stream(xyz), B, N, M, cin, ns, xyz.data_ptr(), new_xyz.data_ptr(),
-                 0 if feat_pm is None else feat_pm.data_ptr(), idx.data_ptr(), pk.nlayers, pk.dims_ptr,
+    _native.call("pdm_sa_mlp_fused", _native.stream(xyz), B, N, M, cin, ns, xyz.data_ptr(), new_xyz.data_ptr(),
+                 0 if feat_pm is None else feat_pm.data_ptr(), idx.data_ptr(), pk.nlayers, pk.dims_c,
                  pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], out_coff, pk.cout)
 
 
@@ -312,9 +296,9 @@ def fp_forward(pk, known_pm, skip_pm, idx, weight, out_pm):
     cs = 0 if skip_pm is None else skip_pm.shape[2]
     assert pk.cin == ck + cs
     _count("pdm_fp_mlp_fused", B * n, pk)
-    _native.call("pdm_fp_mlp_fused", _stream(known_pm), B, n, m, ck, cs, known_pm.data_ptr(),
+    _native.call("pdm_fp_mlp_fused", _native.stream(known_pm), B, n, m, ck, cs, known_pm.data_ptr(),
                  0 if skip_pm is None else skip_pm.data_ptr(), idx.data_ptr(), weight.data_ptr(), pk.nlayers,
-                 pk.dims_ptr, pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], pk.cout)
+                 pk.dims_c, pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], pk.cout)
 
 
 def rows_forward(pk, in_pm, out_pm, relu_last=True):
@@ -323,7 +307,7 @@ def rows_forward(pk, in_pm, out_pm, relu_last=True):
     rows = in_pm.numel() // cin
     assert pk.cin == cin and in_pm.is_contiguous() and out_pm.is_contiguous()
     _count(f"pdm_rows_mlp_fused[{pk.nlayers} layers, {cin} in, {rows} rows]", rows, pk)   # bench.py keeps the shapes apart
-    _native.call("pdm_rows_mlp_fused", _stream(in_pm), rows, cin, in_pm.data_ptr(), pk.nlayers, pk.dims_ptr,
+    _native.call("pdm_rows_mlp_fused", _native.stream(in_pm), rows, cin, in_pm.data_ptr(), pk.nlayers, pk.dims_c,
                  pk.wpack.data_ptr(), pk.bias.data_ptr(), 1 if relu_last else 0, out_pm.data_ptr(),
                  out_pm.shape[-1], pk.cout)
 
@@ -338,7 +322,7 @@ def rows_forward_pair(pk_a, pk_b, in_pm, out_a, out_b, relu_last=True):
     tag = f"pdm_rows_mlp_fused_pair[{pk_a.nlayers} layers, {cin} in, {rows} rows]"    # bench.py's OpTimer forms the same name
     _count(tag, rows, pk_a)
     _count(tag, rows, pk_b)
-    _native.call("pdm_rows_mlp_fused_pair", _stream(in_pm), rows, cin, in_pm.data_ptr(), pk_a.nlayers, pk_a.dims_ptr,
+    _native.call("pdm_rows_mlp_fused_pair", _native.stream(in_pm), rows, cin, in_pm.data_ptr(), pk_a.nlayers, pk_a.dims_c,
                  pk_a.wpack.data_ptr(), pk_a.bias.data_ptr(), pk_b.wpack.data_ptr(), pk_b.bias.data_ptr(), 1 if relu_last else 0,
                  out_a.data_ptr(), out_a.shape[-1], pk_a.cout, out_b.data_ptr(), out_b.shape[-1], pk_b.cout)
 
@@ -376,9 +360,9 @@ def fp_head_forward(d, pk_a, pk_b, out_a, out_b, relu_last=False):
     tag = f"pdm_rows_mlp_fused_pair[{pk_a.nlayers} layers, {pk_a.cin} in, {rows} rows]"
     _count(tag, rows, pk_a)
     _count(tag, rows, pk_b)
-    _native.call("pdm_fp_head_fused", _stream(d.z), B, n, m, cs, d.z.data_ptr(), d.z.shape[2],
-                 0 if d.skip_pm is None else d.skip_pm.data_ptr(), d.idx.data_ptr(), d.weight.data_ptr(), d.pk.dims_ptr,
-                 d.pk.wpack.data_ptr(), d.pk.bias.data_ptr(), d.out_pm.data_ptr(), d.out_pm.shape[2], d.pk.cout, pk_a.dims_ptr,
+    _native.call("pdm_fp_head_fused", _native.stream(d.z), B, n, m, cs, d.z.data_ptr(), d.z.shape[2],
+                 0 if d.skip_pm is None else d.skip_pm.data_ptr(), d.idx.data_ptr(), d.weight.data_ptr(), d.pk.dims_c,
+                 d.pk.wpack.data_ptr(), d.pk.bias.data_ptr(), d.out_pm.data_ptr(), d.out_pm.shape[2], d.pk.cout, pk_a.dims_c,
                  pk_a.wpack.data_ptr(), pk_a.bias.data_ptr(), pk_b.wpack.data_ptr(), pk_b.bias.data_ptr(), 1 if relu_last else 0,
                  out_a.data_ptr(), out_a.shape[-1], pk_a.cout, out_b.data_ptr(), out_b.shape[-1], pk_b.cout)
     d.done = True
@@ -390,8 +374,8 @@ def sa_scale_forward_pre(pk, xyz, new_xyz, z, z_coff, idx, out_pm, out_coff):
     M, ns = idx.shape[1], idx.shape[2]
     assert pk.cin == 3 and z.shape[0] == B and z.shape[1] == N
     _count("pdm_sa_mlp_fused_pre", B * M * ns, pk)
-    _native.call("pdm_sa_mlp_fused_pre", _stream(xyz), B, N, M, ns, xyz.data_ptr(), new_xyz.data_ptr(), z.data_ptr(),
-                 z.shape[2], z_coff, idx.data_ptr(), pk.nlayers, pk.dims_ptr, pk.wpack.data_ptr(), pk.bias.data_ptr(),
+    _native.call("pdm_sa_mlp_fused_pre", _native.stream(xyz), B, N, M, ns, xyz.data_ptr(), new_xyz.data_ptr(), z.data_ptr(),
+                 z.shape[2], z_coff, idx.data_ptr(), pk.nlayers, pk.dims_c, pk.wpack.data_ptr(), pk.bias.data_ptr(),
                  out_pm.data_ptr(), out_pm.shape[2], out_coff, pk.cout)
 
 
@@ -407,7 +391,7 @@ def sa_pack(idx, n):
     meta = torch.empty((8,), dtype=torch.int32, device=idx.device)
     ws_bytes = l.pdm_sa_pack_workspace_bytes(B, M)
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=idx.device)
-    _native.call("pdm_sa_pack", _stream(idx), B, n, M, ns, idx.data_ptr(), ws.data_ptr(), ws_bytes, pack.data_ptr(),
+    _native.call("pdm_sa_pack", _native.stream(idx), B, n, M, ns, idx.data_ptr(), ws.data_ptr(), ws_bytes, pack.data_ptr(),
                  meta.data_ptr())
     return pack, meta
 
@@ -418,16 +402,15 @@ def sa_pack_pair(idx0, idx1, n):
     B, M = idx0.shape[:2]
     l = _native.lib()
     ws_bytes = l.pdm_sa_pack_workspace_bytes(B, M)
-    outs, keep = [], []
+    outs = []
     for idx in (idx0, idx1):
         rows = l.pdm_sa_pack_rows(B, M, idx.shape[2])
         outs.append((torch.empty((rows, 2), dtype=torch.int32, device=idx.device), torch.empty((8,), dtype=torch.int32, device=idx.device),
                      torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=idx.device)))
     I2, P2 = ctypes.c_int * 2, ctypes.c_void_p * 2
-    keep = [I2(idx0.shape[2], idx1.shape[2]), P2(idx0.data_ptr(), idx1.data_ptr()), P2(outs[0][2].data_ptr(), outs[1][2].data_ptr()),
-            P2(outs[0][0].data_ptr(), outs[1][0].data_ptr()), P2(outs[0][1].data_ptr(), outs[1][1].data_ptr())]
-    c = [ctypes.cast(k, ctypes.c_void_p) for k in keep]
-    _native.call("pdm_sa_pack_pair", _stream(idx0), B, n, M, c[0], c[1], c[2], ws_bytes, c[3], c[4])
+    _native.call("pdm_sa_pack_pair", _native.stream(idx0), B, n, M, I2(idx0.shape[2], idx1.shape[2]), P2(idx0.data_ptr(), idx1.data_ptr()),
+                 P2(outs[0][2].data_ptr(), outs[1][2].data_ptr()), ws_bytes, P2(outs[0][0].data_ptr(), outs[1][0].data_ptr()),
+                 P2(outs[0][1].data_ptr(), outs[1][1].data_ptr()))
     return [(outs[0][0], outs[0][1]), (outs[1][0], outs[1][1])]
 
 
@@ -441,9 +424,9 @@ def sa_scale_forward_packed(pk, xyz, new_xyz, feat_pm, z, z_coff, packed, ns, ou
     assert pk.cin == cin + 3
     if FLOP_COUNTER is not None:
         _count("pdm_sa_mlp_packed", int(meta[6].item()), pk)   # rows actually run (a sync: accounting passes only)
-    _native.call("pdm_sa_mlp_packed", _stream(xyz), B, N, M, cin, ns, xyz.data_ptr(), new_xyz.data_ptr(),
+    _native.call("pdm_sa_mlp_packed", _native.stream(xyz), B, N, M, cin, ns, xyz.data_ptr(), new_xyz.data_ptr(),
                  0 if cin == 0 else feat_pm.data_ptr(), 0 if z is None else z.data_ptr(),
-                 0 if z is None else z.shape[2], z_coff, pack.data_ptr(), meta.data_ptr(), pk.nlayers, pk.dims_ptr,
+                 0 if z is None else z.shape[2], z_coff, pack.data_ptr(), meta.data_ptr(), pk.nlayers, pk.dims_c,
                  pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], out_coff, pk.cout)
 
 
@@ -458,13 +441,11 @@ def sa_level_forward_packed(pks, xyz, new_xyz, feat_pm, z, z_coffs, packeds, nss
         for pk, (pack, meta) in zip(pks, packeds):
             _count("pdm_sa_mlp_packed_pair", int(meta[6].item()), pk)   # rows actually run (a sync: accounting passes only)
     I2, P2 = ctypes.c_int * 2, ctypes.c_void_p * 2
-    keep = [I2(*nss), I2(*z_coffs), P2(*[p.data_ptr() for p, _ in packeds]), P2(*[m.data_ptr() for _, m in packeds]),
-            I2(*[pk.nlayers for pk in pks]), P2(*[pk.dims_ptr.value for pk in pks]), P2(*[pk.wpack.data_ptr() for pk in pks]),
-            P2(*[pk.bias.data_ptr() for pk in pks]), I2(*out_coffs), I2(*[pk.cout for pk in pks])]
-    c = [ctypes.cast(k, ctypes.c_void_p) for k in keep]
-    _native.call("pdm_sa_mlp_packed_pair", _stream(xyz), B, N, M, cin, c[0], xyz.data_ptr(), new_xyz.data_ptr(),
-                 0 if cin == 0 else feat_pm.data_ptr(), 0 if z is None else z.data_ptr(), 0 if z is None else z.shape[2], c[1], c[2], c[3],
-                 c[4], c[5], c[6], c[7], out_pm.data_ptr(), out_pm.shape[2], c[8], c[9])
+    _native.call("pdm_sa_mlp_packed_pair", _native.stream(xyz), B, N, M, cin, I2(*nss), xyz.data_ptr(), new_xyz.data_ptr(),
+                 0 if cin == 0 else feat_pm.data_ptr(), 0 if z is None else z.data_ptr(), 0 if z is None else z.shape[2], I2(*z_coffs),
+                 P2(*[p.data_ptr() for p, _ in packeds]), P2(*[m.data_ptr() for _, m in packeds]), I2(*[pk.nlayers for pk in pks]),
+                 P2(*[ctypes.addressof(pk.dims_c) for pk in pks]), P2(*[pk.wpack.data_ptr() for pk in pks]),
+                 P2(*[pk.bias.data_ptr() for pk in pks]), out_pm.data_ptr(), out_pm.shape[2], I2(*out_coffs), I2(*[pk.cout for pk in pks]))
 
 
 def fp_forward_pre(pk, z, skip_pm, idx, weight, out_pm):
@@ -474,6 +455,6 @@ def fp_forward_pre(pk, z, skip_pm, idx, weight, out_pm):
     cs = 0 if skip_pm is None else skip_pm.shape[2]
     assert pk.cin == cs
     _count("pdm_fp_mlp_fused_pre", B * n, pk)
-    _native.call("pdm_fp_mlp_fused_pre", _stream(z), B, n, m, cs, z.data_ptr(), z.shape[2],
+    _native.call("pdm_fp_mlp_fused_pre", _native.stream(z), B, n, m, cs, z.data_ptr(), z.shape[2],
                  0 if skip_pm is None else skip_pm.data_ptr(), idx.data_ptr(), weight.data_ptr(), pk.nlayers,
-                 pk.dims_ptr, pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], pk.cout)
+                 pk.dims_c, pk.wpack.data_ptr(), pk.bias.data_ptr(), out_pm.data_ptr(), out_pm.shape[2], pk.cout)

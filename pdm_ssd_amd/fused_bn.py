@@ -123,13 +123,13 @@ class _BnRelu(Function):
         if stats is not None and layout == 0:
             # the producing GEMM left the column sums of x and x^2 (train_gemm.gemm_nt(..., stats=True)): no statistics pass
             assert stats.shape[1:] == (C, 2) and stats.dtype == torch.float32 and stats.is_contiguous()
-            _native.call("pdm_bn_relu_forward_stats", torch.cuda.current_stream(x.device).cuda_stream, dtype, n, C, x.data_ptr(),
+            _native.call("pdm_bn_relu_forward_stats", _native.stream(x.device), dtype, n, C, x.data_ptr(),
                          y.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
                          0 if running_mean is None else running_mean.data_ptr(), 0 if running_var is None else running_var.data_ptr(),
                          coef.data_ptr(), stats.data_ptr(), stats.shape[0], int(relu))
         else:
             partial = torch.empty((parts, C, 2), dtype=torch.float32, device=x.device)
-            _native.call("pdm_bn_relu_forward", torch.cuda.current_stream(x.device).cuda_stream, dtype, layout, n, C, L, x.data_ptr(),
+            _native.call("pdm_bn_relu_forward", _native.stream(x.device), dtype, layout, n, C, L, x.data_ptr(),
                          y.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
                          0 if running_mean is None else running_mean.data_ptr(), 0 if running_var is None else running_var.data_ptr(),
                          coef.data_ptr(), partial.data_ptr(), int(relu))
@@ -147,7 +147,7 @@ class _BnRelu(Function):
             dy = torch.empty_like(x, dtype=want).copy_(dy)       # the operator's gradient type, x's memory format
         grads = torch.empty((4, C), dtype=torch.float32, device=x.device)
         partial = torch.empty((parts, C, 2), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        stream = _native.stream(x.device)
         if ctx.link is not None and LAZY_BN_BACKWARD and dtype == 1 and layout == 0 and relu:
             # x came straight from a rows GEMM node: only the gradient statistics are taken here; that node's data gradient
             # forms dx while it reads dy and x (see _take_lazy_bn_backward — the same hand-over _BnReluRowsGemm uses)
@@ -183,14 +183,14 @@ class _BnReluPool(Function):
             # the contraction that produced x left the column sums AND every group's extremes in its epilogue (pdm_tg_gemm_nt_pool):
             # no statistics pass over x (POOL_IN_GEMM)
             assert dtype == 1 and keep.shape == (2, G, C) and idx.shape == (2, G, C) and stats.shape[1:] == (C, 2)
-            _native.call("pdm_bn_relu_pool_forward_kept", torch.cuda.current_stream(dev).cuda_stream, 1, G, ns, C, y.data_ptr(), keep[0].data_ptr(),
+            _native.call("pdm_bn_relu_pool_forward_kept", _native.stream(dev), 1, G, ns, C, y.data_ptr(), keep[0].data_ptr(),
                          keep[1].data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum), running_mean.data_ptr(),
                          running_var.data_ptr(), coef.data_ptr(), stats.data_ptr(), stats.shape[0], 1)
         else:
             keep = torch.empty((2, G, C), dtype=x.dtype, device=dev)
             idx = torch.empty((2, G, C), dtype=torch.uint8, device=dev)
             partial = torch.empty((parts, C, 2), dtype=torch.float32, device=dev)
-            _native.call("pdm_bn_relu_pool_forward", torch.cuda.current_stream(dev).cuda_stream, dtype, G, ns, C, x.data_ptr(), y.data_ptr(),
+            _native.call("pdm_bn_relu_pool_forward", _native.stream(dev), dtype, G, ns, C, x.data_ptr(), y.data_ptr(),
                          keep[0].data_ptr(), keep[1].data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), weight.data_ptr(), bias.data_ptr(),
                          float(eps), float(momentum), running_mean.data_ptr(), running_var.data_ptr(), coef.data_ptr(),
                          partial.data_ptr(), 1)
@@ -207,7 +207,7 @@ class _BnReluPool(Function):
         dx = torch.empty_like(x)
         grads = torch.empty((4, C), dtype=torch.float32, device=x.device)
         partial = torch.empty((parts, C, 2), dtype=torch.float32, device=x.device)
-        _native.call("pdm_bn_relu_pool_backward", torch.cuda.current_stream(x.device).cuda_stream, dtype, G, ns, C, x.data_ptr(),
+        _native.call("pdm_bn_relu_pool_backward", _native.stream(x.device), dtype, G, ns, C, x.data_ptr(),
                      dyp.data_ptr(), dx.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(),
                      coef.data_ptr(), grads.data_ptr(), partial.data_ptr(), 1)
         return dx, grads[0], grads[1], None, None, None, None, None, None, None
@@ -312,7 +312,7 @@ def _bn_relu_backward_rows(in_link, xr, coef, grads, da):
         return da
     R, K = xr.shape
     dx = torch.empty_like(xr)
-    _native.call("pdm_bn_relu_backward_apply", torch.cuda.current_stream(da.device).cuda_stream, 1, 0, R, K, 1, xr.data_ptr(),
+    _native.call("pdm_bn_relu_backward_apply", _native.stream(da.device), 1, 0, R, K, 1, xr.data_ptr(),
                  da.data_ptr(), dx.data_ptr(), coef.data_ptr(), grads.data_ptr(), 1)
     return dx
 
@@ -412,7 +412,7 @@ def _act_rows_backward(ctx, dy, xr, coef, grads, weight, wt):
         else:
             grads = torch.empty((4, K), dtype=torch.float32, device=dy.device)
             scratch = torch.empty((_native.lib().pdm_bn_parts(0, R, K, 1), K, 2), dtype=torch.float32, device=dy.device)
-            _native.call("pdm_bn_relu_backward_stats", torch.cuda.current_stream(dy.device).cuda_stream, 1, 0, R, K, 1, xr.data_ptr(),
+            _native.call("pdm_bn_relu_backward_stats", _native.stream(dy.device), 1, 0, R, K, 1, xr.data_ptr(),
                          da.data_ptr(), coef.data_ptr(), grads.data_ptr(), scratch.data_ptr(), 1)
     dx = _bn_relu_backward_rows(ctx.in_link, xr, coef, grads, da)
     return _rows_to_layout(dx, None, K, xshape, xdim), grads, dw, db
@@ -482,11 +482,11 @@ class _BnReluRowsGemm(Function):
             # then BatchNorm + ReLU ride in this contraction's load path like anywhere else — no normalised tensor
             assert xr.stride(0) == K
             scratch = torch.empty((_native.lib().pdm_bn_parts(0, R, K, 1), K, 2), dtype=torch.float32, device=x.device)
-            _native.call("pdm_bn_forward_coef", torch.cuda.current_stream(x.device).cuda_stream, 1, R, K, xr.data_ptr(), gamma.data_ptr(),
+            _native.call("pdm_bn_forward_coef", _native.stream(x.device), 1, R, K, xr.data_ptr(), gamma.data_ptr(),
                          beta.data_ptr(), float(eps), float(momentum), running_mean.data_ptr(), running_var.data_ptr(), coef.data_ptr(),
                          scratch.data_ptr())
         else:
-            _native.call("pdm_bn_finalize_stats", torch.cuda.current_stream(x.device).cuda_stream, R, K, gamma.data_ptr(), beta.data_ptr(),
+            _native.call("pdm_bn_finalize_stats", _native.stream(x.device), R, K, gamma.data_ptr(), beta.data_ptr(),
                          float(eps), float(momentum), running_mean.data_ptr(), running_var.data_ptr(), coef.data_ptr(), stats.data_ptr(),
                          stats.shape[0])
         out, st, wt = _rows_forward(ctx, x, xr, weight, bias, coef, want_stats, keep_pad, pool_ns, out_link)

@@ -35,10 +35,10 @@ class _PointHeadLoss(Function):
         dbox = torch.empty((N, 8), dtype=box_preds.dtype, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
         cw = (ctypes.c_float * 8)(*[float(v) for v in code_w])
-        _native.call("pdm_point_head_loss", torch.cuda.current_stream(dev).cuda_stream, N, n_per_sample, gt_boxes.shape[1], C,
+        _native.call("pdm_point_head_loss", _native.stream(dev), N, n_per_sample, gt_boxes.shape[1], C,
                      mean_size.shape[0], 1 if cls_preds.dtype == torch.bfloat16 else 0, cls_preds.data_ptr(), cls_preds.stride(0),
                      box_preds.data_ptr(), box_preds.stride(0), xyz_rows.data_ptr(), xyz_rows.stride(0), box_idx.data_ptr(),
-                     ext_idx.data_ptr(), gt_boxes.data_ptr(), mean_size.data_ptr(), ctypes.cast(cw, ctypes.c_void_p), beta, alpha, gamma,
+                     ext_idx.data_ptr(), gt_boxes.data_ptr(), mean_size.data_ptr(), cw, beta, alpha, gamma,
                      cls_w, box_w, labels.data_ptr(), dcls.data_ptr(), dbox.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes)
         ctx.save_for_backward(dcls, dbox)
         ctx.mark_non_differentiable(labels)

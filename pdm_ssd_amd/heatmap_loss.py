@@ -17,7 +17,7 @@ def heatmap_targets(gt_boxes, num_class, H, W, x0, y0, vx, vy, stride, min_overl
     gt = gt_boxes.detach().float().contiguous()
     B, M, _ = gt.shape
     hm = torch.empty((B, num_class, H, W), dtype=torch.float32, device=gt.device)
-    _native.call("pdm_heatmap_targets", torch.cuda.current_stream(gt.device).cuda_stream, B, M, num_class, H, W, gt.data_ptr(),
+    _native.call("pdm_heatmap_targets", _native.stream(gt.device), B, M, num_class, H, W, gt.data_ptr(),
                  float(x0), float(y0), float(vx), float(vy), float(stride), float(min_overlap), int(min_radius), int(max_radius), hm.data_ptr())
     return hm
 
@@ -36,7 +36,7 @@ class _HeatmapFocalLoss(Function):
         dl = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
         sb, sc, sh, sw = logits.stride()
-        _native.call("pdm_heatmap_focal_loss", torch.cuda.current_stream(dev).cuda_stream, B, C, H, W, logits.data_ptr(),
+        _native.call("pdm_heatmap_focal_loss", _native.stream(dev), B, C, H, W, logits.data_ptr(),
                      1 if logits.dtype == torch.bfloat16 else 0, sb, sc, sh, sw, heatmap.data_ptr(), float(weight), dl.data_ptr(),
                      out.data_ptr(), ws.data_ptr(), nbytes)
         ctx.save_for_backward(dl, out)

@@ -57,7 +57,7 @@ def sample_points_batch(raw, counts, num_points, seed=0, host_counts=None, retur
                 raise ValueError(f"a cloud of {n} points cannot be padded to {num_points} without replacement")
     out = torch.empty((B * num_points, 1 + C), dtype=torch.float32, device=raw.device)
     choice = torch.empty((B * num_points,), dtype=torch.int32, device=raw.device) if return_choice else None
-    _native.call("pdm_sample_points", torch.cuda.current_stream(raw.device).cuda_stream, B, int(num_points),
+    _native.call("pdm_sample_points", _native.stream(raw.device), B, int(num_points),
                  int(seed) & 0xffffffff, C, raw.data_ptr(), counts.data_ptr(), out.data_ptr(),
                  0 if choice is None else choice.data_ptr())
     return (out, choice) if return_choice else out

@@ -15,14 +15,10 @@ def _boxes(name, t):
     return t.float().contiguous()
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _pairwise(entry, boxes_a, boxes_b):
     a, b = _boxes("boxes_a", boxes_a), _boxes("boxes_b", boxes_b)
     out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    _native.call(entry, _stream(a), a.shape[0], a.data_ptr(), b.shape[0], b.data_ptr(), out.data_ptr())
+    _native.call(entry, _native.stream(a), a.shape[0], a.data_ptr(), b.shape[0], b.data_ptr(), out.data_ptr())
     return out
 
 
@@ -60,7 +56,7 @@ def _aligned_overlap(boxes_a, boxes_b):
     a, b = _boxes("boxes_a", boxes_a), _boxes("boxes_b", boxes_b)
     assert a.shape[0] == b.shape[0], "aligned IoU needs two box lists of the same length"
     out = torch.zeros((a.shape[0], 1), dtype=torch.float32, device=a.device)
-    _native.call("pdm_boxes_aligned_overlap_bev", _stream(a), a.shape[0], a.data_ptr(), b.data_ptr(), out.data_ptr())
+    _native.call("pdm_boxes_aligned_overlap_bev", _native.stream(a), a.shape[0], a.data_ptr(), b.data_ptr(), out.data_ptr())
     return a, b, out
 
 
@@ -87,7 +83,7 @@ def _nms(boxes, scores, thresh, pre_maxsize, normal):
     num = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
     nbytes = _native.lib().pdm_nms_workspace_bytes(n)
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=boxes.device)
-    _native.call("pdm_nms", _stream(boxes), n, sorted_boxes.data_ptr(), float(thresh), 1 if normal else 0, ws.data_ptr(),
+    _native.call("pdm_nms", _native.stream(boxes), n, sorted_boxes.data_ptr(), float(thresh), 1 if normal else 0, ws.data_ptr(),
                  nbytes, keep.data_ptr(), num.data_ptr())
     return order[keep[:int(num.item())]].contiguous(), None
 
@@ -110,7 +106,7 @@ def points_in_boxes_gpu(points, boxes):
     B, M, _ = points.shape
     pts, bxs = points.float().contiguous(), boxes.float().contiguous()
     out = torch.full((B, M), -1, dtype=torch.int32, device=points.device)
-    _native.call("pdm_points_in_boxes", _stream(points), B, boxes.shape[1], M, bxs.data_ptr(), pts.data_ptr(), out.data_ptr())
+    _native.call("pdm_points_in_boxes", _native.stream(points), B, boxes.shape[1], M, bxs.data_ptr(), pts.data_ptr(), out.data_ptr())
     return out
 
 

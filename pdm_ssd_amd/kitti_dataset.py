@@ -182,10 +182,6 @@ def _calib_of_info(info):
 
 # ---- device calls ------------------------------------------------------------------------------------------------------
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _check_frames(raw, counts, calib, shape):
     assert raw.is_cuda and raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2
     assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.dim() == 1
@@ -235,8 +231,8 @@ def fov_crop_padded(raw, counts, calib, image_shape, capacity_rows=None, out_row
            'overflow': torch.empty((1,), dtype=torch.int32, device=dev)}
     fl = torch.empty((max(raw.shape[0], 1),), dtype=torch.uint8, device=dev) if flags else None
     args = _frame_args(raw, counts, calib, image_shape) + (cap, out['counts'].data_ptr(), out['overflow'].data_ptr())
-    _native.call("pdm_kitti_data_fov_count", _stream(raw), *args, None if fl is None else fl.data_ptr(), ws.data_ptr(), ws.numel())
-    _native.call("pdm_kitti_data_fov_fill", _stream(raw), *args, rows.data_ptr(), ws.data_ptr(), ws.numel())
+    _native.call("pdm_kitti_data_fov_count", _native.stream(raw), *args, None if fl is None else fl.data_ptr(), ws.data_ptr(), ws.numel())
+    _native.call("pdm_kitti_data_fov_fill", _native.stream(raw), *args, rows.data_ptr(), ws.data_ptr(), ws.numel())
     out['rows'] = rows[:cap]
     if flags:
         out['flags'] = fl[:raw.shape[0]]
@@ -254,12 +250,12 @@ def fov_crop(raw, counts, calib, image_shape, workspace=None, flags=False):
     fl = torch.empty((max(raw.shape[0], 1),), dtype=torch.uint8, device=dev) if flags else None
     front = _frame_args(raw, counts, calib, image_shape)
     tail = (out['counts'].data_ptr(), out['overflow'].data_ptr())
-    _native.call("pdm_kitti_data_fov_count", _stream(raw), *front, 0, *tail, None if fl is None else fl.data_ptr(), ws.data_ptr(),
+    _native.call("pdm_kitti_data_fov_count", _native.stream(raw), *front, 0, *tail, None if fl is None else fl.data_ptr(), ws.data_ptr(),
                  ws.numel())
     host = out['counts'].cpu().tolist()
     total = sum(host)
     rows = torch.empty((max(total, 1), raw.shape[1]), dtype=torch.float32, device=dev)
-    _native.call("pdm_kitti_data_fov_fill", _stream(raw), *front, total, *tail, rows.data_ptr(), ws.data_ptr(), ws.numel())
+    _native.call("pdm_kitti_data_fov_fill", _native.stream(raw), *front, total, *tail, rows.data_ptr(), ws.data_ptr(), ws.numel())
     out['rows'] = rows[:total]
     out['host_counts'] = host
     out['overflow'].zero_()
@@ -307,7 +303,7 @@ class BoxMembership:
         self.num_points_in_gt = torch.empty((B, M), dtype=torch.int32, device=dev)
         self.db_count = torch.empty((B, M), dtype=torch.int32, device=dev)
         self.totals = torch.empty((2,), dtype=torch.int64, device=dev)
-        _native.call("pdm_kitti_data_boxes_count", _stream(raw), *self._args(), *self._outs(), self.ws.data_ptr(), self.ws.numel())
+        _native.call("pdm_kitti_data_boxes_count", _native.stream(raw), *self._args(), *self._outs(), self.ws.data_ptr(), self.ws.numel())
 
     def _args(self):
         return _frame_args(self.raw, self.counts, self.calib, self.shape) + (
@@ -327,7 +323,7 @@ class BoxMembership:
         offsets = torch.empty((N + 1,), dtype=torch.int64, device=dev)
         out_boxes = torch.empty((max(N, 1), 7), dtype=torch.float32, device=dev)
         a = self._args()
-        _native.call("pdm_kitti_data_boxes_fill", _stream(self.raw), *a, centres.data_ptr(), *self._outs(), P, N, points.data_ptr(),
+        _native.call("pdm_kitti_data_boxes_fill", _native.stream(self.raw), *a, centres.data_ptr(), *self._outs(), P, N, points.data_ptr(),
                      offsets.data_ptr(), out_boxes.data_ptr(), self.ws.data_ptr(), self.ws.numel())
         return points[:P], offsets, out_boxes[:N]
 

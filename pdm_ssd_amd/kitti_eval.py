@@ -133,7 +133,7 @@ def boxes_to_camera(boxes, count, V2C, R0, P2, image_shape=None):
     cam = torch.empty((B, P, 7), dtype=torch.float32, device=dev)
     img = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
     alpha = torch.empty((B, P), dtype=torch.float32, device=dev)
-    _native.call("pdm_kitti_boxes_to_camera", torch.cuda.current_stream(dev).cuda_stream, B, P, boxes.data_ptr(), count.data_ptr(),
+    _native.call("pdm_kitti_boxes_to_camera", _native.stream(dev), B, P, boxes.data_ptr(), count.data_ptr(),
                  V2C.data_ptr(), R0.data_ptr(), P2.data_ptr(), shp.data_ptr() if shp is not None else None, cam.data_ptr(),
                  img.data_ptr(), alpha.data_ptr())
     return cam, img, alpha
@@ -217,10 +217,6 @@ def _dt_to_device(pack, device):
             'cam': torch.from_numpy(np.ascontiguousarray(pack['cam'])).to(device)}
 
 
-def _iarr(values):
-    return (ctypes.c_int * max(len(values), 1))(*[int(v) for v in values])
-
-
 def _ptr(t):
     return t.data_ptr() if t is not None and t.numel() > 0 else None
 
@@ -254,7 +250,7 @@ def evaluate_device(gt, dt, classes, difficulties, metrics, min_overlaps, comput
     assert min_overlaps.shape == (K, 3, nC)
     ncombo = nM * nC * nD * K
     dev = dt['bbox'].device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _native.stream(dev)
     stats = stats if stats is not None else {}
     stats.setdefault('launches', 0)
     stats.setdefault('reads', 0)
@@ -310,19 +306,19 @@ def evaluate_device(gt, dt, classes, difficulties, metrics, min_overlaps, comput
     else:
         ws = workspace
         assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nbytes
-    c_metrics, c_classes, c_diffs = _iarr(metrics), _iarr(classes), _iarr(difficulties)
+    c_metrics, c_classes, c_diffs = (_native.host_array(ctypes.c_int, v) for v in (metrics, classes, difficulties))
     _stage(stats, 'host flags + upload', dev)
     off_g, off_d, off_o = d_offs[0].data_ptr(), d_offs[1].data_ptr(), d_offs[2].data_ptr()
 
-    _native.call("pdm_kitti_eval_overlaps", stream, F, off_g, off_d, off_o, NP, nM, ctypes.cast(c_metrics, ctypes.c_void_p),
+    _native.call("pdm_kitti_eval_overlaps", stream, F, off_g, off_d, off_o, NP, nM, c_metrics,
                  _ptr(g_bbox), _ptr(t_bbox), _ptr(g_cam), _ptr(t_cam), _ptr(overlaps))
     stats['launches'] += nM if F and NP else 0
     _stage(stats, 'overlaps', dev)
-    _native.call("pdm_kitti_eval_dt_flags", stream, ND, _ptr(t_bbox), _ptr(t_name), nC, ctypes.cast(c_classes, ctypes.c_void_p), nD,
-                 ctypes.cast(c_diffs, ctypes.c_void_p), _ptr(ign_dt))
+    _native.call("pdm_kitti_eval_dt_flags", stream, ND, _ptr(t_bbox), _ptr(t_name), nC, c_classes, nD,
+                 c_diffs, _ptr(ign_dt))
     stats['launches'] += 1 if ND else 0
     _stage(stats, 'detection flags', dev)
-    _native.call("pdm_kitti_eval_pass1", stream, F, off_g, off_d, off_o, max_dt, nM, ctypes.cast(c_metrics, ctypes.c_void_p), nC, nD, K,
+    _native.call("pdm_kitti_eval_pass1", stream, F, off_g, off_d, off_o, max_dt, nM, c_metrics, nC, nD, K,
                  _ptr(overlaps), NP, _ptr(d_ign_gt), NG, _ptr(ign_dt), ND, _ptr(t_score), d_mo.data_ptr(), d_slot.data_ptr(), SV,
                  _ptr(slab))
     stats['launches'] += 1 if F else 0
@@ -345,7 +341,7 @@ def evaluate_device(gt, dt, classes, difficulties, metrics, min_overlaps, comput
     aos_mask = 0
     if compute_aos:
         aos_mask = (1 << nM) - 1 if compute_aos is True else int(compute_aos)
-    _native.call("pdm_kitti_eval_pass2", stream, F, off_g, off_d, off_o, max_dt, nM, ctypes.cast(c_metrics, ctypes.c_void_p), nC, nD, K,
+    _native.call("pdm_kitti_eval_pass2", stream, F, off_g, off_d, off_o, max_dt, nM, c_metrics, nC, nD, K,
                  _ptr(overlaps), NP, _ptr(d_ign_gt), NG, _ptr(ign_dt), ND, _ptr(t_score), _ptr(g_alpha), _ptr(t_alpha), _ptr(g_bbox),
                  _ptr(t_bbox), _ptr(g_name), d_mo.data_ptr(), d_thr.data_ptr(), d_nthr.data_ptr(), aos_mask, ws.data_ptr(), nbytes,
                  sums.data_ptr())

@@ -28,10 +28,6 @@ class BevGrid:
         return [float(v) for v in (*self.origin, *self.cell, *self.inv_cell)]
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _chk(name, t, shape=None):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
         raise ValueError(f"{name} must be a contiguous fp32 GPU tensor")
@@ -59,7 +55,7 @@ class PDMScatter(Function):
         shape = (B, g.H, g.W, C * g.D) if layout == 1 else (B, C * g.D, g.H, g.W)
         grid = torch.zeros(shape, dtype=torch.float32, device=xyz.device)
         wsum = torch.zeros((B, g.H, g.W, g.D), dtype=torch.float32, device=xyz.device)
-        _native.call("pdm_scatter_bev", _stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(),
+        _native.call("pdm_scatter_bev", _native.stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(),
                      sh.data_ptr(), inv2s2.data_ptr(), *g.floats(), g.W, g.H, g.D, *kernel, layout,
                      grid.data_ptr(), wsum.data_ptr())
         ctx.save_for_backward(xyz, feat, sh, inv2s2)
@@ -81,7 +77,7 @@ class PDMScatter(Function):
         dfeat = torch.empty_like(feat)
         dsh = torch.empty_like(sh)
         dinv = torch.empty_like(inv2s2)
-        _native.call("pdm_scatter_bev_grad", _stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(),
+        _native.call("pdm_scatter_bev_grad", _native.stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(),
                      sh.data_ptr(), inv2s2.data_ptr(), *g.floats(), g.W, g.H, g.D, *kernel, layout,
                      dgrid.data_ptr(), dwsum_ptr, dfeat.data_ptr(), dsh.data_ptr(), dinv.data_ptr())
         return None, dfeat, dsh, dinv, None, None, None, None
@@ -96,7 +92,7 @@ def bev_normalize_(grid, wsum, C, grid_spec, layout=1, eps=1e-6):
     g = grid_spec
     _chk("grid", grid); _chk("wsum", wsum)
     B = grid.shape[0]
-    _native.call("pdm_bev_normalize", _stream(grid), B, C, g.W, g.H, g.D, layout, float(eps), grid.data_ptr(),
+    _native.call("pdm_bev_normalize", _native.stream(grid), B, C, g.W, g.H, g.D, layout, float(eps), grid.data_ptr(),
                  wsum.data_ptr())
     return grid
 
@@ -109,7 +105,7 @@ class BevNormalize(Function):
     def forward(ctx, grid, wsum, C, grid_spec, eps):
         g = grid_spec
         grid = grid.contiguous()
-        _native.call("pdm_bev_normalize", _stream(grid), grid.shape[0], C, g.W, g.H, g.D, 1, float(eps), grid.data_ptr(),
+        _native.call("pdm_bev_normalize", _native.stream(grid), grid.shape[0], C, g.W, g.H, g.D, 1, float(eps), grid.data_ptr(),
                      wsum.data_ptr())
         ctx.mark_dirty(grid)
         ctx.save_for_backward(grid, wsum)
@@ -123,7 +119,7 @@ class BevNormalize(Function):
         dy = dy.float().contiguous()
         dx = torch.empty_like(y)
         dw = torch.empty_like(wsum)
-        _native.call("pdm_bev_normalize_grad", _stream(y), y.shape[0], C, g.W, g.H, g.D, eps, y.data_ptr(), wsum.data_ptr(),
+        _native.call("pdm_bev_normalize_grad", _native.stream(y), y.shape[0], C, g.W, g.H, g.D, eps, y.data_ptr(), wsum.data_ptr(),
                      dy.data_ptr(), dx.data_ptr(), dw.data_ptr())
         return dx, dw, None, None, None
 
@@ -146,7 +142,7 @@ def pdm_gather(xyz, feat, sh, inv2s2, grid_spec, kernel, degree, normalize=True,
     wsum = torch.empty((B, g.H, g.W, g.D), dtype=torch.float32, device=xyz.device)
     nbytes = _native.lib().pdm_gather_bev_workspace_bytes(B, P, g.W, g.H, kernel[0], kernel[1])
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=xyz.device)
-    _native.call("pdm_gather_bev", _stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(), sh.data_ptr(),
+    _native.call("pdm_gather_bev", _native.stream(xyz), B, P, C, degree, xyz.data_ptr(), feat.data_ptr(), sh.data_ptr(),
                  inv2s2.data_ptr(), *g.floats(), g.W, g.H, g.D, *kernel, 1 if normalize else 0, float(eps),
                  grid.data_ptr(), wsum.data_ptr(), ws.data_ptr(), nbytes)
     return grid, wsum
@@ -180,7 +176,7 @@ class PDMGatherNormalized(Function):
         C = feat.shape[2]
         dy = dy.float().contiguous()
         dw = torch.empty_like(wsum)
-        s = _stream(y)
+        s = _native.stream(y)
         _native.call("pdm_bev_normalize_grad", s, B, C, g.W, g.H, g.D, eps, y.data_ptr(), wsum.data_ptr(), dy.data_ptr(),
                      0, dw.data_ptr())
         dfeat = torch.empty_like(feat)

@@ -37,9 +37,9 @@ def _run(fn, ref, *args):
     dev = ref.device
     if torch.cuda.current_device() != dev.index:
         with torch.cuda.device(dev):
-            _native.call(fn, torch.cuda.current_stream(dev).cuda_stream, *args)
+            _native.call(fn, _native.stream(dev), *args)
     else:
-        _native.call(fn, torch.cuda.current_stream(dev).cuda_stream, *args)
+        _native.call(fn, _native.stream(dev), *args)
 
 
 # Clouds at least this large go through the grid-accelerated kernel (identical indices); smaller ones
@@ -88,7 +88,7 @@ class _GridCache:
                 self.entries.clear()
 
     def get(self, pts, b, n, radius_hint):
-        stream = torch.cuda.current_stream(pts.device).cuda_stream
+        stream = _native.stream(pts.device)
         if self.depth > 0:
             for e in self.entries:
                 if (e[0]() is pts and e[1] == pts._version and e[2] == pts.data_ptr() and e[3] == b and e[4] == n

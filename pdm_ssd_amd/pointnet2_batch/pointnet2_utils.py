@@ -72,16 +72,12 @@ def fps_segments(jobs, npoint):
         assert xyz.shape == (B, N, 3) and temp.shape == (B, N) and idx.shape == (B, npoint)
         assert xyz.dtype == torch.float32 and temp.dtype == torch.float32 and idx.dtype == torch.int32
     n = len(jobs)
-    P = ctypes.c_void_p * n
-    I = ctypes.c_int * n
     ws_bytes = _native.lib().pdm_furthest_point_sampling_ws_bytes(B, N)   # 0 unless N > 16384 (cooperating workgroups)
     ws = [torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=jobs[0][0].device) for _ in jobs] if ws_bytes else []
-    _native.call("pdm_furthest_point_sampling_jobs", torch.cuda.current_stream(jobs[0][0].device).cuda_stream, n, B, N,
-                 npoint, ctypes.cast(P(*[j[0].data_ptr() for j in jobs]), ctypes.c_void_p),
-                 ctypes.cast(P(*[j[1].data_ptr() for j in jobs]), ctypes.c_void_p),
-                 ctypes.cast(P(*[j[2].data_ptr() for j in jobs]), ctypes.c_void_p),
-                 ctypes.cast(I(*[j[3] for j in jobs]), ctypes.c_void_p), ctypes.cast(I(*[j[4] for j in jobs]), ctypes.c_void_p),
-                 ctypes.cast(P(*[w.data_ptr() for w in ws]), ctypes.c_void_p) if ws else None, ws_bytes)
+    _native.call("pdm_furthest_point_sampling_jobs", _native.stream(jobs[0][0].device), n, B, N,
+                 npoint, *[_native.host_array(ctypes.c_void_p, [j[k].data_ptr() for j in jobs]) for k in range(3)],
+                 *[_native.host_array(ctypes.c_int, [j[k] for j in jobs]) for k in (3, 4)],
+                 _native.host_array(ctypes.c_void_p, [w.data_ptr() for w in ws]) if ws else None, ws_bytes)
     for w in ws:   # cooperating workgroups wait for each other with bounded spins: a give-up raises (deferred check)
         _native.fps_watch(w, B, N)
     return ws      # during graph capture the caller keeps these and checks them with _native.fps_check_workspace
@@ -96,7 +92,7 @@ def topk_sample(scores: torch.Tensor, npoint: int) -> torch.Tensor:
     scores = scores.detach().float().contiguous()
     B, N = scores.shape
     idx = torch.empty((B, npoint), dtype=torch.int32, device=scores.device)
-    _native.call("pdm_topk_sampling", torch.cuda.current_stream(scores.device).cuda_stream, B, N, int(npoint),
+    _native.call("pdm_topk_sampling", _native.stream(scores.device), B, N, int(npoint),
                  scores.data_ptr(), idx.data_ptr())
     return idx
 
@@ -222,7 +218,7 @@ class InterpConcatRows(Function):
         skip = None if skip_rows is None else skip_rows.contiguous()
         assert known_rows.dtype in (torch.float32, torch.bfloat16) and (skip is None or skip.dtype in (torch.float32, torch.bfloat16))
         out = torch.empty((B, n, ld), dtype=torch.bfloat16, device=known_rows.device)
-        _native.call("pdm_interp_concat_rows", torch.cuda.current_stream(out.device).cuda_stream, B, n, m, C2, C1, ld,
+        _native.call("pdm_interp_concat_rows", _native.stream(out.device), B, n, m, C2, C1, ld,
                      known_rows.data_ptr(), 1 if known_rows.dtype == torch.bfloat16 else 0,
                      0 if skip is None else skip.data_ptr(), 0 if skip is None or skip.dtype != torch.bfloat16 else 1,
                      idx.data_ptr(), weight.data_ptr(), out.data_ptr())
@@ -245,7 +241,7 @@ class InterpConcatRows(Function):
             dknown = torch.empty((B, m, C2), dtype=torch.bfloat16 if ob else torch.float32, device=g.device)
             nbytes = _native.lib().pdm_three_interpolate_grad_ws_bytes(B, n, m)
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
-            _native.call("pdm_interp_concat_rows_grad_out", torch.cuda.current_stream(g.device).cuda_stream, B, n, m, C2, ld, rows.data_ptr(),
+            _native.call("pdm_interp_concat_rows_grad_out", _native.stream(g.device), B, n, m, C2, ld, rows.data_ptr(),
                          idx.data_ptr(), weight.data_ptr(), dknown.data_ptr(), 1 if ob else 0, ws.data_ptr(), nbytes)
             if not ob and kdtype != torch.float32:
                 dknown = dknown.to(kdtype)
@@ -376,7 +372,7 @@ class _FusedQueryAndGroupCL(Function):
             features = features.float()
         feat_pm = None if features is None else features.transpose(1, 2).contiguous()
         out = torch.empty((B, M, nsample, ld), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=xyz.device)
-        _native.call("pdm_group_concat_cl_ld_f", torch.cuda.current_stream(xyz.device).cuda_stream, B, N, M, C, nsample,
+        _native.call("pdm_group_concat_cl_ld_f", _native.stream(xyz.device), B, N, M, C, nsample,
                      xyz.data_ptr(), new_xyz.data_ptr(), 0 if feat_pm is None else feat_pm.data_ptr(), 1 if feat_bf16 else 0, idx.data_ptr(),
                      out.data_ptr(), 1 if out_bf16 else 0, ld)
         ctx.for_backwards = (idx, N, C, ld)
@@ -401,7 +397,7 @@ class _FusedQueryAndGroupCL(Function):
         grad_pm = torch.empty((B, N, C), dtype=torch.float32, device=grad_out.device)
         nbytes = _native.lib().pdm_group_concat_cl_grad_ws_bytes(B, N, M, ns)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=grad_out.device)
-        _native.call("pdm_group_concat_cl_grad_ld", torch.cuda.current_stream(grad_out.device).cuda_stream, B, N, M, C, ns,
+        _native.call("pdm_group_concat_cl_grad_ld", _native.stream(grad_out.device), B, N, M, C, ns,
                      g.data_ptr(), 1 if g.dtype == torch.bfloat16 else 0, ld, idx.data_ptr(), grad_pm.data_ptr(), ws.data_ptr(), nbytes)
         # (B, C, N) view of point-major storage: the source features of the training path are themselves such views
         return None, None, None, None, grad_pm.transpose(1, 2), None, None

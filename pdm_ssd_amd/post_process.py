@@ -91,14 +91,14 @@ def post_process_padded(batch_dict, post_cfg, num_class, gt_boxes=None, workspac
     else:
         ws = workspace
         assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nbytes
-    tarr = (ctypes.c_float * max(len(thresholds), 1))(*thresholds)
+    tarr = _native.host_array(ctypes.c_float, thresholds)
     score_thresh = _get(post_cfg, 'SCORE_THRESH', None)
-    _native.call("pdm_post_process", torch.cuda.current_stream(dev).cuda_stream, B, C, 1 if multi else 0, probs.shape[0],
+    _native.call("pdm_post_process", _native.stream(dev), B, C, 1 if multi else 0, probs.shape[0],
                  probs.data_ptr(), probs.stride(0), boxes.data_ptr(), boxes.stride(0), offsets.data_ptr(),
                  bif.data_ptr() if bif is not None else None,
                  float('-inf') if score_thresh is None else float(score_thresh), pre, post,
                  float(_get(nms_cfg, 'NMS_THRESH')), normal, G, gdim, gt.data_ptr() if gt is not None else None,
-                 len(thresholds), ctypes.cast(tarr, ctypes.c_void_p), ws.data_ptr(), nbytes, out['rows'].data_ptr(),
+                 len(thresholds), tarr, ws.data_ptr(), nbytes, out['rows'].data_ptr(),
                  out['boxes'].data_ptr(), out['scores'].data_ptr(), out['labels'].data_ptr(), out['count'].data_ptr(),
                  out['error'].data_ptr(), out['recall'].data_ptr() if out['recall'] is not None else None)
     return out

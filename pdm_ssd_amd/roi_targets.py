@@ -49,7 +49,7 @@ def proposal_targets(rois, roi_scores, roi_labels, gt_boxes, roi_per_image, fg_p
            'rcnn_cls_labels': torch.empty((B, S), dtype=torch.int64 if cls_score_type == 'cls' else torch.float32, device=dev),
            'sampled_inds': torch.empty((B, S), dtype=torch.int32, device=dev),
            'gt_assignment': torch.empty((B, S), dtype=torch.int32, device=dev)}
-    _native.call('pdm_proposal_targets', torch.cuda.current_stream(dev).cuda_stream, B, R, M, S, rois.data_ptr(),
+    _native.call('pdm_proposal_targets', _native.stream(dev), B, R, M, S, rois.data_ptr(),
                  roi_scores.data_ptr(), roi_labels.data_ptr(), gt_boxes.data_ptr(), 1 if by_class else 0, int(fg_per_image),
                  float(hard_bg_ratio), float(reg_fg_thresh), float(cls_fg_thresh), float(cls_bg_thresh), float(cls_bg_thresh_lo),
                  0 if cls_score_type == 'cls' else 1, int(seed) & 0xFFFFFFFF, state.data_ptr(), out['rois'].data_ptr(),
@@ -83,9 +83,9 @@ class _RCNNLoss(Function):
         dcorner = torch.empty((n, 7), dtype=torch.float32, device=dev)
         outs = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(4)]
         cw = (ctypes.c_float * 7)(*[float(v) for v in code_w])
-        _native.call('pdm_rcnn_loss', torch.cuda.current_stream(dev).cuda_stream, n, cls_c.data_ptr(), reg_c.data_ptr(), rois.data_ptr(),
+        _native.call('pdm_rcnn_loss', _native.stream(dev), n, cls_c.data_ptr(), reg_c.data_ptr(), rois.data_ptr(),
                      gt_of_rois.data_ptr(), gt_of_rois_src.data_ptr(), reg_valid_mask.data_ptr(), cls_labels.data_ptr(),
-                     1 if cls_labels.dtype == torch.float32 else 0, ctypes.cast(cw, ctypes.c_void_p), beta, w_cls, w_reg, w_corner,
+                     1 if cls_labels.dtype == torch.float32 else 0, cw, beta, w_cls, w_reg, w_corner,
                      1 if use_corner else 0, dcls.data_ptr(), dreg.data_ptr(), dcorner.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),
                      outs[2].data_ptr(), outs[3].data_ptr(), ws.data_ptr(), nbytes)
         ctx.save_for_backward(dcls, dreg, dcorner)

@@ -11,10 +11,6 @@ from .. import _native
 from ..iou3d_nms.iou3d_nms_utils import points_in_boxes_gpu  # noqa: F401  (lives there; the reference exports it from here)
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _out_size(out_size):
     """an int (a cube) or three ints -> (out_x, out_y, out_z)"""
     dims = (out_size,) * 3 if isinstance(out_size, int) else tuple(out_size)
@@ -50,7 +46,7 @@ class RoIAwarePool3dFunction(Function):
         pool_method = {'max': 0, 'avg': 1}[pool_method]
         nbytes = _native.lib().pdm_roiaware_pool3d_workspace_bytes(num_rois, out_x, out_y, out_z)
         ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=feats.device)
-        _native.call("pdm_roiaware_pool3d_forward", _stream(feats), num_rois, num_pts, num_channels, int(max_pts_each_voxel), out_x,
+        _native.call("pdm_roiaware_pool3d_forward", _native.stream(feats), num_rois, num_pts, num_channels, int(max_pts_each_voxel), out_x,
                      out_y, out_z, rois.data_ptr(), pts.data_ptr(), feats.data_ptr(), pool_method, ws.data_ptr(), nbytes,
                      pts_idx_of_voxels.data_ptr(), argmax.data_ptr(), pooled_features.data_ptr())
         ctx.roiaware_pool3d_for_backward = (pts_idx_of_voxels, argmax, pool_method, num_pts, num_channels, rois, pts,
@@ -63,7 +59,7 @@ class RoIAwarePool3dFunction(Function):
         pts_idx_of_voxels, argmax, pool_method, num_pts, num_channels, rois, pts, out, max_pts = ctx.roiaware_pool3d_for_backward
         grad_out = grad_out.float().contiguous()
         grad_in = torch.empty((num_pts, num_channels), dtype=torch.float32, device=grad_out.device)   # fully written
-        _native.call("pdm_roiaware_pool3d_backward", _stream(grad_out), rois.shape[0], num_pts, num_channels, max_pts, out[0], out[1],
+        _native.call("pdm_roiaware_pool3d_backward", _native.stream(grad_out), rois.shape[0], num_pts, num_channels, max_pts, out[0], out[1],
                      out[2], rois.data_ptr(), pts.data_ptr(), pts_idx_of_voxels.data_ptr(), argmax.data_ptr(), grad_out.data_ptr(),
                      pool_method, grad_in.data_ptr())
         return None, None, grad_in, None, None, None

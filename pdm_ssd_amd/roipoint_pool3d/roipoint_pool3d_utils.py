@@ -19,10 +19,6 @@ def _extra_width(pool_extra_width):
     return ew
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _check(points, point_features, boxes3d):
     assert points.dim() == 3 and points.shape[2] == 3
     assert boxes3d.dim() == 3 and boxes3d.shape[0] == points.shape[0] and boxes3d.shape[2] >= 7
@@ -58,7 +54,7 @@ class RoIPointPool3dFunction(Function):
         pooled_empty_flag = torch.zeros((B, M), dtype=torch.int32, device=points.device)
         if N == 0:      # no point to test: every box is empty (the entry point writes nothing for a zero size)
             pooled_empty_flag.fill_(1)
-        _native.call("pdm_roipoint_pool3d", _stream(points), B, N, M, C, S, points.data_ptr(), enlarged.data_ptr(),
+        _native.call("pdm_roipoint_pool3d", _native.stream(points), B, N, M, C, S, points.data_ptr(), enlarged.data_ptr(),
                      point_features.data_ptr(), pooled_features.data_ptr(), pooled_empty_flag.data_ptr())
         ctx.mark_non_differentiable(pooled_empty_flag)
         return pooled_features, pooled_empty_flag
@@ -82,6 +78,6 @@ def roipoint_pool3d_canonical(points, point_features, rois, pool_extra_width, nu
     if N == 0:          # nothing to test: every RoI is empty (the entry point writes nothing for a zero size)
         pooled.zero_()
         flag.fill_(1)
-    _native.call("pdm_roipoint_pool3d_canonical", _stream(points), B, N, M, C, int(num_sampled_points), points.data_ptr(),
+    _native.call("pdm_roipoint_pool3d_canonical", _native.stream(points), B, N, M, C, int(num_sampled_points), points.data_ptr(),
                  rois.data_ptr(), rois.shape[2], ew[0], ew[1], ew[2], point_features.data_ptr(), pooled.data_ptr(), flag.data_ptr())
     return pooled, flag

@@ -9,10 +9,6 @@ import torch
 from . import _native
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def usable(rows, k, n):
     """shapes the kernels take: channel counts multiples of 8 (16-byte rows)"""
     return rows > 0 and k > 0 and n > 0 and k % 8 == 0 and n % 8 == 0
@@ -39,7 +35,7 @@ def pack_weight(w, transposed=False, pad_to=None):
     inner = N if transposed else K
     ld = (inner + 7) // 8 * 8 if pad_to is None else pad_to
     out = torch.empty((K if transposed else N, ld), dtype=torch.bfloat16, device=w.device)
-    _native.call("pdm_tg_pack_weight", _stream(w), N, K, w.data_ptr(), 0 if transposed else out.data_ptr(), 0 if transposed else ld,
+    _native.call("pdm_tg_pack_weight", _native.stream(w), N, K, w.data_ptr(), 0 if transposed else out.data_ptr(), 0 if transposed else ld,
                  out.data_ptr() if transposed else 0, ld if transposed else 0)
     return out
 
@@ -53,7 +49,7 @@ def pack_weight_into(w, out, transposed=False):
     assert out.shape[0] >= (K if transposed else N) and out.shape[1] >= (N if transposed else K)
     ld = out.stride(0)
     # the kernel writes ld columns per row: rows of the block are rewritten whole (pad columns zero)
-    _native.call("pdm_tg_pack_weight", _stream(w), N, K, w.data_ptr(), 0 if transposed else out.data_ptr(), 0 if transposed else ld,
+    _native.call("pdm_tg_pack_weight", _native.stream(w), N, K, w.data_ptr(), 0 if transposed else out.data_ptr(), 0 if transposed else ld,
                  out.data_ptr() if transposed else 0, ld if transposed else 0)
     return out
 
@@ -63,7 +59,7 @@ def _pack_weight_pair_now(w, rows_to, cols_to, buf=None):
     if buf is None:
         buf = torch.empty((2, rows_to * cols_to), dtype=torch.bfloat16, device=w.device)     # the kernel writes the padding too
     wb, wt = buf[0].view(rows_to, cols_to), buf[1].view(cols_to, rows_to)
-    _native.call("pdm_tg_pack_weight_pair", _stream(w), N, K, w.data_ptr(), wb.data_ptr(), wt.data_ptr(), rows_to, cols_to)
+    _native.call("pdm_tg_pack_weight_pair", _native.stream(w), N, K, w.data_ptr(), wb.data_ptr(), wt.data_ptr(), rows_to, cols_to)
     return wb, wt
 
 
@@ -123,7 +119,7 @@ def _refresh_packs(dev_index, device):
         table = (host.to(device), len(live), first, keys)
         _pack_tables[dev_index] = table
     if table[1]:
-        _native.call("pdm_tg_pack_weight_many", torch.cuda.current_stream(device).cuda_stream, table[1], table[0].data_ptr(), table[2])
+        _native.call("pdm_tg_pack_weight_many", _native.stream(device), table[1], table[0].data_ptr(), table[2])
     for key, base, _ in live:
         _packs[key][2] = base._version
         _packs[key][3] = _opt_epoch[0]
@@ -180,7 +176,7 @@ def gemm_nt_bs(x, w, bx, bcoef):
     assert bx.shape == (R, N) and bx.stride(1) == 1 and bcoef.shape == (4, N) and bcoef.dtype == torch.float32 and bcoef.is_contiguous()
     y = torch.empty((R, N), dtype=torch.bfloat16, device=x.device)
     st = torch.empty((_native.lib().pdm_tg_stats_parts(R, N), N, 2), dtype=torch.float32, device=x.device)
-    _native.call("pdm_tg_gemm_nt_bs", _stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
+    _native.call("pdm_tg_gemm_nt_bs", _native.stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
                  bx.data_ptr(), bx.stride(0), bcoef.data_ptr(), st.data_ptr())
     return y, st
 
@@ -191,7 +187,7 @@ def bn_bwd_finalize(rows, coef, partial):
     C = coef.shape[1]
     assert partial.shape[1:] == (C, 2) and partial.dtype == torch.float32 and partial.is_contiguous()
     grads = torch.empty((4, C), dtype=torch.float32, device=coef.device)
-    _native.call("pdm_bn_finalize_bwd_stats", _stream(coef), rows, C, coef.data_ptr(), grads.data_ptr(), partial.data_ptr(), partial.shape[0])
+    _native.call("pdm_bn_finalize_bwd_stats", _native.stream(coef), rows, C, coef.data_ptr(), grads.data_ptr(), partial.data_ptr(), partial.shape[0])
     return grads
 
 
@@ -214,11 +210,11 @@ def gemm_nt(x, w, bias=None, stats=False, out=None, x_bn_coef=None, pool_ns=0):
         G = R // pool_ns
         keep = torch.empty((2, G, N), dtype=torch.bfloat16, device=x.device)
         idx = torch.empty((2, G, N), dtype=torch.uint8, device=x.device)
-        _native.call("pdm_tg_gemm_nt_pool", _stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
+        _native.call("pdm_tg_gemm_nt_pool", _native.stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
                      0 if bias is None else bias.data_ptr(), st.data_ptr(), 0 if x_bn_coef is None else x_bn_coef.data_ptr(), pool_ns,
                      keep[0].data_ptr(), keep[1].data_ptr(), idx[0].data_ptr(), idx[1].data_ptr())
         return y, st, (keep, idx)
-    _native.call("pdm_tg_gemm_nt", _stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
+    _native.call("pdm_tg_gemm_nt", _native.stream(x), R, K, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0),
                  0 if bias is None else bias.data_ptr(), 0 if st is None else st.data_ptr(),
                  0 if x_bn_coef is None else x_bn_coef.data_ptr())
     return (y, st) if stats else y
@@ -241,11 +237,11 @@ def gemm_nt_dy(dz, yp, coef, grads, w, bs=None):
         bx, bcoef = bs
         assert bx.shape == (R, N) and bx.dtype == torch.bfloat16 and bx.stride(1) == 1 and bcoef.shape == (4, N) and bcoef.is_contiguous()
         st = torch.empty((_native.lib().pdm_tg_dy_stats_parts(R, N), N, 2), dtype=torch.float32, device=dz.device)
-        _native.call("pdm_tg_gemm_nt_dy_bs", _stream(dz), R, K, N, dz.data_ptr(), dz.stride(0), yp.data_ptr(), yp.stride(0), w.data_ptr(),
+        _native.call("pdm_tg_gemm_nt_dy_bs", _native.stream(dz), R, K, N, dz.data_ptr(), dz.stride(0), yp.data_ptr(), yp.stride(0), w.data_ptr(),
                      w.stride(0), dx.data_ptr(), dx.stride(0), dy.data_ptr(), dy.stride(0), coef.data_ptr(), grads.data_ptr(),
                      bx.data_ptr(), bx.stride(0), bcoef.data_ptr(), st.data_ptr())
         return dx, dy, st
-    _native.call("pdm_tg_gemm_nt_dy", _stream(dz), R, K, N, dz.data_ptr(), dz.stride(0), yp.data_ptr(), yp.stride(0), w.data_ptr(),
+    _native.call("pdm_tg_gemm_nt_dy", _native.stream(dz), R, K, N, dz.data_ptr(), dz.stride(0), yp.data_ptr(), yp.stride(0), w.data_ptr(),
                  w.stride(0), dx.data_ptr(), dx.stride(0), dy.data_ptr(), dy.stride(0), coef.data_ptr(), grads.data_ptr())
     return dx, dy
 
@@ -258,7 +254,7 @@ def wgrad(dy, x, out=None, accumulate=False, x_bn_coef=None):
     dw = torch.empty((N, K), dtype=torch.float32, device=x.device) if out is None else out
     nbytes = _native.lib().pdm_tg_wgrad_ws_bytes(R, K, N)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
-    _native.call("pdm_tg_wgrad", _stream(x), R, K, N, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(),
+    _native.call("pdm_tg_wgrad", _native.stream(x), R, K, N, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(),
                  1 if accumulate else 0, ws.data_ptr(), nbytes, 0 if x_bn_coef is None else x_bn_coef.data_ptr())
     return dw
 
@@ -269,5 +265,5 @@ def colsum(y):
     assert y.dtype == torch.bfloat16 and y.stride(1) == 1 and N % 8 == 0 and N <= 512
     out = torch.empty((N,), dtype=torch.float32, device=y.device)
     ws = torch.empty((max(_native.lib().pdm_tg_colsum_ws_floats(R, N), 4),), dtype=torch.float32, device=y.device)
-    _native.call("pdm_tg_colsum", _stream(y), R, N, y.data_ptr(), y.stride(0), out.data_ptr(), ws.data_ptr())
+    _native.call("pdm_tg_colsum", _native.stream(y), R, N, y.data_ptr(), y.stride(0), out.data_ptr(), ws.data_ptr())
     return out

@@ -31,9 +31,10 @@ def test_library_loads_and_exports_every_declared_symbol():
     raw = ctypes.CDLL(_native.LIB_PATH)
     for name in declared_symbols():
         assert hasattr(raw, name), f"{name} declared in include/pdmssd_hip.h but not exported"
-    # and the Python binding table covers the header (tuning knobs are extra, undeclared on purpose)
+    # and the Python binding covers the header: it is derived from it, so "bound" means "declared"
     bound = set(_native.EXPORTS)
     assert set(declared_symbols()) <= bound, set(declared_symbols()) - bound
+    assert bound == set(declared_symbols()), bound - set(declared_symbols())
 
 
 def test_extension_module_mirrors_reference_function_table():
@@ -87,3 +88,94 @@ def test_new_entry_points_validate_their_arguments_before_any_launch():
         _native.call("pdm_point_head_loss", 0, 1000, 500, 4, 3, 3, 0, ptr, 3, ptr, 8, ptr, 4, ptr, ptr, ptr, ptr, ptr, 0.1, 0.25, 2.0, 1.0, 1.0,
                      ptr, ptr, ptr, ptr, ptr, 8)
 
+
+
+LITERAL_HEADER = """
+#ifndef X_H
+#define X_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PDM_E_BADARG (-1)   /* negative size (or a null pointer) */
+/* returns the text of the last error ( thread-local ) */
+const char *pdm_last_error(void);
+int pdm_abi_version(void);
+size_t pdm_ws_bytes(int n, long long rows);   // trailing comment with pdm_not_a_function(int)
+/* a comment with a call-like text: pdm_fake(int a,
+ * float b); and a parenthesis ( in it ) */
+int pdm_many(void *stream, int count, const float *const *src, void *const *dst, const size_t *bytes,
+             unsigned seed, unsigned int flags, long long n,
+             size_t ws_bytes, double overlap, float eps,
+             unsigned long long *slot, const unsigned long long total);
+int pdm_tune_knob(int);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_maps_every_type_of_the_header():
+    import ctypes as C
+
+    from pdm_ssd_amd import _native
+    got = _native.parse_header(LITERAL_HEADER)
+    assert got == {
+        "pdm_last_error": (C.c_char_p, []),
+        "pdm_abi_version": (C.c_int, []),
+        "pdm_ws_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
+        "pdm_many": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_longlong,
+                               C.c_size_t, C.c_double, C.c_float, C.c_void_p, C.c_ulonglong]),
+        "pdm_tune_knob": (C.c_int, [C.c_int]),
+    }
+
+
+@pytest.mark.parametrize("proto, words", [
+    ("int pdm_f(void *stream, short n);", ("pdm_f", "short n")),
+    ("int pdm_g(int n, struct box b);", ("pdm_g", "struct box b")),
+    ("float pdm_h(int n);", ("pdm_h", "float")),
+])
+def test_parser_refuses_a_type_it_does_not_know(proto, words):
+    from pdm_ssd_amd import _native
+    with pytest.raises(_native.NativeLibraryError) as e:
+        _native.parse_header(proto)
+    for w in words:
+        assert w in str(e.value)
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    from pdm_ssd_amd import _native
+    missing = str(tmp_path / "nope.h")
+    monkeypatch.setattr(_native, "_lib", None)
+    monkeypatch.setattr(_native, "_declared", None)
+    monkeypatch.setattr(_native, "HEADER_PATH", missing)
+    with pytest.raises(_native.NativeLibraryError, match="nope.h"):
+        _native.lib()
+
+
+def test_every_declared_function_is_bound_as_the_header_says():
+    from pdm_ssd_amd import _native
+    lib = _native.lib()
+    want = _native.parse_header(open(HEADER).read())
+    assert sorted(want) == declared_symbols() and len(want) >= 187
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert fn.argtypes is not None and len(fn.argtypes) == len(argtypes), name
+        assert list(fn.argtypes) == argtypes, name
+    assert os.path.samefile(_native.HEADER_PATH, HEADER)
+
+
+def test_every_extern_c_definition_is_declared():
+    """What catches the next entry point or tuning knob that is defined and called but missing from the header."""
+    csrc = os.path.join(ROOT, "pdm_ssd_amd", "csrc")
+    defined = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            defined |= set(re.findall(r'extern\s+"C"[^;{()]*?\b(pdm_[a-z0-9_]+)\s*\(', open(os.path.join(csrc, f)).read()))
+    from pdm_ssd_amd import _native
+    raw = ctypes.CDLL(_native.LIB_PATH)
+    defined = {n for n in defined if hasattr(raw, n)}      # (a definition inside an #if of a diagnostic build is not in the library)
+    assert len(defined) >= 187
+    assert defined <= set(declared_symbols()), sorted(defined - set(declared_symbols()))

@@ -19,6 +19,11 @@
  *     value an argument error (PDM_E_*).  Nothing here ever calls exit() (the reference does:
  *     ball_query_gpu.cu:68-72).  pdm_last_error() returns a thread-local message.
  *   - All tensors are contiguous; data is fp32, indices are int32; 64-bit offsets internally.
+ *   - Alignment (DESIGN.md 7p lists every pointer): a typed pointer needs the natural alignment of its element type; a
+ *     `void *workspace` that is not 8-byte aligned is rejected (PDM_E_BADARG) unless the entry rounds it up inside.  Beyond that an entry either HANDLES any offset and any size — it takes 16-byte accesses only
+ *     where the address and the sizes allow and an element path otherwise, with the same results — or REJECTS a pointer that is
+ *     not 16-byte aligned with PDM_E_BADARG before anything is launched.  "align: any" / "align: 16 B ..." on a declaration
+ *     says which; an entry without a note handles any offset (element accesses only).
  *   - No host synchronisation, allocation or memcpy inside any call: every entry point is
  *     hipGraph-capturable.
  */
@@ -43,11 +48,13 @@ const char *pdm_last_error(void);
 
 /* replaces ball_query_wrapper_fast            ball_query.cpp:29-39 -> ball_query_gpu.cu:15-73
  * new_xyz (B,M,3), xyz (B,N,3) -> idx (B,M,nsample), caller-zeroed. */
+/* align: any (xyz is staged 16 bytes at a time only when n % 4 == 0 and xyz is 16-byte aligned). */
 int pdm_ball_query(void *stream, int b, int n, int m, float radius, int nsample,
                    const float *new_xyz, const float *xyz, int *idx);
 
 /* replaces group_points_wrapper_fast          group_points.cpp:27-36 -> group_points_gpu.cu:53-92
  * points (B,C,N), idx (B,npoints,nsample) -> out (B,C,npoints,nsample). */
+/* align: any (16-byte forms need L = npoints * nsample % 4 == 0 and aligned points / idx / out). */
 int pdm_group_points(void *stream, int b, int c, int n, int npoints, int nsample,
                      const float *points, const int *idx, float *out);
 
@@ -59,6 +66,8 @@ int pdm_group_points_grad(void *stream, int b, int c, int n, int npoints, int ns
 /* QueryAndGroup's concat (pointnet2_utils.py:249-257) in channels-last memory for the training path: out (B, M, nsample,
  * 3+C) = an NHWC view of the reference's (B, 3+C, M, nsample) tensor, fp32 or (out_bf16 = 1) bf16 rounded to nearest even
  * from the fp32 value; feat_pm (B, N, C) point-major; idx (B, M, nsample) from pdm_ball_query. */
+/* align: any for the whole pdm_group_concat_cl* family (eight bf16 channels per store need ld % 8 == 0 and an aligned out; the
+ * backward reads 8-byte words when grad is bf16, ld % 8 == 0 and grad aligned), EXCEPT feat_bf16 = 1: out 16 B, ld % 8 == 0. */
 int pdm_group_concat_cl(void *stream, int b, int n, int m, int c, int nsample, const float *xyz, const float *new_xyz,
                         const float *feat_pm, const int *idx, void *out, int out_bf16);
 /* Its backward: grad (B, M, nsample, 3+C) fp32 or bf16 -> grad_feat_pm (B, N, C) fp32, fully written (the xyz channels carry
@@ -110,6 +119,7 @@ int pdm_furthest_point_sampling(void *stream, int b, int n, int m, const float *
  * pdm_furthest_point_sampling_status: *flag = 1 means the indices of that call must not be used. */
 size_t pdm_furthest_point_sampling_ws_bytes(int b, int n);
 int pdm_fps_max_coresident_workgroups(void);
+/* align: workspace 8 B (checked), as workspace[q] of pdm_furthest_point_sampling_jobs. */
 int pdm_furthest_point_sampling_ws(void *stream, int b, int n, int m, const float *points, float *temp,
                                    int *idx, void *workspace, size_t workspace_bytes);
 int pdm_furthest_point_sampling_status(void *stream, int b, int n, const void *workspace, int *flag);
@@ -153,6 +163,7 @@ int pdm_three_interpolate_grad_ws(void *stream, int b, int c, int n, int m, cons
  * idx = ball_query (written, caller need not zero it), out[:,0:3] = xyz[idx] - new_xyz,
  * out[:,3:3+C] = features[:, idx].  features (B,C,N) may be NULL when c == 0.
  * out is (B, 3+C, M, nsample). */
+/* align: any (idx cleared with byte head and tail; 16-byte forms need nsample % 4 == 0 and aligned idx / out). */
 int pdm_query_and_group(void *stream, int b, int n, int m, int c, float radius, int nsample,
                         const float *xyz, const float *new_xyz, const float *features, int *idx,
                         float *out);
@@ -162,6 +173,7 @@ int pdm_query_and_group(void *stream, int b, int n, int m, int c, float radius, 
  * ABI takes from the caller: `workspace` of at least pdm_ball_query_grid_workspace_bytes(b, n) bytes,
  * contents irrelevant before and after the call. */
 size_t pdm_ball_query_grid_workspace_bytes(int b, int n);
+/* align: any for the grid family (16-byte row stores need nsample % 4 == 0 and an aligned idx; workspaces are rounded up inside). */
 int pdm_ball_query_grid(void *stream, int b, int n, int m, float radius, int nsample,
                         const float *new_xyz, const float *xyz, int *idx, void *workspace,
                         size_t workspace_bytes);
@@ -190,6 +202,7 @@ int pdm_three_nn_weights(void *stream, long long rows, const float *dist2, float
 /* The gather half of the above for a given idx (B,M,nsample): grouped xyz minus centre, grouped
  * features, concatenated on the channel axis -> out (B, 3+C, M, nsample)
  * (pointnet2_utils.py:250-257: two grouping_operation calls, the in-place subtract and torch.cat). */
+/* align: any (as pdm_query_and_group). */
 int pdm_group_concat(void *stream, int b, int n, int m, int c, int nsample, const float *xyz,
                      const float *new_xyz, const float *features, const int *idx, float *out);
 
@@ -202,6 +215,7 @@ int pdm_group_concat(void *stream, int b, int n, int m, int c, int nsample, cons
  *
  * pdm_sa_mlp_fused == pointnet2_utils.py:250-257 (group xyz/features, subtract centre, cat) +
  *                     pointnet2_modules.py:40-52 (MLP, max_pool2d over nsample) for a given idx. */
+/* align: 16 B for wpack, bias, out_pm (out_stride, out_coff % 4 == 0) and for feat_pm when cin % 4 == 0; xyz, new_xyz, idx any. */
 int pdm_sa_mlp_fused(void *stream, int b, int n, int m, int cin, int nsample, const float *xyz,
                      const float *new_xyz, const float *feat_pm, const int *idx, int nlayers,
                      const int *dims, const float *wpack, const float *bias, float *out_pm,
@@ -209,6 +223,8 @@ int pdm_sa_mlp_fused(void *stream, int b, int n, int m, int cin, int nsample, co
 
 /* pdm_fp_mlp_fused == pointnet2_modules.py:158-170 (three_interpolate, cat with the skip features, MLP)
  * for given idx/weight (B,n,3): known_pm (B,m,c_known), skip_pm (B,n,c_skip) or NULL -> out_pm (B,n,out_stride). */
+/* align: 16 B for wpack, bias, out_pm (out_stride % 4 == 0), for known_pm when c_known % 4 == 0 and skip_pm when c_skip % 4 == 0;
+ * idx, weight any. */
 int pdm_fp_mlp_fused(void *stream, int b, int n, int m, int c_known, int c_skip,
                      const float *known_pm, const float *skip_pm, const int *idx, const float *weight,
                      int nlayers, const int *dims, const float *wpack, const float *bias,
@@ -217,6 +233,8 @@ int pdm_fp_mlp_fused(void *stream, int b, int n, int m, int c_known, int c_skip,
 /* Per-row MLP on fp32 MFMA: in_pm (rows, cin) -> out_pm (rows, out_stride), same dims/wpack/bias packing.
  * relu_last = 0 leaves the last layer linear.  Serves 1x1 convolutions over point-major rows and the
  * pre-projections below. */
+/* align: 16 B for wpack, bias, out_pm (out_stride % 4 == 0); in_pm 16 B when cin % 4 == 0 (the LDS-tiled GEMM form — one layer,
+ * >= 256 tiles of 128 x 128 — takes any in_pm), any otherwise. */
 int pdm_rows_mlp_fused(void *stream, int rows, int cin, const float *in_pm, int nlayers, const int *dims,
                        const float *wpack, const float *bias, int relu_last, float *out_pm, int out_stride,
                        int cout);
@@ -226,6 +244,7 @@ int pdm_rows_mlp_fused(void *stream, int rows, int cin, const float *in_pm, int 
  * (/root/reference/pcdet/models/dense_heads/point_head_box.py:7-60, forward :85-86).  One launch where an instantiation
  * exists (128 -> 256 -> 256 -> <= 16 over >= 8192 rows: the rows are read once), otherwise two pdm_rows_mlp_fused calls;
  * bit-identical outputs either way. */
+/* align: as pdm_rows_mlp_fused, for both stacks. */
 int pdm_rows_mlp_fused_pair(void *stream, int rows, int cin, const float *in_pm, int nlayers, const int *dims,
                             const float *wpack_a, const float *bias_a, const float *wpack_b, const float *bias_b,
                             int relu_last, float *out_a, int out_stride_a, int cout_a, float *out_b, int out_stride_b,
@@ -238,6 +257,7 @@ int pdm_rows_mlp_fused_pair(void *stream, int rows, int cin, const float *in_pm,
  * pdm_rows_mlp_fused_pair; out_pm receives the module's rows, out_a / out_b the stacks' outputs on them.  Bit-identical to the
  * two calls (FP through the register-resident chain kernel).  Shapes: <= 4 skip channels, dims {16, 128, 128}, hdims
  * {128, 256, 256, 16}, >= 32768 rows; PDM_E_BADARG otherwise (issue the two calls instead). */
+/* align: 16 B for z_pm, wpack, bias, out_pm, hw_*, hb_*, out_a, out_b (strides % 4 == 0); skip_pm, idx, weight any. */
 int pdm_fp_head_fused(void *stream, int b, int n, int m, int c_skip, const float *z_pm, int z_stride, const float *skip_pm,
                       const int *idx, const float *weight, const int *dims, const float *wpack, const float *bias,
                       float *out_pm, int out_stride, int cout, const int *hdims, const float *hw_a, const float *hb_a,
@@ -318,6 +338,7 @@ int pdm_center_reg_loss(void *stream, int B, int num_max_objs, int D, int H, int
  * v_mfma_f32_16x16x32_bf16 with fp32 accumulation (3/8 of the fp32-MFMA pipe time; dropped terms <= 2^-24 |a b|).
  * Only dims = {128, 256, 256, 16} (the point head's stacks, point_head_box.py:7-60); `wstream` = the pre-split weights in
  * consumption order (pdm_ssd_amd/fused.py::PackedMLPx3, pdm_rows_mlp_x3_stream_bytes bytes), bias fp32 padded. */
+/* align: 16 B for in_pm, wstream, bias, out_pm. */
 int pdm_rows_mlp_x3(void *stream, int rows, int cin, const float *in_pm, int nlayers, const int *dims, const void *wstream,
                     size_t wstream_bytes, const float *bias, int relu_last, float *out_pm, int out_stride, int cout);
 size_t pdm_rows_mlp_x3_stream_bytes(int nlayers, const int *dims);
@@ -330,6 +351,7 @@ int pdm_tune_rows_x3_wg_per_cu(int n);
  * z_pm rows hold the layer's padded C1 floats at [z_coff, z_coff + C1pad) of z_stride (pdm_rows_mlp_fused with
  * relu_last = 0 and zero bias); dims[0] is the padded width of what stays in the kernel (16 for xyz; the
  * padded skip width, or 16 with zero weights when c_skip == 0). */
+/* align: as pdm_sa_mlp_fused / pdm_fp_mlp_fused, and 16 B for z_pm (z_stride, z_coff % 4 == 0). */
 int pdm_sa_mlp_fused_pre(void *stream, int b, int n, int m, int nsample, const float *xyz,
                          const float *new_xyz, const float *z_pm, int z_stride, int z_coff, const int *idx,
                          int nlayers, const int *dims, const float *wpack, const float *bias, float *out_pm,
@@ -350,6 +372,8 @@ int pdm_fp_mlp_fused_pre(void *stream, int b, int n, int m, int c_skip, const fl
  *     bit-identical to the unpacked entry points. */
 size_t pdm_sa_pack_workspace_bytes(int b, int m);
 size_t pdm_sa_pack_rows(int b, int m, int nsample);
+/* align: idx 16 B (rows are read as int4), pack 8 B.  pdm_sa_mlp_packed and pdm_sa_mlp_packed_pair: pack 8 B and, as pdm_sa_mlp_fused /
+ * pdm_sa_mlp_fused_pre, 16 B for wpack, bias, out_pm, z_pm (strides and offsets % 4 == 0) and for feat_pm when cin % 4 == 0. */
 int pdm_sa_pack(void *stream, int b, int n, int m, int nsample, const int *idx, void *workspace,
                 size_t workspace_bytes, int *pack, int *meta);
 /* both scales of an MSG level in one count -> scan -> fill sequence (per-scale nsample / idx / workspace / pack / meta as HOST arrays
@@ -465,6 +489,7 @@ int pdm_stack_vector_pool_grad(void *stream, const float *grad_new_features, con
  *   [mean | invstd | gamma*invstd | beta] is what the backward needs besides x.
  * backward: dx (same type and layout as x), grads (4, C) fp32 = [dgamma | dbeta | p | q] (dx = gamma invstd (g - p - (x - mean) q)).
  * partial: workspace of pdm_bn_parts(layout, n, C, L) * C * 2 floats (slice sums, folded in double: reproducible). */
+/* align (every pdm_bn_* entry): 16 B for x, y, dy, dx, xmax, xmin, imax, imin, coef and grads; 8 B for partial. */
 int pdm_bn_parts(int layout, long long n, int C, long long L);
 int pdm_bn_relu_forward(void *stream, int dtype, int layout, long long n, int C, long long L, const void *x, void *y,
                         const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
@@ -517,6 +542,8 @@ int pdm_bn_relu_pool_backward(void *stream, int dtype, long long G, int ns, int 
  * Depthwise 3x3 convolution + folded BatchNorm + ReLU over the neck's channels-last BEV grid, the context stage of
  * the heat-map head (pdm_ssd_amd/dense_heads/pdm_heatmap_head.py); the point head's MLPs and the heat-map head's 1x1
  * stack run through pdm_rows_mlp_fused.  in / out (B, H, W, C) fp32, w (9, C) tap-major, shift (C); C % 4 == 0. */
+/* align: 16 B for every pointer of the pdm_bev_depthwise3x3* entries and of pdm_bev_head_fused; pdm_point_head_decode: code 16 B
+ * (code_stride % 4 == 0), the others any. */
 int pdm_bev_depthwise3x3(void *stream, int B, int H, int W, int C, const float *in, const float *w, const float *shift,
                          float *out, int relu);
 /* The heat-map head's inference stack in ONE launch: out[cell] = MLP(relu(depthwise3x3(map)[cell] + shift)), the
@@ -588,6 +615,7 @@ int pdm_points_in_boxes(void *stream, int B, int T, int M, const float *boxes, c
  * row k >= cnt repeats row k % cnt; a row is [x, y, z, feats...] copied bit for bit.  cnt == 0: flag 1 and the box's S rows
  * are NOT written (the caller zero-fills, as the reference's); every flag is written.  One launch, no (B,N,M) intermediate,
  * nothing allocated.  B, N, M or S == 0: success, nothing written. */
+/* align: any (rows are written with an element head up to a 16-byte boundary of the address). */
 int pdm_roipoint_pool3d(void *stream, int B, int N, int M, int C, int S, const float *xyz, const float *boxes, const float *feats,
                         float *pooled, int *empty_flag);
 /* The same with the PointRCNN head's epilogue (pcdet/models/roi_heads/pointrcnn_head.py:121-129) in the launch: rois
@@ -769,6 +797,7 @@ int pdm_kitti_eval_pass2(void *stream, int F, const int *gt_off, const int *dt_o
  * an entry; out_offsets (capacity_entries + 1) int64; out_boxes (N, 7).  Entries are ordered frame after frame, box after
  * box; a point inside two boxes goes to both.  Nothing is written at or past capacity_points rows / capacity_entries
  * entries.  workspace >= pdm_kitti_data_boxes_workspace_bytes(B, M), shared by boxes_count -> boxes_fill on one stream. */
+/* align: raw, out_rows, out_points 16 B when C == 4 (rows read / written as float4), any otherwise. */
 size_t pdm_kitti_data_fov_workspace_bytes(int B);
 size_t pdm_kitti_data_boxes_workspace_bytes(int B, int M);
 int pdm_kitti_data_fov_count(void *stream, int B, int C, long long total_rows, const float *raw, const int *counts,
@@ -794,6 +823,9 @@ int pdm_kitti_data_boxes_fill(void *stream, int B, int C, long long total_rows, 
  * element the fp32 value (pinned fma order of pdm_three_interpolate) rounded to nearest even.  known (B, m, C2) and skip
  * (B, n, C1) are point-major rows, fp32 or bf16.  Backward: dx (B, n, ld) bf16 -> dknown (B, m, C2) fp32 through an inverted
  * (CSR) index, no atomics; the skip gradient is dx[..., C2 : C2 + C1].  workspace: pdm_three_interpolate_grad_ws_bytes(b, n, m). */
+/* align: any (eight channels per thread need c2 % 8 == 0, ld % 8 == 0 and aligned known / out — dx / dknown in the backward —,
+ * the element form otherwise: the forward gives the same bits; the backward's sums are added in the order of lists whose entry
+ * order is not fixed between launches, so its last bits may differ from call to call in either form). */
 int pdm_interp_concat_rows(void *stream, int b, int n, int m, int c2, int c1, int ld, const void *known, int known_bf16,
                            const void *skip, int skip_bf16, const int *idx, const float *weight, void *out);
 int pdm_interp_concat_rows_grad(void *stream, int b, int n, int m, int c2, int ld, const void *dx, const int *idx,
@@ -811,6 +843,8 @@ int pdm_interp_concat_rows_grad_out(void *stream, int b, int n, int m, int c2, i
  * (pdm_tg_stats_parts(R, N), N, 2) fp32 = per persistent slot the column sums of y and y^2 of the ROUNDED outputs (BatchNorm
  * statistics without another pass over Y; pdm_bn_relu_forward_stats folds the parts).  The data gradient is the same call on
  * the transposed weights. */
+/* align (every pdm_tg_* contraction): 16 B for X, W, Y, dZ, Yp, dX, dYout, dY, Bx, xmax, xmin, coef, grads, bcoef, the x_bn_coef and
+ * workspace of pdm_tg_wgrad; 8 B for imax, imin; bias, stats, bstats, dW, out, scratch and the pack_weight buffers any. */
 int pdm_tg_stats_parts(long long rows, int N);
 /* x_bn_coef: null, or (4, K) fp32 [mean | invstd | gamma invstd | beta] from pdm_bn_finalize_stats: X holds the PRE-BatchNorm
  * outputs of the layer before and is read through bf16(relu((x - mean) scale + beta)) — that layer's BatchNorm + ReLU without
@@ -894,6 +928,7 @@ int pdm_tune_copy_max_wg(int n);       /* pdm_copy_many: grid cap in workgroups 
 
 /* count device-to-device copies dst[k] <- src[k] (bytes[k] each; host arrays) in one launch per 48 buffers.
  * Plumbing for the stream pipeline's hand-over buffers, not a reference operator. */
+/* align: any, per transfer (16-byte pieces only when source and destination are both 16-byte aligned, then a byte tail). */
 int pdm_copy_many(void *stream, int count, void *const *dst, const void *const *src, const size_t *bytes);
 /* The same with device-side lengths: where dyn_count[k] != NULL only the first *dyn_count[k] * dyn_unit[k] bytes of buffer
  * k are copied (the count is read when the kernel runs): worst-case-sized buffers with a device-computed number of
@@ -914,6 +949,7 @@ int pdm_scatter_bev(void *stream, int B, int P, int C, int degree, const float *
                     int H, int D, int kx, int ky, int kz, int layout, float *grid, float *wsum);
 
 /* grid[cell] /= wsum[cell] where |wsum| > eps */
+/* align: any (the float4 form needs layout 1, C * D % 4 == 0 and an aligned grid). */
 int pdm_bev_normalize(void *stream, int B, int C, int W, int H, int D, int layout, float eps,
                       float *grid, const float *wsum);
 
@@ -922,6 +958,7 @@ int pdm_bev_normalize(void *stream, int B, int C, int W, int H, int D, int layou
  * summation order (ascending point index), so the result is bitwise reproducible.  workspace >=
  * pdm_gather_bev_workspace_bytes(...) bytes. */
 size_t pdm_gather_bev_workspace_bytes(int B, int P, int W, int H, int kx, int ky);
+/* align: any (features are staged 16 bytes at a time when C % 4 == 0 and feat is aligned). */
 int pdm_gather_bev(void *stream, int B, int P, int C, int degree, const float *xyz, const float *feat,
                    const float *sh, const float *inv2s2, float ox, float oy, float oz, float cx, float cy,
                    float cz, float icx, float icy, float icz, int W, int H, int D, int kx, int ky, int kz,
@@ -930,11 +967,13 @@ int pdm_gather_bev(void *stream, int B, int P, int C, int degree, const float *x
 /* Backward of pdm_bev_normalize for layout 1 (channels-last): y = the normalised grid, dy its gradient ->
  * dx (B,H,W,C*D) and dwsum (B,H,W,D), both fully written.  dx may be NULL (dwsum only: pdm_scatter_bev_grad_normalized
  * applies the division on its own reads of dy). */
+/* align: any (the float4 form needs D == 1, C % 4 == 0 and aligned y, dy, dx). */
 int pdm_bev_normalize_grad(void *stream, int B, int C, int W, int H, int D, float eps, const float *y,
                            const float *wsum, const float *dy, float *dx, float *dwsum);
 
 /* backward of pdm_scatter_bev w.r.t. feat, sh, inv2s2 (outputs fully written, no zero-fill needed);
  * dwsum may be NULL. */
+/* align: any (channel pairs — 8-byte accesses — need layout 1, D == 1, an even C and 8-byte aligned feat, dgrid / dy, dfeat). */
 int pdm_scatter_bev_grad(void *stream, int B, int P, int C, int degree, const float *xyz,
                          const float *feat, const float *sh, const float *inv2s2, float ox,
                          float oy, float oz, float cx, float cy, float cz, float icx, float icy,

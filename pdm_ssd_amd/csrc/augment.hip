@@ -532,6 +532,7 @@ extern "C" int pdm_augment_draw(void *stream, int B, int G, const int *group_cla
                 "augment_draw: null pointer");
     const AGLayout l = ag_layout(B, K);
     PDM_REQUIRE(workspace_bytes >= l.total, PDM_E_BADARG, "augment_draw: workspace %zu < %zu bytes", workspace_bytes, l.total);
+    PDM_WS_ALIGNED("augment_draw", workspace);
     int *walk = reinterpret_cast<int *>(static_cast<char *>(workspace) + l.walk);
     hipLaunchKernelGGL(ag_draw_kernel, dim3(1), dim3(1024), 0, as_stream(stream), B, g, limit_whole_scene ? 1 : 0, M, gt_boxes,
                        seed, state, flip_axes, use_rot ? 1 : 0, rot_lo, rot_hi, use_scale ? 1 : 0, scale_lo, scale_hi, K,
@@ -562,6 +563,7 @@ extern "C" int pdm_augment_select(void *stream, int B, int M, const float *gt_bo
                 PDM_E_BADARG, "augment_select: null pointer");
     const AGLayout l = ag_layout(B, K);
     PDM_REQUIRE(workspace_bytes >= l.total, PDM_E_BADARG, "augment_select: workspace %zu < %zu bytes", workspace_bytes, l.total);
+    PDM_WS_ALIGNED("augment_select", workspace);
     AGSelect a;
     a.B = B; a.M = M; a.K = K; a.M_out = M_out; a.remove_outside = remove_outside ? 1 : 0;
     a.db_entries = db_entries;
@@ -590,6 +592,7 @@ static int ag_scene_args(const char *who, int B, int C, const float *raw, const 
                 PDM_E_BADARG, "%s: null pointer", who);
     const AGLayout l = ag_layout(B, K);
     PDM_REQUIRE(workspace_bytes >= l.total, PDM_E_BADARG, "%s: workspace %zu < %zu bytes", who, workspace_bytes, l.total);
+    PDM_WS_ALIGNED(who, workspace);
     char *ws = static_cast<char *>(workspace);
     a->B = B; a->C = C; a->K = K; a->W = ag_segments(B); a->capacity = capacity;
     a->raw = raw; a->counts = counts; a->db_pts = db_points; a->db_boxes = db_boxes; a->db_off = db_offsets;

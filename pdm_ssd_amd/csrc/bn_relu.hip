@@ -495,6 +495,14 @@ static int bn_check(const char *who, int dtype, int layout, long long n, int C, 
     return 0;
 }
 
+// coef / grads (4, C) rows are read 16 bytes at a time by the rows x C kernels (ldv), the [parts][C][2] sums 8 bytes at a time
+// (bn_fold): a null pointer passes
+static int bn_tables_check(const char *who, const float *coef, const float *grads, const float *partial) {
+    PDM_REQUIRE(((reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(grads)) & 15) == 0 && (reinterpret_cast<uintptr_t>(partial) & 7) == 0,
+                PDM_E_BADARG, "%s: coef / grads must be 16-byte, partial 8-byte aligned", who);
+    return 0;
+}
+
 static BnCoef coef_of(const float *coef, const float *bwd, int C) {
     BnCoef k{};
     if (coef) { k.mean = coef; k.invstd = coef + C; k.scale = coef + 2 * C; k.shift = coef + 3 * C; }
@@ -522,6 +530,7 @@ extern "C" int pdm_bn_relu_forward(void *stream, int dtype, int layout, long lon
     if (layout == 0) L = 1;
     if (int rc = bn_check("bn_relu_forward", dtype, layout, n, C, L, x, y)) return rc;
     PDM_REQUIRE(coef && partial, PDM_E_BADARG, "bn_relu_forward: null workspace");
+    if (int rc = bn_tables_check("bn_relu_forward", coef, nullptr, partial)) return rc;
     if (n == 0) return 0;
     const int parts = pdm_bn_parts(layout, n, C, L);
     BnCoef none{};
@@ -559,6 +568,7 @@ extern "C" int pdm_bn_relu_forward_stats(void *stream, int dtype, long long n, i
                                          float *coef, const float *partial, int parts, int relu) {
     if (int rc = bn_check("bn_relu_forward_stats", dtype, 0, n, C, 1, x, y)) return rc;
     PDM_REQUIRE(coef && partial && parts >= 1, PDM_E_BADARG, "bn_relu_forward_stats: null workspace");
+    if (int rc = bn_tables_check("bn_relu_forward_stats", coef, nullptr, partial)) return rc;
     if (n == 0) return 0;
     hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(C), dim3(64), 0, as_stream(stream), partial, parts, C, (double)n, gamma, beta, eps,
                        momentum, running_mean, running_var, coef, 1);   // the producer's sums are plain sums: pivot 0
@@ -581,6 +591,7 @@ extern "C" int pdm_bn_forward_coef(void *stream, int dtype, long long n, int C, 
     if (int rc = bn_check("bn_forward_coef", dtype == 2 ? 0 : dtype, 0, n, C, 1, x, x)) return rc;
     PDM_REQUIRE(dtype == 0 || dtype == 1, PDM_E_BADARG, "bn_forward_coef: dtype %d (0 = fp32, 1 = bf16)", dtype);
     PDM_REQUIRE(coef && partial && n >= 1, PDM_E_BADARG, "bn_forward_coef: null workspace or no rows");
+    if (int rc = bn_tables_check("bn_forward_coef", coef, nullptr, partial)) return rc;
     const int parts = pdm_bn_parts(0, n, C, 1);
     BnCoef none{};
     none.pivot = coef + 3 * (size_t)C;   // parked in the shift row until the finalize kernel replaces it
@@ -596,6 +607,7 @@ extern "C" int pdm_bn_forward_coef(void *stream, int dtype, long long n, int C, 
 extern "C" int pdm_bn_finalize_stats(void *stream, long long n, int C, const float *gamma, const float *beta, float eps, float momentum,
                                      float *running_mean, float *running_var, float *coef, const float *partial, int parts) {
     PDM_REQUIRE(n >= 1 && C >= 1 && coef && partial && parts >= 1, PDM_E_BADARG, "bn_finalize_stats: bad argument");
+    if (int rc = bn_tables_check("bn_finalize_stats", coef, nullptr, partial)) return rc;
     hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(C), dim3(64), 0, as_stream(stream), partial, parts, C, (double)n, gamma, beta, eps,
                        momentum, running_mean, running_var, coef, 1);
     return check_launch("bn_finalize_stats");
@@ -609,6 +621,7 @@ static int bn_relu_backward_phases(const char *who, int phase, void *stream, int
     if (int rc = bn_check(who, dtype, layout, n, C, L, x, dy)) return rc;
     PDM_REQUIRE(coef && grads && ((phase & 1) == 0 || partial) && ((phase & 2) == 0 || n == 0 || dx), PDM_E_BADARG, "%s: null pointer", who);
     PDM_REQUIRE((reinterpret_cast<uintptr_t>(dx) & 15) == 0, PDM_E_BADARG, "%s: dx must be 16-byte aligned", who);
+    if (int rc = bn_tables_check(who, coef, grads, partial)) return rc;
     if (n == 0) return 0;
     const int parts = pdm_bn_parts(layout, n, C, L);
     const int V = dtype == 1 ? 8 : 4;
@@ -662,6 +675,7 @@ extern "C" int pdm_bn_relu_backward_apply(void *stream, int dtype, int layout, l
 // (train_gemm.hip); folded in double, in slot order.
 extern "C" int pdm_bn_finalize_bwd_stats(void *stream, long long n, int C, const float *coef, float *grads, const float *partial, int parts) {
     PDM_REQUIRE(n >= 1 && C >= 1 && coef && grads && partial && parts >= 1, PDM_E_BADARG, "bn_finalize_bwd_stats: bad argument");
+    if (int rc = bn_tables_check("bn_finalize_bwd_stats", coef, grads, partial)) return rc;
     hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(C), dim3(64), 0, as_stream(stream), partial, parts, C, (double)n, coef, grads);
     return check_launch("bn_finalize_bwd_stats");
 }
@@ -698,6 +712,7 @@ extern "C" int pdm_bn_relu_pool_forward(void *stream, int dtype, long long G, in
                                         float *coef, float *partial, int relu) {
     if (int rc = bn_pool_check("bn_relu_pool_forward", dtype, G, ns, C, x, y, xmax, xmin, imax, imin)) return rc;
     PDM_REQUIRE(coef && partial, PDM_E_BADARG, "bn_relu_pool_forward: null workspace");
+    if (int rc = bn_tables_check("bn_relu_pool_forward", coef, nullptr, partial)) return rc;
     if (G == 0) return 0;
     const int V = dtype ? 8 : 4, per = 256 / (C / V);
     const unsigned parts = bn_pool_grid(G, per);
@@ -725,6 +740,7 @@ extern "C" int pdm_bn_relu_pool_forward_kept(void *stream, int dtype, long long 
     PDM_REQUIRE(y && xmax && xmin && coef && partial && parts >= 1, PDM_E_BADARG, "bn_relu_pool_forward_kept: null pointer");
     PDM_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(xmax) | reinterpret_cast<uintptr_t>(xmin)) & 15) == 0, PDM_E_BADARG,
                 "bn_relu_pool_forward_kept: buffers must be 16-byte aligned");
+    if (int rc = bn_tables_check("bn_relu_pool_forward_kept", coef, nullptr, partial)) return rc;
     hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(C), dim3(64), 0, as_stream(stream), partial, parts, C, (double)G * (double)ns, gamma, beta,
                        eps, momentum, running_mean, running_var, coef, 1);
     const int per = 256 / (C / 8);
@@ -742,6 +758,7 @@ extern "C" int pdm_bn_relu_pool_backward(void *stream, int dtype, long long G, i
     if (int rc = bn_pool_check("bn_relu_pool_backward", dtype, G, ns, C, x, dy, xmax, xmin, imax, imin)) return rc;
     PDM_REQUIRE(coef && grads && partial && (G == 0 || dx) && (reinterpret_cast<uintptr_t>(dx) & 15) == 0, PDM_E_BADARG,
                 "bn_relu_pool_backward: null or unaligned pointer");
+    if (int rc = bn_tables_check("bn_relu_pool_backward", coef, grads, partial)) return rc;
     if (G == 0) return 0;
     const int V = dtype ? 8 : 4, per = 256 / (C / V);
     const unsigned parts = bn_pool_grid(G, per);

@@ -147,3 +147,6 @@ __device__ __forceinline__ void build_prefix_pair(int B, const int *__restrict__
             return (code);                \
         }                                 \
     } while (0)
+// every void *workspace holds ints, floats and 64-bit words of the library's own: 8-byte aligned, or rejected
+#define PDM_WS_ALIGNED(who, ws) \
+    PDM_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, PDM_E_BADARG, "%s: workspace must be 8-byte aligned", who)

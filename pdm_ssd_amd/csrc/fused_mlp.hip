@@ -1451,7 +1451,8 @@ static int fp_fused_launch(void *stream, int mode, int relu_last, int b, int n, 
                     (reinterpret_cast<uintptr_t>(wpack) & 15) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0 &&
                     (c_known % 4 != 0 || (reinterpret_cast<uintptr_t>(known_pm) & 15) == 0) &&
                     (c_skip % 4 != 0 || c_skip == 0 || (reinterpret_cast<uintptr_t>(skip_pm) & 15) == 0),
-                PDM_E_BADARG, "fp_mlp_fused: buffers must be 16-byte aligned and out_stride a multiple of 4");
+                PDM_E_BADARG, "%s: buffers must be 16-byte aligned and out_stride a multiple of 4",
+                mode == 2 ? "rows_mlp_fused" : mode == 1 ? "fp_mlp_fused_pre" : "fp_mlp_fused");
     FpArgs a{b, n, m, c_known, c_skip, known_pm, skip_pm, idx, weight, out_pm, out_stride, cout, mode == 1 ? z_pm : nullptr, z_stride};
     const bool pre_form = mode == 1;
     PDM_REQUIRE(!pre_form || (long long)m * z_stride < (1ll << 31), PDM_E_TOOLARGE, "fp_mlp_fused_pre: m * z_stride overflows 32-bit row offsets");

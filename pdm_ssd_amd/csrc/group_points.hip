@@ -545,7 +545,7 @@ extern "C" int pdm_group_concat_cl_ld_f(void *stream, int b, int n, int m, int c
                                         const void *feat_v, int feat_bf16, const int *idx, void *out, int out_bf16, int ld) {
     const float *feat_pm = static_cast<const float *>(feat_v);
     PDM_REQUIRE(!feat_bf16 || (out_bf16 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0), PDM_E_BADARG,
-                "group_concat_cl: bf16 features need the bf16 result with ld a multiple of 8");
+                "group_concat_cl: bf16 features need the bf16 result with ld a multiple of 8 in a 16-byte aligned out");
     PDM_REQUIRE(b >= 0 && n >= 0 && m >= 0 && c >= 0 && nsample >= 0 && ld >= 3 + c, PDM_E_BADARG, "group_concat_cl: negative size or ld < 3 + c");
     const long long total = (long long)b * m * nsample * ld;
     if (total == 0) return 0;

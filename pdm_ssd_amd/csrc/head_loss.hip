@@ -179,6 +179,7 @@ extern "C" int pdm_point_head_loss(void *stream, long long n_total, int n_per_sa
                 "point_head_loss: bad size");
     PDM_REQUIRE(out && workspace && workspace_bytes >= pdm_point_head_loss_workspace_bytes(n_total), PDM_E_BADARG,
                 "point_head_loss: null output or workspace too small");
+    PDM_WS_ALIGNED("point_head_loss", workspace);
     PDM_REQUIRE(n_total == 0 || (cls_preds && box_preds && xyz && box_idx && ext_idx && gt_boxes && mean_size && code_weights && labels &&
                                  dcls && dbox), PDM_E_BADARG, "point_head_loss: null pointer");
     PDM_REQUIRE(n_total % n_per_sample == 0, PDM_E_BADARG, "point_head_loss: n_total is not a multiple of n_per_sample");

@@ -427,17 +427,18 @@ __global__ __launch_bounds__(256) void interp_concat_rows8_kernel(long long tota
 }
 
 // d known[b, j, c] = sum over the CSR list of j of w * dx[b, i, c], c < C2: one wave per known point, lanes over channels,
-// every gradient row read contiguously, no atomics (fixed order: reproducible)
+// every gradient row read contiguously, no global atomics (the terms of a point are added in LIST order, and interp_csr_build_kernel
+// fills the lists through an LDS atomic cursor: the last bits of a sum can differ between launches)
 template <bool OB>   // OB: dknown is written as bf16 (round to nearest even of the same fp32 sums) instead of fp32
 __global__ __launch_bounds__(256) void interp_rows_grad_kernel(int n, int m, int c2, int ld, int ne, const unsigned short *__restrict__ dx,
                                                                const int *__restrict__ start_all, const unsigned short *__restrict__ ej_all,
-                                                               const float *__restrict__ ew_all, void *__restrict__ dknown_v) {
+                                                               const float *__restrict__ ew_all, void *__restrict__ dknown_v, int vec8) {
     float *__restrict__ dknown = static_cast<float *>(dknown_v);
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int *__restrict__ start = start_all + (size_t)b * (m + 1);
     const unsigned short *__restrict__ ej = ej_all + (size_t)b * ne;
     const float *__restrict__ ew = ew_all + (size_t)b * ne;
-    if ((c2 & 7) == 0 && (ld & 7) == 0) {        // eight channels per lane: 16-byte reads of the gradient rows
+    if (vec8) {        // c2 % 8 == 0, ld % 8 == 0, dx and dknown 16-byte aligned (host): eight channels per lane, 16-byte reads of the gradient rows
         // lpp lanes per known point (C2 / 8 rounded up to a power of two, <= 64): at C2 = 256 a wave serves two points instead of
         // leaving half its lanes idle; four list entries are in flight per step (one dependent index + weight + row load at a
         // time was a latency chain).  Same summation order per channel.
@@ -558,16 +559,19 @@ extern "C" int pdm_interp_concat_rows_grad_out(void *stream, int b, int n, int m
     int rc = check_launch("interp_concat_rows_grad(csr)");
     if (rc) return rc;
     int lpp = 1;     // as in the kernel's eight-channel form: points per workgroup = 4 * 64 / lpp
-    if ((c2 & 7) == 0 && (ld & 7) == 0)
+    // the eight-channel form reads dx and writes dknown 16 bytes at a time: a sub-buffer at another offset takes the element form
+    // (the same sums, added in list order)
+    const int vec8 = (c2 & 7) == 0 && (ld & 7) == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (reinterpret_cast<uintptr_t>(dknown) & 15) == 0;
+    if (vec8)
         while (lpp < (c2 >> 3) && lpp < 64) lpp <<= 1;
     else lpp = 64;
     const int ppb = 4 * (64 / lpp);
     if (out_bf16)
         hipLaunchKernelGGL(interp_rows_grad_kernel<true>, dim3((unsigned)((m + ppb - 1) / ppb), (unsigned)b), dim3(256), 0, as_stream(stream), n, m, c2, ld, ne,
-                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown);
+                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown, vec8);
     else
         hipLaunchKernelGGL(interp_rows_grad_kernel<false>, dim3((unsigned)((m + ppb - 1) / ppb), (unsigned)b), dim3(256), 0, as_stream(stream), n, m, c2, ld, ne,
-                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown);
+                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown, vec8);
     return check_launch("interp_concat_rows_grad");
 }
 

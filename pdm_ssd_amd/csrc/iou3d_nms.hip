@@ -123,6 +123,7 @@ extern "C" int pdm_nms(void *stream, int n, const float *boxes, float thresh, in
     if (n == 0) return zero_fill(stream, "nms(zero)", num_out, sizeof(int));
     PDM_REQUIRE(boxes && keep && workspace && workspace_bytes >= pdm_nms_workspace_bytes(n), PDM_E_BADARG,
                 "nms: null pointer or workspace of %zu bytes, need %zu", workspace_bytes, pdm_nms_workspace_bytes(n));
+    PDM_WS_ALIGNED("nms", workspace);
     const int cb = (n + 63) / 64;
     unsigned long long *mask = static_cast<unsigned long long *>(workspace);
     hipLaunchKernelGGL(nms_mask_kernel, dim3(cb, cb), dim3(64), 0, as_stream(stream), n, thresh, normal, boxes, mask);

@@ -444,6 +444,7 @@ static int kd_fov_args(const char *who, int B, int C, long long total_rows, cons
     PDM_REQUIRE(out_counts && overflow && workspace, PDM_E_BADARG, "%s: null pointer", who);
     const KDFovLayout l = kd_fov_layout(B);
     PDM_REQUIRE(workspace_bytes >= l.total, PDM_E_BADARG, "%s: workspace %zu < %zu bytes", who, workspace_bytes, l.total);
+    PDM_WS_ALIGNED(who, workspace);
     char *ws = static_cast<char *>(workspace);
     a->capacity = capacity;
     a->seg_count = reinterpret_cast<int *>(ws + l.seg_count);
@@ -466,6 +467,7 @@ static int kd_box_args(const char *who, int B, int C, long long total_rows, cons
                 "%s: null pointer", who);
     const KDBoxLayout l = kd_box_layout(B, M);
     PDM_REQUIRE(workspace_bytes >= l.total, PDM_E_BADARG, "%s: workspace %zu < %zu bytes", who, workspace_bytes, l.total);
+    PDM_WS_ALIGNED(who, workspace);
     char *ws = static_cast<char *>(workspace);
     a->M = M; a->boxes = boxes; a->box_count = box_count; a->centres = nullptr;
     a->seg_hull = reinterpret_cast<int *>(ws + l.seg_hull);

@@ -512,6 +512,7 @@ extern "C" int pdm_kitti_eval_pass2(void *stream, int F, const int *gt_off, cons
     PDM_REQUIRE(min_overlap && thresholds && num_thresholds && sums && workspace, PDM_E_BADARG, "kitti_eval_pass2: null pointer");
     const size_t need = pdm_kitti_eval_workspace_bytes(F, ncombo);
     PDM_REQUIRE(workspace_bytes >= need, PDM_E_BADARG, "kitti_eval_pass2: workspace %zu < %zu bytes", workspace_bytes, need);
+    PDM_WS_ALIGNED("kitti_eval_pass2", workspace);
     PDM_REQUIRE(F == 0 || (gt_off && dt_off && ov_off && (NP == 0 || overlaps) && (NG == 0 || (ign_gt && gt_alpha && gt_bbox && gt_name)) &&
                            (ND == 0 || (ign_dt && dt_score && dt_alpha && dt_bbox))), PDM_E_BADARG, "kitti_eval_pass2: null pointer");
     const KEFrames fr{F, gt_off, dt_off, ov_off};

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(PG_THREADS, CPL <= 2 ? 5 : 1) void pdm_gather_reg_k
         const int np = min(PG_CHUNK, e - s - c0);
         __syncthreads();
 #define PG_POINT(q) (PG_DIAG & 8 ? (tile * 7 + c0 + (q)) % P : sorted ? sorted[c0 + (q)] : tpg[c0 + (q)])
-        if ((C & 3) == 0) {
+        if ((C & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0) {   // rows of C floats 16-byte aligned: one load per four channels
             const int C4 = C >> 2;
             for (int i = tid; i < np * C4; i += PG_THREADS) {
                 const int q = i / C4, c = i - q * C4;

@@ -280,7 +280,8 @@ __global__ __launch_bounds__(PDM_WAVES * 64, 5) void pdm_scatter_grad_kernel(
 
     // dfeat[c] = sum_k w_k dgrid[k,c];  dw_k += sum_c dgrid[k,c] f[c]
     const float *__restrict__ f = feat + pi * C;
-    if (layout == 1 && g.D == 1 && (C & 1) == 0) {
+    if (layout == 1 && g.D == 1 && (C & 1) == 0 &&
+        ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(dgrid) | reinterpret_cast<uintptr_t>(dfeat)) & 7) == 0) {
         // channels-last map, one height bin: a lane owns the channel pair (2 lane, 2 lane + 1) — one 8-byte load per cell covers
         // 128 channels — and the rows of fourteen cells are requested before the first is consumed.  (One 4-byte load at a time,
         // each consumed before the next was requested, made a wave a chain of 2 K round trips: 0.68 ms per step at bs = 32.)

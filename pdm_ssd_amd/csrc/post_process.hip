@@ -311,6 +311,7 @@ extern "C" int pdm_post_process(void *stream, int B, int C, int multi_class, lon
     const size_t need = pdm_post_process_workspace_bytes((int)S, pre_max, post_max);
     PDM_REQUIRE(S == 0 || (workspace && workspace_bytes >= need), PDM_E_BADARG,
                 "post_process: workspace of %zu bytes, need %zu", workspace ? workspace_bytes : (size_t)0, need);
+    PDM_WS_ALIGNED("post_process", workspace);
     hipLaunchKernelGGL(pp_zero_kernel, dim3(1), dim3(64), 0, as_stream(stream), err_flag,
                        reinterpret_cast<unsigned long long *>(recall), 1 + num_thresh);
     int rc = check_launch("post_process(zero)");

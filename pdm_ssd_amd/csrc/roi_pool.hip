@@ -344,6 +344,7 @@ extern "C" int pdm_roiaware_pool3d_forward(void *stream, int K, int P, int C, in
     const size_t need = pdm_roiaware_pool3d_workspace_bytes(K, out_x, out_y, out_z);
     PDM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), PDM_E_BADARG,
                 "roiaware_pool3d_forward: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    PDM_WS_ALIGNED("roiaware_pool3d_forward", workspace);
     hipLaunchKernelGGL(roiaware_forward_kernel, dim3(K), dim3(RA_NT), 0, as_stream(stream), P, C, max_pts, out_x, out_y, out_z, rois, pts,
                        feats, pool_method, static_cast<int *>(workspace), pts_idx_of_voxels, argmax, pooled);
     return check_launch("roiaware_pool3d_forward");

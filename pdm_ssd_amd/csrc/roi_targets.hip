@@ -490,6 +490,7 @@ extern "C" int pdm_rcnn_loss(void *stream, long long n, const float *rcnn_cls, c
                 dreg && dcorner && loss_cls && loss_reg && loss_corner && fg_count, PDM_E_BADARG, "rcnn_loss: null pointer");
     PDM_REQUIRE(workspace && workspace_bytes >= pdm_rcnn_loss_workspace_bytes(n), PDM_E_BADARG,
                 "rcnn_loss: workspace too small (%zu < %zu bytes)", workspace_bytes, pdm_rcnn_loss_workspace_bytes(n));
+    PDM_WS_ALIGNED("rcnn_loss", workspace);
     RLArgs a{};
     a.n = n;
     a.cls = rcnn_cls; a.reg = rcnn_reg; a.rois = rois; a.gt = gt_of_rois; a.src = gt_of_rois_src; a.mask = reg_valid_mask;

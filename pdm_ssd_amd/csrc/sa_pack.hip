@@ -176,6 +176,7 @@ static int sa_pack_job(const char *who, int b, int n, int m, int nsample, const 
     PDM_REQUIRE(nc == 0 || (idx && workspace), PDM_E_BADARG, "%s: null pointer", who);
     PDM_REQUIRE(workspace_bytes >= pdm_sa_pack_workspace_bytes(b, m), PDM_E_BADARG, "%s: workspace %zu < %zu bytes", who,
                 workspace_bytes, pdm_sa_pack_workspace_bytes(b, m));
+    PDM_WS_ALIGNED(who, workspace);
     PDM_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 15) == 0 && (reinterpret_cast<uintptr_t>(pack) & 7) == 0, PDM_E_BADARG,
                 "%s: idx must be 16-byte, pack 8-byte aligned", who);
     unsigned char *cnt = static_cast<unsigned char *>(workspace);

@@ -1139,7 +1139,8 @@ extern "C" int pdm_tg_wgrad(void *stream, long long R, int K, int N, const void 
     PDM_REQUIRE(dY && X && workspace, PDM_E_BADARG, "tg_wgrad: null pointer");
     PDM_REQUIRE(K % 8 == 0 && N % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= K && ldy >= N, PDM_E_BADARG,
                 "tg_wgrad: K=%d N=%d ldx=%lld ldy=%lld must be multiples of 8 and cover the rows", K, N, ldx, ldy);
-    PDM_REQUIRE(tg_al16(dY) && tg_al16(X) && tg_al16(workspace), PDM_E_BADARG, "tg_wgrad: operands must be 16-byte aligned");
+    PDM_REQUIRE(tg_al16(dY) && tg_al16(X) && tg_al16(workspace) && tg_al16(x_bn_coef), PDM_E_BADARG,
+                "tg_wgrad: operands (and x_bn_coef) must be 16-byte aligned");
     PDM_REQUIRE(workspace_bytes >= pdm_tg_wgrad_ws_bytes(R, K, N), PDM_E_BADARG, "tg_wgrad: workspace of %zu bytes, need %zu",
                 workspace_bytes, pdm_tg_wgrad_ws_bytes(R, K, N));
     const long long slabs = tg_wgrad_slabs(R, K, N);

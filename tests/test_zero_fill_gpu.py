@@ -72,6 +72,22 @@ def test_query_and_group_clears_an_unaligned_index_range_and_nothing_else(dev):
     assert int(base[0]) == 7 and bool((base[1 + m * ns:] == 7).all())
 
 
+@pytest.mark.parametrize("floats", [1, 1025, 16385])
+@pytest.mark.parametrize("offset", [0, 4, 8, 12])
+def test_colsum_of_zero_rows_clears_exactly_its_range_at_every_float_offset(dev, floats, offset):
+    """pdm_tg_colsum with R = 0 hands its `out` (N floats, any N) to the zero fill: 4, 4100 and 65540 bytes — the lengths next
+    to 1, 4099 and 65537 that a float pointer can have — at every offset a float pointer can have: a range shorter than its
+    head, one with a 16-byte middle of one workgroup and one of several, each with head and tail; red zones on both sides."""
+    from arena import Arena
+    a = Arena(dev)
+    out = a.carve((floats,), torch.float32, offset)
+    out.fill_(7.0)
+    _native.call("pdm_tg_colsum", _native.stream(dev), 0, floats, 0, 8, out.data_ptr(), 0)
+    torch.cuda.synchronize()
+    a.check()
+    assert bool((out == 0).all())
+
+
 def test_wgrad_of_zero_rows_clears_an_unaligned_range_with_head_and_tail(dev):
     """21 floats (84 bytes) one element past a 16-byte boundary: 12 bytes of head, four 16-byte stores, 8 bytes of tail"""
     N, K = 3, 7

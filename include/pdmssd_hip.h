@@ -996,6 +996,49 @@ int pdm_scatter_bev_grad_normalized(void *stream, int B, int P, int C, int degre
  * scores (B,n) f32 -> idx (B,k) int32, idx[b,r] = index of the r-th ranked point; k <= n, k <= 16384. */
 int pdm_topk_sampling(void *stream, int b, int n, int k, const float *scores, int *idx);
 
+/* The pillar front end (csrc/pillar.hip, DESIGN.md "Pillar path"): dynamic pillars without a host loop, float atomics or a
+ * sort.  Every result is a function of the input alone, bit for bit.  int32 indices throughout: B * nx * ny and N * C1 must
+ * fit int32 (PDM_E_TOOLARGE), nz must be 1 (PDM_E_BADARG).
+ *
+ * pdm_pillar_assign: points (N, C1) fp32 rows (batch_idx, x, y, z, ...), any row order.  cell = floor((x - x0) / vx) in fp32
+ *   with an IEEE division; a row is kept iff 0 <= cx < nx, 0 <= cy < ny and 0 <= batch_idx < B (z is not tested).  Pillars
+ *   are the occupied cells in ascending b * nx * ny + cx * ny + cy.  Outputs are sized at capacity (cap = min(N, B nx ny)) and
+ *   written up to N' kept rows / P pillars: kept_idx (N) kept rows in input order, unq_inv (N) their pillar, voxel_coords
+ *   (cap, 4) = (b, 0, cy, cx), pillar_count (cap), pillar_mean (cap, 3) = float(double(sum of llrint(x * 2^20)) * 2^-20 /
+ *   count), cell_table (B nx ny) pillar id or -1 in key order (all written), seg_start (cap + 1) / seg_rows (N) the kept rows
+ *   of every pillar (slot order unspecified), record (2) = {N', P}.  workspace >= pdm_pillar_assign_workspace_bytes, 8-byte
+ *   aligned.  N = 0 is valid.
+ * pdm_pillar_features: out (n_kept, F) = [points[:, 1:] | points[:, 4:], xyz - mean, xyz - cell centre, |xyz| if with_dist];
+ *   the cell centre is float(cx) * vx + xoff, product and sum rounded separately; xoff = fp32(vx / 2 + x0 in double).
+ * pdm_pillar_segment_max: x (n_kept, K) -> x_max (P, K), arg (P, K) the winning row, ties to the lower row;
+ *   pdm_pillar_segment_max_grad: grad_x (n_kept, K) = grad_max at the winning rows, zero elsewhere, all written.
+ * pdm_pillar_fused_pfn: features -> weight (K, F <= 16) -> * scale + shift -> ReLU -> max per pillar: out (P, K); the
+ *   (n_kept, K) activations are never stored.
+ * pdm_pillar_cell_table: the table from voxel_coords (P, 4).  pdm_pillar_scatter: features (P, C) -> canvas (B, C, ny, nx),
+ *   every element written in one pass, B <= 65535; pdm_pillar_scatter_grad: grad_features (P, C) gathered from grad_canvas. */
+/* align: any (4-byte accesses only). */
+size_t pdm_pillar_assign_workspace_bytes(int N, int B, int nx, int ny);
+int pdm_pillar_assign(void *stream, int N, int C1, const float *points, int B, int nx, int ny, int nz, float x0, float y0,
+                      float vx, float vy, int *kept_idx, int *unq_inv, int *voxel_coords, int *pillar_count,
+                      float *pillar_mean, int *cell_table, int *seg_start, int *seg_rows, int *record, void *workspace,
+                      size_t workspace_bytes);
+int pdm_pillar_features(void *stream, int n_kept, int C1, const float *points, const int *kept_idx, const int *unq_inv,
+                        const int *voxel_coords, const float *pillar_mean, int abs_xyz, int with_dist, float vx, float vy,
+                        float xoff, float yoff, float zoff, float *out);
+int pdm_pillar_segment_max(void *stream, int P, int K, const float *x, const int *seg_start, const int *seg_rows, float *x_max,
+                           int *arg);
+int pdm_pillar_segment_max_grad(void *stream, int n_kept, int K, const float *grad_max, const int *arg, const int *unq_inv,
+                                float *grad_x);
+int pdm_pillar_fused_pfn(void *stream, int P, int K, int C1, const float *points, const int *kept_idx, const int *voxel_coords,
+                         const float *pillar_mean, const int *seg_start, const int *seg_rows, int abs_xyz, int with_dist,
+                         float vx, float vy, float xoff, float yoff, float zoff, const float *weight, const float *scale,
+                         const float *shift, float *out);
+int pdm_pillar_cell_table(void *stream, int P, const int *voxel_coords, int B, int nx, int ny, int nz, int *cell_table);
+int pdm_pillar_scatter(void *stream, int P, int C, const float *pillar_features, const int *cell_table, int B, int nx, int ny,
+                       int nz, float *canvas);
+int pdm_pillar_scatter_grad(void *stream, int P, int C, const float *grad_canvas, const int *voxel_coords, int B, int nx, int ny,
+                            int nz, float *grad_features);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -1,0 +1,6 @@
+"""2-D backbones, registered by NAME as the reference's pcdet/models/backbones_2d/__init__.py does."""
+from .base_bev_backbone import BaseBEVBackbone
+
+__all__ = {
+    'BaseBEVBackbone': BaseBEVBackbone,
+}

@@ -1,0 +1,6 @@
+"""Pillars -> BEV canvas, registered by NAME as the reference's pcdet/models/backbones_2d/map_to_bev/__init__.py does."""
+from .pointpillar_scatter import PointPillarScatter
+
+__all__ = {
+    'PointPillarScatter': PointPillarScatter,
+}

@@ -35,3 +35,8 @@ def _wrap(v):
 
 def cfg_from_dict(d):
     return _wrap(d)
+
+
+def cfg_get(cfg, key, default=None):
+    """cfg[key] of a dict or cfg.key of any other configuration object, `default` when absent"""
+    return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)

@@ -92,6 +92,23 @@ CENTER_PDM_CFG = {
                                        'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
 }
 
+# CenterPoint on dynamic pillars: DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone -> CenterHead.  The 2-D backbone
+# holds the upstream project's published KITTI PointPillars values (its tools/cfgs/kitti_models/pointpillar.yaml) restated
+# as a dict; the head is CENTER_PDM_CFG's on that backbone's map (248 x 216 cells of 0.32 m: FEATURE_MAP_STRIDE 2).
+PILLAR_RANGE = [0, -39.68, -3, 69.12, 39.68, 1]
+PILLAR_VOXEL_SIZE = [0.16, 0.16, 4]
+PILLAR_GRID_SIZE = [432, 496, 1]
+CENTER_PILLAR_CFG = {
+    'NAME': 'CenterPoint',
+    'VFE': {'NAME': 'DynamicPillarVFE', 'USE_NORM': True, 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'NUM_FILTERS': [64]},
+    'MAP_TO_BEV': {'NAME': 'PointPillarScatter', 'NUM_BEV_FEATURES': 64},
+    'BACKBONE_2D': {'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [3, 5, 5], 'LAYER_STRIDES': [2, 2, 2], 'NUM_FILTERS': [64, 128, 256],
+                    'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [128, 128, 128]},
+    'DENSE_HEAD': copy.deepcopy(CENTER_PDM_CFG['DENSE_HEAD']),
+    'POST_PROCESSING': copy.deepcopy(CENTER_PDM_CFG['POST_PROCESSING']),
+}
+CENTER_PILLAR_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['FEATURE_MAP_STRIDE'] = 2
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -119,3 +136,19 @@ def build_center_pdm(model_cfg=None, num_point_features=4):
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(CENTER_PDM_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=synthetic_dataset(num_point_features))
+
+
+def pillar_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None, grid_size=None):
+    """The pillar detectors' dataset namespace: the KITTI PointPillars range, 0.16 m pillars over the whole height."""
+    return SimpleNamespace(class_names=CLASS_NAMES, grid_size=list(PILLAR_GRID_SIZE if grid_size is None else grid_size),
+                           voxel_size=list(PILLAR_VOXEL_SIZE if voxel_size is None else voxel_size),
+                           point_cloud_range=list(PILLAR_RANGE if point_cloud_range is None else point_cloud_range),
+                           point_feature_encoder=SimpleNamespace(num_point_features=num_point_features))
+
+
+def build_center_pillar(model_cfg=None, num_point_features=4, dataset=None):
+    """CenterPoint from CENTER_PILLAR_CFG (or a dict like it): DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone ->
+    CenterHead, on pillar_dataset() unless another dataset namespace is given."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(CENTER_PILLAR_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillar_dataset(num_point_features) if dataset is None else dataset)

@@ -2,7 +2,7 @@
 detectors/__init__.py:19-46: build_detector / build_network by NAME, model_fn_decorator for the training loop."""
 from collections import namedtuple
 
-from .detector3d_template import BACKBONES_3D, MAP_TO_BEV, Detector3DTemplate
+from .detector3d_template import BACKBONES_2D, BACKBONES_3D, MAP_TO_BEV, VFE, Detector3DTemplate
 from .centerpoint import CenterPoint
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN

@@ -4,21 +4,24 @@ Contract restated from /root/reference/pcdet/models/detectors/detector3d_templat
 `build_<slot>` per slot, modules chosen by `NAME` from registry dicts, `model_info_dict` threading channel counts),
 :178-263 (post_processing: per-sample class-agnostic NMS over the head's boxes) and :330-359 (shape-filtered
 checkpoint loading).  The reference's template cannot be imported on this platform (it pulls in spconv,
-pcdet/utils/spconv_utils.py:3); the slots that only exist for voxel models (vfe, pfe, backbone_2d) are kept as names so
-reference configs read naturally, and build nothing here.  The roi_head slot builds the point-based RoI heads of
-roi_heads/ (PointRCNN's second stage), which need no spconv.
+pcdet/utils/spconv_utils.py:3).  The vfe, map_to_bev and backbone_2d slots build the pillar family (DynamicPillarVFE ->
+PointPillarScatter -> BaseBEVBackbone), which needs no spconv; a NAME outside the registries (MeanVFE, ...) and the pfe
+slot are refused.  The roi_head slot builds the point-based RoI heads of roi_heads/ (PointRCNN's second stage).
 """
 import torch
 import torch.nn as nn
 
-from .. import dense_heads, roi_heads
+from .. import backbones_2d, dense_heads, roi_heads, vfe
+from ..backbones_2d import map_to_bev
 from ..iou3d_nms import iou3d_nms_utils
 from ..pdm_neck import PDMNeck
 from ..pointnet2_backbone import PointNet2MSG
 
 # registries keyed by NAME, as pcdet/models/backbones_3d/__init__.py:10-22 and map_to_bev/__init__.py:5-10
 BACKBONES_3D = {'PointNet2MSG': PointNet2MSG}
-MAP_TO_BEV = {'PDMNeck': PDMNeck}
+MAP_TO_BEV = {'PDMNeck': PDMNeck, **map_to_bev.__all__}
+VFE = {k: v for k, v in vfe.__all__.items() if k != 'VFETemplate'}
+BACKBONES_2D = dict(backbones_2d.__all__)
 
 
 def _get(cfg, key, default=None):
@@ -63,14 +66,38 @@ class Detector3DTemplate(nn.Module):
         assert _get(self.model_cfg, key, None) is None, f'{key} needs spconv / voxel modules: not part of the point path'
         return None, model_info_dict
 
+    def _registered(self, key, registry):
+        """the slot's config, or None; a NAME outside the registry is one of the reference's spconv / voxel modules"""
+        cfg = _get(self.model_cfg, key, None)
+        assert cfg is None or _get(cfg, 'NAME') in registry, \
+            f"{key} {_get(cfg, 'NAME')} needs spconv / voxel modules: not built here (have {sorted(registry)})"
+        return cfg
+
     def build_vfe(self, model_info_dict):
-        return self._unsupported('VFE', model_info_dict)
+        """ref :62-77: the encoder's output width becomes num_point_features"""
+        cfg = self._registered('VFE', VFE)
+        if cfg is None:
+            return None, model_info_dict
+        module = VFE[_get(cfg, 'NAME')](
+            model_cfg=cfg, num_point_features=model_info_dict['num_rawpoint_features'],
+            point_cloud_range=model_info_dict['point_cloud_range'], voxel_size=model_info_dict['voxel_size'],
+            grid_size=model_info_dict['grid_size'])
+        model_info_dict['num_point_features'] = module.get_output_feature_dim()
+        model_info_dict['module_list'].append(module)
+        return module, model_info_dict
 
     def build_pfe(self, model_info_dict):
         return self._unsupported('PFE', model_info_dict)
 
     def build_backbone_2d(self, model_info_dict):
-        return self._unsupported('BACKBONE_2D', model_info_dict)
+        """ref :106-117: reads num_bev_features of the map_to_bev module and replaces it with its own"""
+        cfg = self._registered('BACKBONE_2D', BACKBONES_2D)
+        if cfg is None:
+            return None, model_info_dict
+        module = BACKBONES_2D[_get(cfg, 'NAME')](model_cfg=cfg, input_channels=model_info_dict['num_bev_features'])
+        model_info_dict['module_list'].append(module)
+        model_info_dict['num_bev_features'] = module.num_bev_features
+        return module, model_info_dict
 
     def build_roi_head(self, model_info_dict):
         """ref :159-176: the point-based RoI heads need no spconv; built by NAME from roi_heads.__all__."""

@@ -204,37 +204,10 @@ __global__ __launch_bounds__(BQG_BUILD_T) void bq_grid_build_kernel(int n, float
     }
 
     // ---- exclusive scan of hist[0..ncells) -> hist (running cursor) and cell_start (global)
-    const int per = (H.ncells + BQG_BUILD_T - 1) / BQG_BUILD_T;
-    const int c0 = tid * per, c1 = min(c0 + per, H.ncells);
-    int local = 0;
-    for (int c = c0; c < c1; ++c) local += hist[c];
-    int incl = local;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        int v = lane < BQG_BUILD_T / 64 ? wsum[lane] : 0;
-        int inc = v;
-        for (int off = 1; off < BQG_BUILD_T / 64; off <<= 1) {
-            const int t = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += t;
-        }
-        if (lane < BQG_BUILD_T / 64) wsum[lane] = inc - v;  // exclusive wave offsets
-    }
-    __syncthreads();
-    int run = wsum[wave] + incl - local;
-    for (int c = c0; c < c1; ++c) {
-        const int cnt = hist[c];
-        hist[c] = run;
-        run += cnt;
-    }
+    hist_to_cursors<BQG_BUILD_T>(hist, H.ncells, wsum, nullptr);
     if (tid == 0) cell_start[H.ncells] = n;
-    __syncthreads();
-    // the starts leave through coalesced stores (a thread's own block of cells is `per` words apart from its neighbour's:
-    // written from the loop above, the 14 k cell starts of a KITTI-range cloud took 4 of the scan's 6 us)
+    // the starts leave through coalesced stores (inside the scan a thread's own block of cells is a chunk apart from its
+    // neighbour's: written from there, the 14 k cell starts of a KITTI-range cloud took 4 of the scan's 6 us)
     for (int c = tid; c < H.ncells; c += BQG_BUILD_T) {
         const int v = hist[c];
         cell_start[c] = v;
@@ -337,11 +310,7 @@ __device__ __forceinline__ void bq_centre_wave(const BqGrid &G, float cx, float 
             beg = G.cell_start[base + x0];
             cntr = G.cell_start[base + x1 + 1] - beg;
         }
-        int incl = cntr;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_scan_incl(cntr);
         const int total = __shfl(incl, 63, 64);
         if (total == 0) continue;  // wave-uniform
         const int rows_here = min(64, nrows - r0);
@@ -399,12 +368,7 @@ __device__ __forceinline__ void bq_centre_wave(const BqGrid &G, float cx, float 
     unsigned int *mine = bm + lane * wpl;
     int cnt = 0;
     for (int w = 0; w < wpl; ++w) cnt += __popc(mine[w]);
-    int incl = cnt;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    int pos = incl - cnt;  // hits in lower lanes
+    int pos = wave_scan_incl(cnt) - cnt;  // hits in lower lanes
     int first_local = -1;
     if (cnt > 0) {
         for (int w = 0; w < wpl; ++w) {

@@ -8,6 +8,7 @@
 //         backward = two sums per channel (2 reads) -> finalize -> input gradient (2 reads, 1 write)
 // Bound: HBM.  Partial sums go to a (parts, C, 2) buffer and are folded in double by the finalize kernels, so a run is
 // bit-reproducible (no float atomics).
+#include "bf16.h"
 #include "common.h"
 
 namespace pdm {
@@ -23,13 +24,6 @@ template <> struct BnVec<float> {
     __device__ static void store(float *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 };
 typedef unsigned short bf16_t;
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) {   // round to nearest even; NaN stays NaN
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 template <> struct BnVec<bf16_t> {
     static constexpr int V = 8;
     __device__ static void load(const bf16_t *p, float (&v)[8]) {
@@ -38,12 +32,7 @@ template <> struct BnVec<bf16_t> {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
     }
-    __device__ static void store(bf16_t *p, const float (&v)[8]) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = (unsigned)f2bf(v[2 * i]) | ((unsigned)f2bf(v[2 * i + 1]) << 16);
-        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    __device__ static void store(bf16_t *p, const float (&v)[8]) { *reinterpret_cast<uint4 *>(p) = pack_bf16x8(v); }
 };
 
 struct BnCoef {   // per-channel constants, all (C) fp32
@@ -185,8 +174,8 @@ __global__ __launch_bounds__(256) void bn_cl_apply_mixed_kernel(const float *__r
                 ov[i] = relu ? fmaxf(y, 0.f) : y;
             }
             uint2 w;
-            w.x = (unsigned)f2bf(ov[0]) | ((unsigned)f2bf(ov[1]) << 16);
-            w.y = (unsigned)f2bf(ov[2]) | ((unsigned)f2bf(ov[3]) << 16);
+            w.x = (unsigned)f32_to_bf16(ov[0]) | ((unsigned)f32_to_bf16(ov[1]) << 16);
+            w.y = (unsigned)f32_to_bf16(ov[2]) | ((unsigned)f32_to_bf16(ov[3]) << 16);
             *reinterpret_cast<uint2 *>(static_cast<bf16_t *>(out) + e * 4) = w;
         } else {
             float gv[4], pp[4], qq[4];

@@ -19,12 +19,6 @@ int zero_fill(void *stream, const char *who, void *p, size_t bytes);
 // pairs, thread-safe; returns hipSuccess (0) or the runtime's error code.
 int grant_lds(const void *fn, size_t bytes);
 
-// Scatter-add backward through an inverted (CSR) index, shared by three_interpolate and group_points (interpolate.hip)
-size_t csr_workspace_bytes(int b, long long ne, int m);
-bool csr_form_applies(int b, int row_len, long long ne, int m);
-int csr_scatter_grad_launch(void *stream, const char *who, int b, int c, int row_len, int per, int m, const float *grad_out,
-                            const int *idx, const float *weight, float *grad_points, void *workspace);
-
 // Ragged compaction in W segments per frame (augment.hip, kitti_data.hip; defined in augment.hip): seg_count (B, W) ->
 // seg_base (B, W) the exclusive prefix inside the frame, out_counts (B) the frame totals, offsets (B + 1) their exclusive
 // prefix over the frames, overflow[0] = offsets[B] > capacity.  B <= 1024.
@@ -49,17 +43,23 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask, int lane) {
     return __popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// inclusive scan of one int per lane over the wave (all 64 lanes call it)
+__device__ __forceinline__ int wave_scan_incl(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(v, off, 64);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
 // block-wide exclusive scan of one int per thread (NT threads, every one calls it); returns the exclusive prefix,
 // *total = block sum.  s_wave: NT / 64 ints of LDS, reusable by the next call at once.
 template <int NT>
 __device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
+    const int incl = wave_scan_incl(v);
     __syncthreads();                      // s_wave reuse across calls
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
@@ -71,6 +71,37 @@ __device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
     }
     *total = tot;
     return base + incl - v;
+}
+
+// Exclusive scan of an LDS histogram in place: counts become running cursors (the fill positions of a counting sort).
+// Every thread of the workgroup (NT threads) calls it after the barrier that completes hist[0..ncells); a thread owns a
+// contiguous chunk of cells (a compile-time ncells gives constant-trip loops, which unroll).  start_out, when not null,
+// receives the ncells + 1 starts.  s_wave: NT / 64 ints of LDS.  Ends with a barrier: the cursors are ready on return.
+template <int NT>
+__device__ __forceinline__ void hist_to_cursors(int *hist, int ncells, int *s_wave, int *__restrict__ start_out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per = (ncells + NT - 1) / NT;
+    const int c0 = threadIdx.x * per, c1 = min(c0 + per, ncells);
+    int local = 0;
+    for (int c = c0; c < c1; ++c) local += hist[c];
+    const int incl = wave_scan_incl(local);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    if (wave == 0) {
+        const int v = lane < NT / 64 ? s_wave[lane] : 0;
+        const int inc = wave_scan_incl(v);
+        if (lane < NT / 64) s_wave[lane] = inc - v;   // exclusive wave offsets
+    }
+    __syncthreads();
+    int run = s_wave[wave] + incl - local;
+    for (int c = c0; c < c1; ++c) {
+        const int cnt = hist[c];
+        hist[c] = run;
+        if (start_out) start_out[c] = run;
+        run += cnt;
+    }
+    if (start_out && threadIdx.x == NT - 1) start_out[ncells] = run;   // the last thread ends on the total
+    __syncthreads();
 }
 
 // Squared distance with the rounding sequence pinned:
@@ -87,12 +118,7 @@ __device__ __forceinline__ void radix_pick256(const int *hist, int remaining, in
     const int lane = threadIdx.x & 63;
     const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
     const int sum = h0 + h1 + h2 + h3;
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
+    const int incl = wave_scan_incl(sum);
     const int excl = incl - sum;
     const unsigned long long hit = __ballot(excl < remaining && incl >= remaining);
     const int src = hit ? __ffsll((long long)hit) - 1 : 63;   // no lane reaches it only if remaining > total: last bins

@@ -8,7 +8,8 @@
 // the flattened (M*ns) axis — one 16-byte index load, then for each channel of its channel group
 // four L2-resident gathers and one 16-byte coalesced store.  The reference issues one 4-byte
 // store per thread and re-reads the index for every channel.
-#include "common.h"
+#include "bf16.h"
+#include "csr.h"
 
 namespace pdm {
 
@@ -386,11 +387,11 @@ extern "C" int pdm_group_points_grad(void *stream, int b, int c, int n, int npoi
 }
 
 extern "C" size_t pdm_group_points_grad_ws_bytes(int b, int npoints, int nsample, int n) {
-    return csr_workspace_bytes(b, (long long)npoints * nsample, n);
+    return csr_workspace_bytes(CSR_ROW_WEIGHT, b, (long long)npoints * nsample, n);
 }
 
 // pdm_group_points_grad with a caller-provided workspace (pdm_group_points_grad_ws_bytes bytes): the scatter onto the n
-// source points is inverted into per-cloud CSR lists, then accumulated without atomics (interpolate.hip).  Applies when a
+// source points is inverted into per-cloud CSR lists, then accumulated without atomics (csr.hip).  Applies when a
 // grad_out row (npoints * nsample floats) fits 128 KB of LDS and n <= 16384; otherwise the plain entry point is used.
 extern "C" int pdm_group_points_grad_ws(void *stream, int b, int c, int n, int npoints, int nsample, const float *grad_out,
                                         const int *idx, float *grad_points, void *workspace, size_t workspace_bytes) {
@@ -454,13 +455,6 @@ extern "C" int pdm_query_and_group(void *stream, int b, int n, int m, int c, flo
 // bf16 = round-to-nearest-even of the fp32 value, i.e. exactly what the cast would have produced.
 namespace pdm {
 
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);   // NaN stays NaN (quiet)
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
 template <bool BF16>
 __global__ __launch_bounds__(256) void group_concat_cl_kernel(long long total, int n, int m, int c, int ns, int ld,
                                                               const float *__restrict__ xyz, const float *__restrict__ new_xyz,
@@ -477,7 +471,7 @@ __global__ __launch_bounds__(256) void group_concat_cl_kernel(long long total, i
         if (ch < 3) v = xyz[((size_t)b * n + src) * 3 + ch] - new_xyz[bm * 3 + ch];   // pointnet2_utils.py:252
         else if (ch >= w) v = 0.0f;
         else v = feat_pm[((size_t)b * n + src) * c + (ch - 3)];
-        if constexpr (BF16) static_cast<unsigned short *>(out)[e] = f32_to_bf16_rne(v);
+        if constexpr (BF16) static_cast<unsigned short *>(out)[e] = f32_to_bf16(v);
         else static_cast<float *>(out)[e] = v;
     }
 }
@@ -513,15 +507,10 @@ __global__ __launch_bounds__(256) void group_concat_cl8_kernel(long long total8,
         for (int t = 0; t < 8; ++t) {
             const int ch = ch0 + t;
             if (ch < 3) v[t] = xyz[((size_t)b * n + src) * 3 + ch] - new_xyz[bm * 3 + ch];
-            else if (ch < w) v[t] = FB ? __uint_as_float((unsigned)fh[ch] << 16) : f[ch];
+            else if (ch < w) v[t] = FB ? bf16_to_f32(fh[ch]) : f[ch];
             else v[t] = 0.0f;
         }
-        uint4 o;
-        o.x = (unsigned)f32_to_bf16_rne(v[0]) | ((unsigned)f32_to_bf16_rne(v[1]) << 16);
-        o.y = (unsigned)f32_to_bf16_rne(v[2]) | ((unsigned)f32_to_bf16_rne(v[3]) << 16);
-        o.z = (unsigned)f32_to_bf16_rne(v[4]) | ((unsigned)f32_to_bf16_rne(v[5]) << 16);
-        o.w = (unsigned)f32_to_bf16_rne(v[6]) | ((unsigned)f32_to_bf16_rne(v[7]) << 16);
-        *reinterpret_cast<uint4 *>(out + e * 8) = o;
+        *reinterpret_cast<uint4 *>(out + e * 8) = pack_bf16x8(v);
     }
 }
 }  // namespace pdm
@@ -573,55 +562,9 @@ extern "C" int pdm_group_concat_cl_ld_f(void *stream, int b, int n, int m, int c
 
 // Backward of the channels-last form: grad (B, M, ns, 3+C) fp32 or bf16 -> grad_feat_pm (B, N, C) fp32, every element
 // written (zero where a point is in no group).  The scatter is inverted per cloud into CSR lists "source point <- grouped
-// slots" (counting sort in LDS, one workgroup per cloud); then one wave per source point adds up its slots' rows, lanes over
+// slots" (csr.hip: counting sort in LDS, one workgroup per cloud); then one wave per source point adds up its slots' rows, lanes over
 // channels: every row is read once, contiguously, nothing is atomic.
 namespace pdm {
-
-constexpr int GCL_THREADS = 1024;
-
-__global__ __launch_bounds__(GCL_THREADS) void gcl_csr_build_kernel(int ne, int n, const int *__restrict__ idx,
-                                                                   int *__restrict__ start_all, int *__restrict__ el_all) {
-    extern __shared__ int s_cnt[];   // n counters, then fill cursors
-    __shared__ int s_wave[GCL_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int *__restrict__ id = idx + (size_t)b * ne;
-    int *__restrict__ start = start_all + (size_t)b * (n + 1);
-    int *__restrict__ el = el_all + (size_t)b * ne;
-    for (int k = tid; k < n; k += GCL_THREADS) s_cnt[k] = 0;
-    __syncthreads();
-    for (int e = tid; e < ne; e += GCL_THREADS) {
-        const int k = id[e];
-        if (k >= 0 && k < n) atomicAdd(&s_cnt[k], 1);
-    }
-    __syncthreads();
-    const int chunk = (n + GCL_THREADS - 1) / GCL_THREADS;
-    const int k0 = tid * chunk, k1 = min(k0 + chunk, n);
-    int local = 0;
-    for (int k = k0; k < k1; ++k) local += s_cnt[k];
-    int incl = local;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int q = 0; q < wave; ++q) base += s_wave[q];
-    int run = base + incl - local;
-    for (int k = k0; k < k1; ++k) {
-        const int cnt = s_cnt[k];
-        start[k] = run;
-        s_cnt[k] = run;
-        run += cnt;
-    }
-    if (tid == GCL_THREADS - 1) start[n] = run;
-    __syncthreads();
-    for (int e = tid; e < ne; e += GCL_THREADS) {
-        const int k = id[e];
-        if (k < 0 || k >= n) continue;
-        el[atomicAdd(&s_cnt[k], 1)] = e;
-    }
-}
 
 // lpp = lanes per source point (a power of two <= 64, >= min(c, 64) rounded up): with few channels a wave serves 64 / lpp
 // points at once (SA1 has ONE feature channel: a wave per point left 63 lanes idle)
@@ -640,7 +583,7 @@ __global__ __launch_bounds__(256) void gcl_grad_kernel(int n, int c, int ne, int
         float acc = 0.0f;
         for (int p = s; p < e; ++p) {
             const size_t off = ((size_t)b * ne + el[p]) * w + 3 + ch;
-            if constexpr (BF16) acc += __uint_as_float((unsigned)static_cast<const unsigned short *>(grad)[off] << 16);
+            if constexpr (BF16) acc += bf16_to_f32(static_cast<const unsigned short *>(grad)[off]);
             else acc += static_cast<const float *>(grad)[off];
         }
         out_pm[((size_t)b * n + k) * c + ch] = acc;
@@ -689,8 +632,8 @@ __global__ __launch_bounds__(256) void gcl_grad_bf16x4_kernel(int n, int c, int 
 }  // namespace pdm
 
 extern "C" size_t pdm_group_concat_cl_grad_ws_bytes(int b, int n, int m, int nsample) {
-    if (b <= 0 || n <= 0 || m <= 0 || nsample <= 0) return 0;
-    return (size_t)b * ((size_t)(n + 1) + (size_t)m * nsample) * sizeof(int) + 64;
+    if (nsample <= 0) return 0;
+    return pdm::csr_workspace_bytes(pdm::CSR_ELEMENT, b, (long long)m * nsample, n);
 }
 
 // grad (B, M, ns, 3+C) fp32 / bf16 (grad_bf16) -> grad_feat_pm (B, N, C) fp32, fully written.  n <= 16384.
@@ -713,17 +656,8 @@ extern "C" int pdm_group_concat_cl_grad_ld(void *stream, int b, int n, int m, in
                 "group_concat_cl_grad: workspace of %zu bytes, need %zu", workspace_bytes,
                 pdm_group_concat_cl_grad_ws_bytes(b, n, m, nsample));
     const int ne = m * nsample;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15;
-    int *start = reinterpret_cast<int *>(p);
-    int *el = start + (size_t)b * (n + 1);
-    if ((size_t)n * sizeof(int) + 1024 > 64 * 1024) {   // dynamic + static LDS above the default 64 KB (n near 16384)
-        // (the kernel also holds a small static block: dynamic + static must stay within the 160 KB of a CU)
-        const int e = pdm::grant_lds(reinterpret_cast<const void *>(&pdm::gcl_csr_build_kernel), 128 * 1024);
-        PDM_REQUIRE(e == 0, PDM_E_TOOLARGE, "group_concat_cl_grad: cannot obtain %zu bytes of LDS", (size_t)n * sizeof(int));
-    }
-    hipLaunchKernelGGL(pdm::gcl_csr_build_kernel, dim3(b), dim3(pdm::GCL_THREADS), (size_t)n * sizeof(int), pdm::as_stream(stream), ne,
-                       n, idx, start, el);
-    int rc = pdm::check_launch("group_concat_cl_grad(csr)");
+    const pdm::CsrLists L = pdm::csr_carve(workspace, pdm::CSR_ELEMENT, b, ne, n);
+    int rc = pdm::csr_build_launch(stream, "group_concat_cl_grad(csr)", pdm::CSR_ELEMENT, b, ne, 1, n, idx, nullptr, L);
     if (rc) return rc;
     if (grad_bf16 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(grad) & 15) == 0) {   // 16-byte rows: 8-byte words, four occurrences in flight
         int l4 = 1;
@@ -731,7 +665,7 @@ extern "C" int pdm_group_concat_cl_grad_ld(void *stream, int b, int n, int m, in
         const int ppb4 = 4 * (64 / l4);
         const dim3 grid4((unsigned)((n + ppb4 - 1) / ppb4), (unsigned)b);
         hipLaunchKernelGGL(pdm::gcl_grad_bf16x4_kernel, grid4, dim3(256), 0, pdm::as_stream(stream), n, c, ne, ld, l4,
-                           static_cast<const uint2 *>(grad), start, el, grad_feat_pm);
+                           static_cast<const uint2 *>(grad), L.start, L.elem, grad_feat_pm);
         return pdm::check_launch("group_concat_cl_grad");
     }
     int lpp = 1;
@@ -739,8 +673,8 @@ extern "C" int pdm_group_concat_cl_grad_ld(void *stream, int b, int n, int m, in
     const int ppb = 4 * (64 / lpp);                                      // points per workgroup
     const dim3 grid((unsigned)((n + ppb - 1) / ppb), (unsigned)b);
     if (grad_bf16)
-        hipLaunchKernelGGL(pdm::gcl_grad_kernel<true>, grid, dim3(256), 0, pdm::as_stream(stream), n, c, ne, ld, lpp, grad, start, el, grad_feat_pm);
+        hipLaunchKernelGGL(pdm::gcl_grad_kernel<true>, grid, dim3(256), 0, pdm::as_stream(stream), n, c, ne, ld, lpp, grad, L.start, L.elem, grad_feat_pm);
     else
-        hipLaunchKernelGGL(pdm::gcl_grad_kernel<false>, grid, dim3(256), 0, pdm::as_stream(stream), n, c, ne, ld, lpp, grad, start, el, grad_feat_pm);
+        hipLaunchKernelGGL(pdm::gcl_grad_kernel<false>, grid, dim3(256), 0, pdm::as_stream(stream), n, c, ne, ld, lpp, grad, L.start, L.elem, grad_feat_pm);
     return pdm::check_launch("group_concat_cl_grad");
 }

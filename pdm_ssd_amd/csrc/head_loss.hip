@@ -13,6 +13,7 @@
 // Launch 1 counts the positives (and checks the classes against the mean-size table: the reference asserts there; here the box
 // loss turns NaN).  Launch 2 forms labels, loss partials (one pair per workgroup, folded in double in a fixed order by the
 // third, one-workgroup launch: bit-reproducible) and d L / d pred for both stacks, in the predictions' dtype.
+#include "bf16.h"
 #include "common.h"
 
 namespace pdm {
@@ -39,16 +40,10 @@ struct HeadLossArgs {
 };
 
 __device__ __forceinline__ float hl_load(const void *p, long long i, int bf16) {
-    return bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(p)[i] << 16) : static_cast<const float *>(p)[i];
-}
-__device__ __forceinline__ unsigned short hl_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
+    return bf16 ? bf16_to_f32(static_cast<const unsigned short *>(p)[i]) : static_cast<const float *>(p)[i];
 }
 __device__ __forceinline__ void hl_store(void *p, long long i, float v, int bf16) {
-    if (bf16) static_cast<unsigned short *>(p)[i] = hl_bf16(v);
+    if (bf16) static_cast<unsigned short *>(p)[i] = f32_to_bf16(v);
     else static_cast<float *>(p)[i] = v;
 }
 

@@ -9,7 +9,8 @@
 // 1e40 and compares a float candidate with strict '<' (:37, :44-55); float bests initialised to
 // +inf decide identically (every finite float is < 1e40 and < inf; inf and NaN are < neither) and
 // narrow to the same outputs ((float)1e40 == inf).
-#include "common.h"
+#include "bf16.h"
+#include "csr.h"
 
 namespace pdm {
 
@@ -186,156 +187,9 @@ __global__ __launch_bounds__(TIL_THREADS) void three_interpolate_grad_lds_kernel
     }
 }
 
-// ---- backward of three_interpolate without atomics in the inner loop -------------------------------------------------
-// LDS float atomics turned out to be the limit of the kernel above: ~270 GB/s of grad_out for every shape, i.e. one
-// ds_add_f32 lane every three cycles per CU.  The scatter is inverted once per (idx, weight) pair instead: per cloud a CSR
-// table "known point k <- its (unknown point j, weight) contributions" (counting sort, one workgroup per cloud), then
-//   grad_points[b, c, k] += sum_{(j, w) in list(k)} w * grad_out[b, c, j]
-// with the grad_out rows of a few channels staged in LDS (coalesced global reads, random LDS READS) and one thread per
-// known point.  Needs m <= 16384 (LDS histogram) and n <= 65535 (16-bit j).
-constexpr int TIC_THREADS = 1024;
-
-// ne = contributions per cloud, `per` of them per source row (three_interpolate: 3 per unknown point, with weights;
-// group_points: 1 per grouped slot, weight 1)
-__global__ __launch_bounds__(TIC_THREADS) void interp_csr_build_kernel(int ne, int per, int m, const int *__restrict__ idx,
-                                                                       const float *__restrict__ weight,
-                                                                       int *__restrict__ start_all,
-                                                                       unsigned short *__restrict__ ej_all,
-                                                                       float *__restrict__ ew_all) {
-    extern __shared__ int s_cnt[];   // m counters, then running cursors
-    __shared__ int s_wave[TIC_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int *__restrict__ id = idx + (size_t)b * ne;
-    const float *__restrict__ w = weight ? weight + (size_t)b * ne : nullptr;
-    int *__restrict__ start = start_all + (size_t)b * (m + 1);
-    unsigned short *__restrict__ ej = ej_all + (size_t)b * ne;
-    float *__restrict__ ew = ew_all + (size_t)b * ne;
-    for (int k = tid; k < m; k += TIC_THREADS) s_cnt[k] = 0;
-    __syncthreads();
-    for (int e = tid; e < ne; e += TIC_THREADS) {
-        const int k = id[e];
-        if (k >= 0 && k < m) atomicAdd(&s_cnt[k], 1);
-    }
-    __syncthreads();
-    // exclusive scan of the m counters: contiguous chunk per thread, wave scan, wave offsets
-    const int chunk = (m + TIC_THREADS - 1) / TIC_THREADS;
-    const int k0 = tid * chunk, k1 = min(k0 + chunk, m);
-    int local = 0;
-    for (int k = k0; k < k1; ++k) local += s_cnt[k];
-    int incl = local;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int q = 0; q < wave; ++q) base += s_wave[q];
-    int run = base + incl - local;
-    for (int k = k0; k < k1; ++k) {
-        const int cnt = s_cnt[k];
-        start[k] = run;
-        s_cnt[k] = run;      // becomes the fill cursor
-        run += cnt;
-    }
-    if (tid == TIC_THREADS - 1) start[m] = run;
-    __syncthreads();
-    for (int e = tid; e < ne; e += TIC_THREADS) {
-        const int k = id[e];
-        if (k < 0 || k >= m) continue;
-        const int pos = atomicAdd(&s_cnt[k], 1);
-        ej[pos] = (unsigned short)(e / per);
-        ew[pos] = w ? w[e] : 1.0f;
-    }
-}
-
-template <int TC>
-__global__ __launch_bounds__(TIC_THREADS) void interp_grad_csr_kernel(int c, int n, int ne, int m,
-                                                                      const float *__restrict__ grad_out,
-                                                                      const int *__restrict__ start_all,
-                                                                      const unsigned short *__restrict__ ej_all,
-                                                                      const float *__restrict__ ew_all,
-                                                                      float *__restrict__ grad_points) {
-    extern __shared__ float s_g[];   // TC x n
-    const int b = blockIdx.y, c0 = blockIdx.x * TC, tid = threadIdx.x;
-    const int nc = min(TC, c - c0);
-    const float *__restrict__ g = grad_out + ((size_t)b * c + c0) * n;
-    for (int e = tid; e < nc * n; e += TIC_THREADS) s_g[e] = g[e];   // nc consecutive rows are one contiguous block
-    __syncthreads();
-    const int *__restrict__ start = start_all + (size_t)b * (m + 1);
-    const unsigned short *__restrict__ ej = ej_all + (size_t)b * ne;
-    const float *__restrict__ ew = ew_all + (size_t)b * ne;
-    for (int k = tid; k < m; k += TIC_THREADS) {
-        const int s = start[k], e = start[k + 1];
-        float acc[TC];
-#pragma unroll
-        for (int ci = 0; ci < TC; ++ci) acc[ci] = 0.0f;
-        for (int p = s; p < e; ++p) {
-            const int j = ej[p];
-            const float w = ew[p];
-#pragma unroll
-            for (int ci = 0; ci < TC; ++ci)
-                if (ci < nc) acc[ci] += s_g[ci * n + j] * w;
-        }
-#pragma unroll
-        for (int ci = 0; ci < TC; ++ci)
-            if (ci < nc) grad_points[((size_t)b * c + c0 + ci) * m + k] += acc[ci];   // rows are exclusive to this workgroup
-    }
-}
-
 }  // namespace pdm
 
 using namespace pdm;
-
-// Shared by three_interpolate and group_points: rows of `row_len` floats per (cloud, channel) in grad_out, ne = per * rows'
-// contributions per cloud scattered onto m targets.  Workspace: csr_workspace_bytes(b, ne, m).
-namespace pdm {
-size_t csr_workspace_bytes(int b, long long ne, int m) {
-    if (b <= 0 || ne <= 0 || m <= 0) return 0;
-    return ((size_t)b * (m + 1) * sizeof(int) + 15) / 16 * 16 + ((size_t)b * ne * sizeof(unsigned short) + 15) / 16 * 16 +
-           (size_t)b * ne * sizeof(float) + 64;
-}
-bool csr_form_applies(int b, int row_len, long long ne, int m) {
-    return m >= 1 && m <= 16384 && row_len >= 1 && row_len <= 32768 && ne <= 0x7fffffffll / 4 && b <= 65535;
-}
-int csr_scatter_grad_launch(void *stream, const char *who, int b, int c, int row_len, int per, int m, const float *grad_out,
-                            const int *idx, const float *weight, float *grad_points, void *workspace) {
-    const int ne = row_len * per;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15;
-    int *start = reinterpret_cast<int *>(p);
-    p += ((size_t)b * (m + 1) * sizeof(int) + 15) / 16 * 16;
-    unsigned short *ej = reinterpret_cast<unsigned short *>(p);
-    p += ((size_t)b * ne * sizeof(unsigned short) + 15) / 16 * 16;
-    float *ew = reinterpret_cast<float *>(p);
-    if ((size_t)m * sizeof(int) + 1024 > 64 * 1024) {   // dynamic + static LDS above the default 64 KB (m near 16384)
-        // (the kernel also holds a small static block: dynamic + static must stay within the 160 KB of a CU)
-        const int e = grant_lds(reinterpret_cast<const void *>(&interp_csr_build_kernel), 128 * 1024);
-        PDM_REQUIRE(e == 0, PDM_E_TOOLARGE, "%s: cannot obtain %zu bytes of LDS", who, (size_t)m * sizeof(int));
-    }
-    hipLaunchKernelGGL(interp_csr_build_kernel, dim3(b), dim3(TIC_THREADS), (size_t)m * sizeof(int), as_stream(stream), ne, per, m,
-                       idx, weight, start, ej, ew);
-    int rc = check_launch(who);
-    if (rc) return rc;
-    // channel rows staged per workgroup: as many as fit 128 KB of LDS, at most 8
-    const int tc = row_len <= 4096 ? 8 : row_len <= 8192 ? 4 : row_len <= 16384 ? 2 : 1;
-#define PDM_TIC_LAUNCH(TCV, SLOT)                                                                                      \
-    do {                                                                                                               \
-        const size_t lds = (size_t)TCV * row_len * sizeof(float);                                                      \
-        if (lds > 64 * 1024) {   /* granted per function and per device (common.h) */                                  \
-            const int e = grant_lds(reinterpret_cast<const void *>(&interp_grad_csr_kernel<TCV>), 160 * 1024);         \
-            PDM_REQUIRE(e == 0, PDM_E_TOOLARGE, "%s: cannot obtain %zu bytes of LDS", who, lds);                       \
-        }                                                                                                              \
-        hipLaunchKernelGGL(interp_grad_csr_kernel<TCV>, dim3(divup(c, TCV), b), dim3(TIC_THREADS), lds, as_stream(stream), \
-                           c, row_len, ne, m, grad_out, start, ej, ew, grad_points);                                   \
-    } while (0)
-    if (tc == 8) PDM_TIC_LAUNCH(8, 0);
-    else if (tc == 4) PDM_TIC_LAUNCH(4, 1);
-    else if (tc == 2) PDM_TIC_LAUNCH(2, 2);
-    else PDM_TIC_LAUNCH(1, 3);
-#undef PDM_TIC_LAUNCH
-    return check_launch(who);
-}
-}  // namespace pdm
 
 // ---- rows form of the FP module's input (training path, csrc/train_gemm.hip consumes it) ------------------------------------
 // The reference forms cat([three_interpolate(known_feats, idx, weight), unknow_feats], dim=1) as a channel-major fp32 tensor
@@ -346,13 +200,7 @@ int csr_scatter_grad_launch(void *stream, const char *who, int b, int c, int row
 namespace pdm {
 
 __device__ __forceinline__ float icr_load(const void *p, size_t i, bool bf16) {
-    return bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(p)[i] << 16) : static_cast<const float *>(p)[i];
-}
-__device__ __forceinline__ unsigned short icr_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
+    return bf16 ? bf16_to_f32(static_cast<const unsigned short *>(p)[i]) : static_cast<const float *>(p)[i];
 }
 
 __global__ __launch_bounds__(256) void interp_concat_rows_kernel(long long total, int n, int m, int c2, int c1, int ld,
@@ -375,7 +223,7 @@ __global__ __launch_bounds__(256) void interp_concat_rows_kernel(long long total
         } else if (ch < c2 + c1) {
             v = icr_load(skip, (size_t)row * c1 + (ch - c2), skip_bf16);
         }
-        out[e] = icr_bf16(v);
+        out[e] = f32_to_bf16(v);
     }
 }
 
@@ -419,15 +267,12 @@ __global__ __launch_bounds__(256) void interp_concat_rows8_kernel(long long tota
                 v[t] = c < c1 ? icr_load(skip, (size_t)row * c1 + c, skip_bf16) : 0.0f;
             }
         }
-        uint4 o;
-        o.x = (unsigned)icr_bf16(v[0]) | ((unsigned)icr_bf16(v[1]) << 16); o.y = (unsigned)icr_bf16(v[2]) | ((unsigned)icr_bf16(v[3]) << 16);
-        o.z = (unsigned)icr_bf16(v[4]) | ((unsigned)icr_bf16(v[5]) << 16); o.w = (unsigned)icr_bf16(v[6]) | ((unsigned)icr_bf16(v[7]) << 16);
-        *reinterpret_cast<uint4 *>(out + e * 8) = o;
+        *reinterpret_cast<uint4 *>(out + e * 8) = pack_bf16x8(v);
     }
 }
 
 // d known[b, j, c] = sum over the CSR list of j of w * dx[b, i, c], c < C2: one wave per known point, lanes over channels,
-// every gradient row read contiguously, no global atomics (the terms of a point are added in LIST order, and interp_csr_build_kernel
+// every gradient row read contiguously, no global atomics (the terms of a point are added in LIST order, and the builder of csr.hip
 // fills the lists through an LDS atomic cursor: the last bits of a sum can differ between launches)
 template <bool OB>   // OB: dknown is written as bf16 (round to nearest even of the same fp32 sums) instead of fp32
 __global__ __launch_bounds__(256) void interp_rows_grad_kernel(int n, int m, int c2, int ld, int ne, const unsigned short *__restrict__ dx,
@@ -470,10 +315,7 @@ __global__ __launch_bounds__(256) void interp_rows_grad_kernel(int n, int m, int
             }
             for (; p < e; ++p) fma8(acc, ew[p], *reinterpret_cast<const uint4 *>(dxb + (size_t)ej[p] * ld + ch));
             if constexpr (OB) {
-                uint4 o;
-                o.x = (unsigned)icr_bf16(acc[0]) | ((unsigned)icr_bf16(acc[1]) << 16); o.y = (unsigned)icr_bf16(acc[2]) | ((unsigned)icr_bf16(acc[3]) << 16);
-                o.z = (unsigned)icr_bf16(acc[4]) | ((unsigned)icr_bf16(acc[5]) << 16); o.w = (unsigned)icr_bf16(acc[6]) | ((unsigned)icr_bf16(acc[7]) << 16);
-                *reinterpret_cast<uint4 *>(static_cast<unsigned short *>(dknown_v) + ((size_t)b * m + j) * c2 + ch) = o;
+                *reinterpret_cast<uint4 *>(static_cast<unsigned short *>(dknown_v) + ((size_t)b * m + j) * c2 + ch) = pack_bf16x8(acc);
             } else {
                 float *o = dknown + ((size_t)b * m + j) * c2 + ch;
                 *reinterpret_cast<float4 *>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -490,8 +332,8 @@ __global__ __launch_bounds__(256) void interp_rows_grad_kernel(int n, int m, int
         if (ch < c2) {
             float acc = 0.0f;
             for (int p = s; p < e; ++p)
-                acc = __fmaf_rn(ew[p], __uint_as_float((unsigned)dx[((size_t)b * n + ej[p]) * ld + ch] << 16), acc);
-            if constexpr (OB) static_cast<unsigned short *>(dknown_v)[((size_t)b * m + j) * c2 + ch] = icr_bf16(acc);
+                acc = __fmaf_rn(ew[p], bf16_to_f32(dx[((size_t)b * n + ej[p]) * ld + ch]), acc);
+            if constexpr (OB) static_cast<unsigned short *>(dknown_v)[((size_t)b * m + j) * c2 + ch] = f32_to_bf16(acc);
             else dknown[((size_t)b * m + j) * c2 + ch] = acc;
         }
     }
@@ -541,22 +383,11 @@ extern "C" int pdm_interp_concat_rows_grad_out(void *stream, int b, int n, int m
     if (b == 0 || m == 0 || c2 == 0) return 0;
     PDM_REQUIRE(dknown && workspace && (n == 0 || (dx && idx && weight)), PDM_E_BADARG, "interp_concat_rows_grad: null pointer");
     PDM_REQUIRE(m <= 16384 && n <= 65535 && b <= 65535, PDM_E_TOOLARGE, "interp_concat_rows_grad: m=%d (<= 16384), n=%d (<= 65535)", m, n);
-    PDM_REQUIRE(workspace_bytes >= csr_workspace_bytes(b, 3ll * n, m), PDM_E_BADARG, "interp_concat_rows_grad: workspace of %zu bytes, need %zu",
-                workspace_bytes, csr_workspace_bytes(b, 3ll * n, m));
+    PDM_REQUIRE(workspace_bytes >= pdm_three_interpolate_grad_ws_bytes(b, n, m), PDM_E_BADARG,
+                "interp_concat_rows_grad: workspace of %zu bytes, need %zu", workspace_bytes, pdm_three_interpolate_grad_ws_bytes(b, n, m));
     const int ne = 3 * n;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15;
-    int *start = reinterpret_cast<int *>(p);
-    p += ((size_t)b * (m + 1) * sizeof(int) + 15) / 16 * 16;
-    unsigned short *ej = reinterpret_cast<unsigned short *>(p);
-    p += ((size_t)b * ne * sizeof(unsigned short) + 15) / 16 * 16;
-    float *ew = reinterpret_cast<float *>(p);
-    if ((size_t)m * sizeof(int) + 1024 > 64 * 1024) {
-        const int e = grant_lds(reinterpret_cast<const void *>(&interp_csr_build_kernel), 128 * 1024);
-        PDM_REQUIRE(e == 0, PDM_E_TOOLARGE, "interp_concat_rows_grad: cannot obtain %zu bytes of LDS", (size_t)m * sizeof(int));
-    }
-    hipLaunchKernelGGL(interp_csr_build_kernel, dim3(b), dim3(TIC_THREADS), (size_t)m * sizeof(int), as_stream(stream), ne, 3, m, idx, weight,
-                       start, ej, ew);
-    int rc = check_launch("interp_concat_rows_grad(csr)");
+    const CsrLists L = csr_carve(workspace, CSR_ROW_WEIGHT, b, ne, m);
+    int rc = csr_build_launch(stream, "interp_concat_rows_grad(csr)", CSR_ROW_WEIGHT, b, ne, 3, m, idx, weight, L);
     if (rc) return rc;
     int lpp = 1;     // as in the kernel's eight-channel form: points per workgroup = 4 * 64 / lpp
     // the eight-channel form reads dx and writes dknown 16 bytes at a time: a sub-buffer at another offset takes the element form
@@ -568,14 +399,14 @@ extern "C" int pdm_interp_concat_rows_grad_out(void *stream, int b, int n, int m
     const int ppb = 4 * (64 / lpp);
     if (out_bf16)
         hipLaunchKernelGGL(interp_rows_grad_kernel<true>, dim3((unsigned)((m + ppb - 1) / ppb), (unsigned)b), dim3(256), 0, as_stream(stream), n, m, c2, ld, ne,
-                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown, vec8);
+                           static_cast<const unsigned short *>(dx), L.start, L.row, L.weight, dknown, vec8);
     else
         hipLaunchKernelGGL(interp_rows_grad_kernel<false>, dim3((unsigned)((m + ppb - 1) / ppb), (unsigned)b), dim3(256), 0, as_stream(stream), n, m, c2, ld, ne,
-                           static_cast<const unsigned short *>(dx), start, ej, ew, dknown, vec8);
+                           static_cast<const unsigned short *>(dx), L.start, L.row, L.weight, dknown, vec8);
     return check_launch("interp_concat_rows_grad");
 }
 
-extern "C" size_t pdm_three_interpolate_grad_ws_bytes(int b, int n, int m) { return csr_workspace_bytes(b, 3ll * n, m); }
+extern "C" size_t pdm_three_interpolate_grad_ws_bytes(int b, int n, int m) { return csr_workspace_bytes(CSR_ROW_WEIGHT, b, 3ll * n, m); }
 
 // pdm_three_interpolate_grad with a caller-provided workspace (pdm_three_interpolate_grad_ws_bytes(b, n, m) bytes): the
 // scatter is inverted into per-cloud CSR lists first, the accumulation then runs without atomics (same sums, different

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(PG_THREADS) void pdm_bin_kernel(int P, PgGrid g, in
                                                              int *__restrict__ tile_pts_all) {
     extern __shared__ int cnt[];  // ntiles counters, then reused as cursors
     __shared__ int wsum[PG_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int *__restrict__ tile_start = tile_start_all + (size_t)b * (ntiles + 1);
     int *__restrict__ tile_pts = tile_pts_all + (size_t)b * cap;
     for (int t = tid; t < ntiles; t += PG_THREADS) cnt[t] = 0;
@@ -99,31 +99,7 @@ __global__ __launch_bounds__(PG_THREADS) void pdm_bin_kernel(int P, PgGrid g, in
                 }
         }
         __syncthreads();
-        if (pass == 0) {
-            // exclusive scan of cnt -> tile_start, cnt becomes the running cursor
-            const int per = (ntiles + PG_THREADS - 1) / PG_THREADS;
-            const int c0 = tid * per, c1 = min(c0 + per, ntiles);
-            int local = 0;
-            for (int t = c0; t < c1; ++t) local += cnt[t];
-            int incl = local;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int v = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += v;
-            }
-            if (lane == 63) wsum[wave] = incl;
-            __syncthreads();
-            int base = 0;
-            for (int w = 0; w < wave; ++w) base += wsum[w];
-            int run = base + incl - local;
-            for (int t = c0; t < c1; ++t) {
-                const int v = cnt[t];
-                cnt[t] = run;
-                tile_start[t] = run;
-                run += v;
-            }
-            if (tid == PG_THREADS - 1) tile_start[ntiles] = run;
-            __syncthreads();
-        }
+        if (pass == 0) hist_to_cursors<PG_THREADS>(cnt, ntiles, wsum, tile_start);
     }
 }
 

@@ -83,12 +83,7 @@ __global__ __launch_bounds__(64 * PK_NCLS) void sa_pack_scan_kernel(PackJobs job
     for (int b0 = 0; b0 < nblocks; b0 += 64) {
         const int b = b0 + lane;
         const int v = b < nblocks ? bh[b * PK_NCLS + k] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        const int inc = wave_scan_incl(v);
         if (b < nblocks) bh[b * PK_NCLS + k] = run + inc - v;
         run += __shfl(inc, 63, 64);
     }

@@ -24,6 +24,7 @@
 //                    128 x 128 tile of dW for one slab of rows, slabs are summed in a fixed order (bit-reproducible).
 // Numerics = the contract the bf16-emulating checker states (oracle/cpu_detector.py): operands are bf16, products are
 // exact, accumulation is fp32, the forward / data-gradient result is rounded once to bf16, the weight gradient stays fp32.
+#include "bf16.h"
 #include "common.h"
 
 namespace pdm {
@@ -38,13 +39,6 @@ constexpr int TG_BK = 64;
 constexpr int TG_WR = 64;            // rows per stage of the weight-gradient kernel
 constexpr int TG_WPITCH = 320;       // bytes per LDS row there: 256 of data + 64 of pad (transposed reads conflict-free)
 
-__device__ __forceinline__ unsigned short tg_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ float tg_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 // two fp32 -> two bf16 (round to nearest even) in one instruction, v_cvt_pk_bf16_f32: `a` in the low half.  (The software
 // form costs ~8 VALU instructions per value; the forward kernel's epilogue was issue-bound on it: SQ_ACTIVE_INST_ANY 52 %.)
 typedef __bf16 tg_bf16x2 __attribute__((ext_vector_type(2)));
@@ -418,7 +412,7 @@ struct TgNtTile {
                     if (XF != 2 && a.bias) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            if (col0 + col + e < a.N) b4[e] = tg_f32(tg_bf16(a.bias[col0 + col + e]));
+                            if (col0 + col + e < a.N) b4[e] = bf16_to_f32(f32_to_bf16(a.bias[col0 + col + e]));
                     }
                     uint2 v;
                     v.x = tg_pack2(acc[i][j][4 * g] + b4[0], acc[i][j][4 * g + 1] + b4[1]);
@@ -867,11 +861,11 @@ __global__ __launch_bounds__(256) void tg_pack_weight_kernel(const float *__rest
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (Wb && e < (long long)rows_b * ldb) {
         const int n = (int)(e / ldb), k = (int)(e % ldb);
-        Wb[e] = (n < N && k < K) ? tg_bf16(W[(long long)n * K + k]) : (unsigned short)0;
+        Wb[e] = (n < N && k < K) ? f32_to_bf16(W[(long long)n * K + k]) : (unsigned short)0;
     }
     if (Wt && e < (long long)rows_t * ldt) {
         const int k = (int)(e / ldt), n = (int)(e % ldt);
-        Wt[e] = (k < K && n < N) ? tg_bf16(W[(long long)n * K + k]) : (unsigned short)0;
+        Wt[e] = (k < K && n < N) ? f32_to_bf16(W[(long long)n * K + k]) : (unsigned short)0;
     }
 }
 
@@ -889,11 +883,11 @@ __global__ __launch_bounds__(256) void tg_pack_weight_many_kernel(const TgPackJo
     if (e >= (long long)j.rows_to * j.cols_to) return;
     {
         const int n = (int)(e / j.cols_to), k = (int)(e % j.cols_to);
-        j.Wb[e] = (n < j.N && k < j.K) ? tg_bf16(j.W[(long long)n * j.K + k]) : (unsigned short)0;
+        j.Wb[e] = (n < j.N && k < j.K) ? f32_to_bf16(j.W[(long long)n * j.K + k]) : (unsigned short)0;
     }
     {
         const int k = (int)(e / j.rows_to), n = (int)(e % j.rows_to);
-        j.Wt[e] = (k < j.K && n < j.N) ? tg_bf16(j.W[(long long)n * j.K + k]) : (unsigned short)0;
+        j.Wt[e] = (k < j.K && n < j.N) ? f32_to_bf16(j.W[(long long)n * j.K + k]) : (unsigned short)0;
     }
 }
 

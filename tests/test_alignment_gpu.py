@@ -102,7 +102,7 @@ def test_scan_ball_query_scalar_staging(oracle, dev, monkeypatch, n, m, ns, mis,
 @pytest.mark.parametrize("ns,mis", [(6, {}), (16, {}), (16, {"idx": 4}), (16, {"xyz": 4, "new_xyz": 8, "idx": 12}), (6, {"idx": 8})],
                          ids=["ns6", "ns16", "ns16-idx+4", "ns16-all", "ns6-idx+8"])
 def test_grid_ball_query_row_stores(oracle, dev, monkeypatch, form, ns, mis):
-    """ball_query_grid.hip:608: the lane form writes a row with 16-byte stores only when nsample % 4 == 0 and idx is aligned."""
+    """ball_query_grid.hip:572: the lane form writes a row with 16-byte stores only when nsample % 4 == 0 and idx is aligned."""
     monkeypatch.setattr(ext, "GRID_MIN_N", 1)
     xyz, new = cached(("bq", 1000, 77), lambda: bq_clouds(1000, 77, 1077))
     old = lib().pdm_tune_bq_quad(form)
@@ -152,7 +152,7 @@ def gp_tune(variant, rpw=0, lsplit=0, threads=0, uq=0):
                                        ((8, 300, 64, 16), {"points": 4, "idx": 8, "out": 12})],
                          ids=["C7-n301-L165", "C8-n300-L1024", "points+4", "idx+4", "out+4", "all"])
 def test_group_points_small_shapes_every_variant(oracle, dev, shape, mis, tune):
-    """group_points.hip:355: 16-byte index loads and stores need L % 4 == 0 and aligned idx / out.  At these shapes (two
+    """group_points.hip:356: 16-byte index loads and stores need L % 4 == 0 and aligned idx / out.  At these shapes (two
     clouds, L < 4 n) every setting of pdm_tune_group_rows ends in the direct kernels: the dispatcher has no other choice."""
     C, n, L0, L1 = shape
     feat, idx = cached(("gp", shape), lambda: gp_inputs(2, C, n, L0, L1, C * n))
@@ -173,7 +173,7 @@ LDS_CASES = [
 
 @pytest.mark.parametrize("name,L0,L1,tune,mis", LDS_CASES, ids=[c[0] for c in LDS_CASES])
 def test_group_points_lds_forms(oracle, dev, name, L0, L1, tune, mis):
-    """group_points.hip:146/155/237/327: the LDS-staged kernels stage a workgroup's rows 16 bytes at a time only when their
+    """group_points.hip:147/156/238/328: the LDS-staged kernels stage a workgroup's rows 16 bytes at a time only when their
     size and address allow it (63-float rows: most workgroups take the scalar loop, those of every fourth cloud the vector
     one; the last workgroup of a cloud has 5 rows, an odd float count) and gather with 16-byte index loads / stores only
     for L % 4 == 0 and aligned idx / out.  The rows kernel is only chosen on aligned pointers with L % 4 == 0; every variant
@@ -187,7 +187,7 @@ def test_group_points_lds_forms(oracle, dev, name, L0, L1, tune, mis):
 @pytest.mark.parametrize("ns", [6, 16])
 @pytest.mark.parametrize("mis", sweep("xyz", "new_xyz", "features", "idx", "out"))
 def test_group_concat_direct_kernels(oracle, dev, ns, mis):
-    """group_points.hip:419: query_group_v4_kernel needs nsample % 4 == 0 and aligned idx / out, else the element kernel."""
+    """group_points.hip:420: query_group_v4_kernel needs nsample % 4 == 0 and aligned idx / out, else the element kernel."""
     B, n, m, C = 2, 1000, 77, 5
     xyz, new = cached(("bq", n, m), lambda: bq_clouds(n, m, n + m))
     feat = cached(("gc_feat", C, n), lambda: np.random.default_rng(3).standard_normal((B, C, n)).astype(np.float32))
@@ -209,7 +209,7 @@ def test_group_concat_direct_kernels(oracle, dev, ns, mis):
     (8, 11, 1, 0, {}), (8, 16, 1, 0, {"xyz": 4, "new_xyz": 8, "feat": 12, "idx": 4, "out": 14}), (8, 11, 0, 0, {}), (8, 11, 0, 0, {"out": 4}),
 ], ids=["cl8", "cl8-out+2", "cl8-out+8", "cl8-bf16feat", "cl8-bf16feat+2", "ld11-bf16", "ld16-all", "ld11-fp32", "ld11-fp32-out+4"])
 def test_group_concat_channels_last_rows(oracle, dev, C, ld, out_bf16, feat_bf16, mis):
-    """group_points.hip:555: eight bf16 channels per 16-byte store need ld % 8 == 0 and an aligned out; ld = 11 and an out at
+    """group_points.hip:544: eight bf16 channels per 16-byte store need ld % 8 == 0 and an aligned out; ld = 11 and an out at
     + 2 / + 8 bytes take the element kernel.  Bit-exact: the oracle's fp32 value rounded to nearest even, zeros in the padding."""
     B, n, m, ns = 2, 1000, 77, 16
     xyz, new = cached(("bq", n, m), lambda: bq_clouds(n, m, n + m))
@@ -238,7 +238,7 @@ def test_group_concat_channels_last_rows(oracle, dev, C, ld, out_bf16, feat_bf16
                                           (8, 11, 1, {}), (8, 11, 1, {"grad": 2}), (5, 8, 0, {}), (5, 8, 0, {"grad": 4}), (5, 8, 0, {"out": 8})],
                          ids=["bf16x4", "bf16x4-grad+2", "bf16x4-grad+8", "bf16x4-all", "ld11-bf16", "ld11-bf16-grad+2", "fp32", "fp32-grad+4", "fp32-out+8"])
 def test_group_concat_channels_last_grad(oracle, dev, C, ld, bf16, mis):
-    """group_points.hip:728: a bf16 gradient is read as 8-byte words only when ld % 8 == 0 and grad is 16-byte aligned; ld = 11,
+    """pdm_group_concat_cl_grad_ld (group_points.hip): a bf16 gradient is read as 8-byte words only when ld % 8 == 0 and grad is 16-byte aligned; ld = 11,
     a grad at + 2 / + 8 / + 14 bytes and an fp32 grad take gcl_grad_kernel.  Bound of tests/test_modules_gpu.py (1e-4 of the
     oracle's scatter-add: the CSR lists are filled through an LDS atomic cursor, the fp32 order is not fixed)."""
     B, n, m, ns = 2, 1000, 77, 16
@@ -463,7 +463,7 @@ ICR = [(12, 5, 0, 1, 24, {}), (12, 5, 0, 1, 24, {"known": 8, "skip": 2, "idx": 4
 
 @pytest.mark.parametrize("c2,c1,kb,sb,ld,mis", ICR, ids=[f"c2={c[0]}-c1={c[1]}-ld={c[4]}-{'bf16' if c[2] else 'fp32'}-" + ("-".join(f"{k}+{o}" for k, o in c[5].items()) or "aligned") for c in ICR])
 def test_interp_concat_rows_and_grad(oracle, dev, c2, c1, kb, sb, ld, mis):
-    """interpolate.hip:509: eight channels per thread need c2 % 8 == 0, ld % 8 == 0 and aligned known / out; c2 = 12 and a
+    """pdm_interp_concat_rows (interpolate.hip): eight channels per thread need c2 % 8 == 0, ld % 8 == 0 and aligned known / out; c2 = 12 and a
     known / out at + 2 or + 8 bytes take the element kernel.  Forward bit-exact against the oracle's pinned fma order rounded to
     bf16; ld = 17 and 20 (c2 = 16, c1 = 1: rows that start at 2-byte granularity) are the other side of ld % 8.  The
     backward's eight-channel form has the same conditions on c2, ld, dx and dknown, decided on the host.  Its CSR lists are filled through an LDS atomic cursor, so the order of a known point's terms — and with
@@ -649,7 +649,7 @@ def pdm_case(C):
 @pytest.mark.parametrize("C", [8, 6])
 @pytest.mark.parametrize("mis", sweep("xyz", "feat", "sh", "inv2s2", "grid", "wsum"))
 def test_pdm_gather_bev(oracle, dev, C, mis):
-    """pdm_gather.hip:330: a point's C features are staged 16 bytes at a time when C % 4 == 0 and feat is aligned.  A pure copy into LDS: bit-equal to the aligned call; 1e-4 of the oracle's scale
+    """pdm_gather.hip:306: a point's C features are staged 16 bytes at a time when C % 4 == 0 and feat is aligned.  A pure copy into LDS: bit-equal to the aligned call; 1e-4 of the oracle's scale
     (tests/test_pdm_gpu.py)."""
     from pdm_ssd_amd import pdm_ops
     cell, kernel, degree = (3.2, 3.2, 4.0), (3, 3, 1), 2

@@ -1039,6 +1039,41 @@ int pdm_pillar_scatter(void *stream, int P, int C, const float *pillar_features,
 int pdm_pillar_scatter_grad(void *stream, int P, int C, const float *grad_canvas, const int *voxel_coords, int B, int nx, int ny,
                             int nz, float *grad_features);
 
+/* The anchor head (csrc/anchor_head.hip, DESIGN.md "Anchor head"): AxisAlignedTargetAssigner.assign_targets, the head's three
+ * loss terms with their gradients, and generate_predicted_boxes, each for the whole batch on the caller's stream with no host
+ * read and no float atomics on a result: two calls give the same bits.  Anchors are ordered y, x, slot (A = H W A_loc); a map
+ * is (B, A_loc * width, H, W), channel = slot * width + column, fp32 or bf16 with any element strides.
+ *
+ * pdm_anchor_targets: anchors (A, 7) fp32; set_of_slot = HOST array of A_loc anchor sets; set_of_class = HOST array of
+ *   num_class + 1 ints, [g] = the set of global class g (1-based) or -1; matched / unmatched = HOST arrays of num_sets
+ *   thresholds; gt_boxes (B, M, cols >= 8) fp32, class last, NOT modified; M <= 1024 (PDM_E_TOOLARGE beyond).  A box takes part
+ *   against the anchors of its class's set only; overlap = nearest-BEV IoU in fp32 (DESIGN.md gives the operation order).
+ *   -> box_cls_labels (B, A) int32, box_reg_targets (B, A, 7), reg_weights (B, A), num_pos (B) int32 = #labels > 0, all written.
+ *   workspace >= pdm_anchor_targets_workspace_bytes(B, M, num_sets), 8-byte aligned.
+ * pdm_anchor_head_loss: maps = HOST array of 3 device pointers [cls (width num_class), box (7), dir (num_dir_bins <= 8) | NULL];
+ *   bf16 = HOST array of 3 flags; strides = HOST array of 3 x 4 element strides (b, c, y, x); anchor_rot = HOST array of A_loc
+ *   rotations; code_weights = HOST array of 7.  out[0..2] = cls / loc / dir term, each summed over the sample divided by
+ *   max(num_pos, 1), then by B, times its weight; grad_cls / grad_box / grad_dir fp32 (B, channels, H, W) contiguous = d term / d
+ *   map, every element written.  workspace >= pdm_anchor_head_loss_workspace_bytes(B, H, W), 8-byte aligned.
+ * pdm_anchor_decode: maps = HOST array of 2 device pointers [box, dir | NULL], bf16 / strides alike -> batch_box_preds
+ *   (B, A, 7) fp32: residual decode, arg-max direction bin (lower bin on equal logits), heading folded into the bin's period. */
+/* align: any (two cells along W per access only where W is even, the strides allow it and the pointers are aligned; the
+ * decode moves its staged pieces 16 bytes at a time only where the table and the output are 16-byte aligned). */
+size_t pdm_anchor_targets_workspace_bytes(int B, int M, int num_sets);
+int pdm_anchor_targets(void *stream, int B, int M, int cols, int A, int A_loc, int num_sets, int num_class, const float *anchors,
+                       const int *set_of_slot, const int *set_of_class, const float *matched, const float *unmatched,
+                       const float *gt_boxes, int norm_by_num_examples, int *box_cls_labels, float *box_reg_targets,
+                       float *reg_weights, int *num_pos, void *workspace, size_t workspace_bytes);
+size_t pdm_anchor_head_loss_workspace_bytes(int B, int H, int W);
+int pdm_anchor_head_loss(void *stream, int B, int H, int W, int A_loc, int num_class, int num_dir_bins, const void *const *maps,
+                         const int *bf16, const long long *strides, const int *labels, const float *targets, const int *num_pos,
+                         const float *anchor_rot, const float *code_weights, float cls_weight, float loc_weight, float dir_weight,
+                         float dir_offset, float beta, float alpha, float gamma, float *out, float *grad_cls, float *grad_box,
+                         float *grad_dir, void *workspace, size_t workspace_bytes);
+int pdm_anchor_decode(void *stream, int B, int H, int W, int A_loc, int num_dir_bins, const void *const *maps, const int *bf16,
+                      const long long *strides, const float *anchors, float dir_offset, float dir_limit_offset,
+                      float *batch_box_preds);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

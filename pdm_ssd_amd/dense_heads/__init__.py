@@ -1,4 +1,6 @@
 """Heads of the detector, registered by NAME as /root/reference/pcdet/models/dense_heads/__init__.py:11-21 does."""
+from .anchor_head_single import AnchorHeadSingle
+from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
 from .pdm_heatmap_head import PDMHeatmapHead
 from .point_head_box import PointHeadBox
@@ -9,4 +11,6 @@ __all__ = {
     'PointHeadBox': PointHeadBox,
     'PDMHeatmapHead': PDMHeatmapHead,
     'CenterHead': CenterHead,
+    'AnchorHeadTemplate': AnchorHeadTemplate,
+    'AnchorHeadSingle': AnchorHeadSingle,
 }

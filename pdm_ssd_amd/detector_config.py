@@ -109,6 +109,34 @@ CENTER_PILLAR_CFG = {
 }
 CENTER_PILLAR_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['FEATURE_MAP_STRIDE'] = 2
 
+# PointPillars: DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone -> AnchorHeadSingle on the 384-channel map.  VFE,
+# scatter and 2-D backbone are CENTER_PILLAR_CFG's; the head values are the upstream project's published KITTI PointPillars
+# settings (the dense head of its tools/cfgs/kitti_models/pointpillar.yaml) restated as a dict: 248 x 216 cells x 6 anchors =
+# 321 408 anchors per sample.
+POINT_PILLAR_CFG = {
+    'NAME': 'PointPillar',
+    'VFE': copy.deepcopy(CENTER_PILLAR_CFG['VFE']),
+    'MAP_TO_BEV': copy.deepcopy(CENTER_PILLAR_CFG['MAP_TO_BEV']),
+    'BACKBONE_2D': copy.deepcopy(CENTER_PILLAR_CFG['BACKBONE_2D']),
+    'DENSE_HEAD': {'NAME': 'AnchorHeadSingle', 'CLASS_AGNOSTIC': False, 'USE_DIRECTION_CLASSIFIER': True, 'DIR_OFFSET': 0.78539,
+                   'DIR_LIMIT_OFFSET': 0.0, 'NUM_DIR_BINS': 2,
+                   'ANCHOR_GENERATOR_CONFIG': [
+                       {'class_name': 'Car', 'anchor_sizes': [[3.9, 1.6, 1.56]], 'anchor_rotations': [0, 1.57],
+                        'anchor_bottom_heights': [-1.78], 'align_center': False, 'feature_map_stride': 2,
+                        'matched_threshold': 0.6, 'unmatched_threshold': 0.45},
+                       {'class_name': 'Pedestrian', 'anchor_sizes': [[0.8, 0.6, 1.73]], 'anchor_rotations': [0, 1.57],
+                        'anchor_bottom_heights': [-0.6], 'align_center': False, 'feature_map_stride': 2,
+                        'matched_threshold': 0.5, 'unmatched_threshold': 0.35},
+                       {'class_name': 'Cyclist', 'anchor_sizes': [[1.76, 0.6, 1.73]], 'anchor_rotations': [0, 1.57],
+                        'anchor_bottom_heights': [-0.6], 'align_center': False, 'feature_map_stride': 2,
+                        'matched_threshold': 0.5, 'unmatched_threshold': 0.35}],
+                   'TARGET_ASSIGNER_CONFIG': {'NAME': 'AxisAlignedTargetAssigner', 'POS_FRACTION': -1.0, 'SAMPLE_SIZE': 512,
+                                              'NORM_BY_NUM_EXAMPLES': False, 'MATCH_HEIGHT': False, 'BOX_CODER': 'ResidualCoder'},
+                   'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0, 'dir_weight': 0.2,
+                                                    'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}}},
+    'POST_PROCESSING': copy.deepcopy(CENTER_PILLAR_CFG['POST_PROCESSING']),
+}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -151,4 +179,12 @@ def build_center_pillar(model_cfg=None, num_point_features=4, dataset=None):
     CenterHead, on pillar_dataset() unless another dataset namespace is given."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(CENTER_PILLAR_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillar_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_point_pillar(model_cfg=None, num_point_features=4, dataset=None):
+    """PointPillar from POINT_PILLAR_CFG (or a dict like it): DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone ->
+    AnchorHeadSingle, on pillar_dataset() unless another dataset namespace is given."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(POINT_PILLAR_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillar_dataset(num_point_features) if dataset is None else dataset)

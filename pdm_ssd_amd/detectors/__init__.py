@@ -6,12 +6,14 @@ from .detector3d_template import BACKBONES_2D, BACKBONES_3D, MAP_TO_BEV, VFE, De
 from .centerpoint import CenterPoint
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
+from .pointpillar import PointPillar
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'PDMSSD': PDMSSD,
     'PointRCNN': PointRCNN,
     'CenterPoint': CenterPoint,
+    'PointPillar': PointPillar,
 }
 
 

@@ -1,4 +1,5 @@
 """Geometry helpers of the RoI heads (behaviour of /root/reference/pcdet/utils/common_utils.py)."""
+import numpy as np
 import torch
 
 
@@ -13,3 +14,9 @@ def rotate_points_along_z(points, angle):
     out[:, :, 0] = x * c - y * s
     out[:, :, 1] = x * s + y * c
     return out
+
+
+def limit_period(val, offset=0.5, period=np.pi):
+    """val folded into [-offset * period, (1 - offset) * period) (the reference's common_utils.limit_period on tensors)"""
+    turns = torch.floor(val / period + offset)
+    return val - turns * period

@@ -70,6 +70,16 @@ class WeightedSmoothL1Loss(nn.Module):
         return out
 
 
+class WeightedCrossEntropyLoss(nn.Module):
+    """Cross-entropy with one weight per anchor: input (B, #anchors, #classes) logits; target either (B, #anchors) class
+    indices or, as the reference passes it (loss_utils.py:183-208), the same shape as input one-hot; weights (B, #anchors)
+    -> (B, #anchors) unreduced."""
+
+    def forward(self, input, target, weights):
+        index = target if target.dim() == input.dim() - 1 else target.argmax(dim=-1)
+        return F.cross_entropy(input.flatten(0, 1), index.flatten().long(), reduction='none').view_as(weights) * weights
+
+
 def neg_loss_cornernet(pred, gt, mask=None):
     """Penalty-reduced pixel focal loss of the heat-map head.  pred / gt (B, C, H, W) in (0, 1) / [0, 1]: peaks
     (gt == 1) contribute (1-p)^2 log p, every other cell (1-gt)^4 p^2 log(1-p); the sum is negated and divided by the

@@ -1074,6 +1074,50 @@ int pdm_anchor_decode(void *stream, int B, int H, int W, int A_loc, int num_dir_
                       const long long *strides, const float *anchors, float dir_offset, float dir_limit_offset,
                       float *batch_box_preds);
 
+/* The voxel path (csrc/sparse_conv.hip, csrc/sparse_conv_mfma.hip, DESIGN.md "Voxel path"): dynamic voxels with means, the
+ * rulebook of a sparse 3-D convolution, the convolution on the exact f32 MFMA, and the dense canvas.  No host loop, sort, hash
+ * or float atomic: every result is a function of the input alone, bit for bit.  A cell's key is
+ * ((b * nx + x) * ny + y) * nz + z as a 64-bit value; a grid may hold up to 2^35 cells (PDM_E_TOOLARGE beyond), row counts and
+ * rows x offsets must fit int32.  Indices are int32 rows (b, z, y, x).
+ *
+ * pdm_voxel_assign: points (N, C1) fp32 rows (batch_idx, x, y, z, ...), any row order.  cell = floor((v - v0) / size) in fp32
+ *   with an IEEE division on x, y and z; a row is kept iff all three cells are in range (NaN drops) and 0 <= batch_idx < B.
+ *   Voxels are numbered in ascending key order.  Outputs at capacity cap = min(N, cells): kept_idx (N) kept rows in input
+ *   order, unq_inv (N) their voxel, voxel_coords (cap, 4) = (b, cz, cy, cx), voxel_count (cap), voxel_mean (cap, C1 - 1) =
+ *   float(double(sum of llrint(v * 2^20)) * 2^-20 / count) of every column, record (2) = {N', P}.  workspace >=
+ *   pdm_voxel_assign_workspace_bytes, 8-byte aligned.  N = 0 is valid.
+ * pdm_sparse_sites, then pdm_sparse_rulebook on the same workspace (>= pdm_sparse_rulebook_workspace_bytes, 8-byte aligned)
+ *   and the same geometry: in_indices (P_in, 4) distinct sites in any row order on the grid (B, D, H, W); kernel, stride and
+ *   padding per axis (z, y, x), at most 27 offsets.  subm: the output sites are the input rows, the neighbour at offset k is
+ *   the row at coord + k - K / 2 (stride 1, padding unused).  Otherwise the output grid is (in + 2 p - k) / s + 1 per axis,
+ *   site o exists iff an input lies at o s - p + k for some k, and sites ascend in the key of the output grid.
+ *   pdm_sparse_sites writes record[0] = P_out (the caller's one host read for a strided convolution); pdm_sparse_rulebook
+ *   writes out_indices (P_out, 4) (strided only; may be null for subm) and nbr (P_out, kvol), kx fastest: input row or -1.
+ * pdm_sparse_conv: out (P_out, Cout) = epilogue(sum over k ascending of W[k] x[nbr[:, k]]); epilogue = * scale + shift (both or
+ *   neither), + residual (P_out, Cout), ReLU, each optional, in this order.  Cin in {3..8, 16, 32, 64, 128}, Cout in {16, 32,
+ *   64, 128} (PDM_E_BADARG otherwise).  wpack: pdm_sparse_conv_packed_floats floats, [k][kb][nb][lane][j] =
+ *   W[k][cin = 16 kb + 4 (lane >> 4) + j][cout = 16 nb + (lane & 15)], zero past Cin.
+ * pdm_sparse_to_dense: features (P, C), indices (P, 4) -> out (B, C, D, H, W), every element written by one launch behind a
+ *   cell table built in the workspace (>= pdm_sparse_to_dense_workspace_bytes); B D H W must fit int32, B <= 65535. */
+/* align: any (4-byte accesses, 16-byte ones only where the pointer allows), except wpack: 16 B (PDM_E_BADARG otherwise). */
+size_t pdm_voxel_assign_workspace_bytes(int N, int C1, int B, int nx, int ny, int nz);
+int pdm_voxel_assign(void *stream, int N, int C1, const float *points, int B, int nx, int ny, int nz, float x0, float y0, float z0,
+                     float vx, float vy, float vz, int *kept_idx, int *unq_inv, int *voxel_coords, int *voxel_count,
+                     float *voxel_mean, int *record, void *workspace, size_t workspace_bytes);
+size_t pdm_sparse_rulebook_workspace_bytes(int P_in, int B, int D, int H, int W, int kd, int kh, int kw, int sd, int sh, int sw, int pd,
+                                           int ph, int pw, int subm);
+int pdm_sparse_sites(void *stream, int P_in, const int *in_indices, int B, int D, int H, int W, int kd, int kh, int kw, int sd, int sh,
+                     int sw, int pd, int ph, int pw, int subm, int *record, void *workspace, size_t workspace_bytes);
+int pdm_sparse_rulebook(void *stream, int P_in, const int *in_indices, int P_out, int B, int D, int H, int W, int kd, int kh, int kw,
+                        int sd, int sh, int sw, int pd, int ph, int pw, int subm, int *out_indices, int *nbr, void *workspace,
+                        size_t workspace_bytes);
+size_t pdm_sparse_conv_packed_floats(int kvol, int Cin, int Cout);
+int pdm_sparse_conv(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+                    const float *scale, const float *shift, const float *residual, int relu, float *out);
+size_t pdm_sparse_to_dense_workspace_bytes(int B, int D, int H, int W);
+int pdm_sparse_to_dense(void *stream, int P, int C, const float *features, const int *indices, int B, int D, int H, int W, float *out,
+                        void *workspace, size_t workspace_bytes);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -1,6 +1,9 @@
-"""Pillars -> BEV canvas, registered by NAME as the reference's pcdet/models/backbones_2d/map_to_bev/__init__.py does."""
+"""Pillars or an encoded sparse tensor -> BEV canvas, registered by NAME as the reference's
+pcdet/models/backbones_2d/map_to_bev/__init__.py does."""
+from .height_compression import HeightCompression
 from .pointpillar_scatter import PointPillarScatter
 
 __all__ = {
     'PointPillarScatter': PointPillarScatter,
+    'HeightCompression': HeightCompression,
 }

@@ -1,0 +1,7 @@
+"""3-D backbones of the voxel family, registered by NAME as the reference's pcdet/models/backbones_3d/__init__.py does."""
+from .spconv_backbone import SparseBasicBlock, VoxelBackBone8x, VoxelResBackBone8x, post_act_block
+
+__all__ = {
+    'VoxelBackBone8x': VoxelBackBone8x,
+    'VoxelResBackBone8x': VoxelResBackBone8x,
+}

@@ -73,6 +73,22 @@ __device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
     return base + incl - v;
 }
 
+// Exclusive scan of n totals in global memory in place by ONE workgroup of NT threads (the middle launch of a multi-launch
+// scan: pillar.hip, sparse_conv.hip); returns the grand total to every thread.  s_wave: NT / 64 ints of LDS.
+template <int NT>
+__device__ __forceinline__ int scan_totals(int n, int *__restrict__ v, int *s_wave) {
+    int carry = 0;
+    for (int base = 0; base < n; base += NT) {
+        const int i = base + threadIdx.x;
+        const int x = i < n ? v[i] : 0;
+        int total;
+        const int excl = block_scan<NT>(x, s_wave, &total);
+        if (i < n) v[i] = carry + excl;
+        carry += total;
+    }
+    return carry;
+}
+
 // Exclusive scan of an LDS histogram in place: counts become running cursors (the fill positions of a counting sort).
 // Every thread of the workgroup (NT threads) calls it after the barrier that completes hist[0..ncells); a thread owns a
 // contiguous chunk of cells (a compile-time ncells gives constant-trip loops, which unroll).  start_out, when not null,
@@ -102,6 +118,14 @@ __device__ __forceinline__ void hist_to_cursors(int *hist, int ncells, int *s_wa
     }
     if (start_out && threadIdx.x == NT - 1) start_out[ncells] = run;   // the last thread ends on the total
     __syncthreads();
+}
+
+// Cell of one coordinate as the reference's dynamic voxel encoders compute it (pillar.hip, sparse_conv.hip):
+// floor((x - x0) / v) in fp32 with an IEEE division (not a reciprocal multiply: 0.16 is no power of two).  Returns -1
+// outside [0, n) and for NaN.
+__device__ __forceinline__ int cell_1d(float x, float x0, float v, int n) {
+    const float c = floorf(__fdiv_rn(__fsub_rn(x, x0), v));
+    return (c >= 0.0f && c < (float)n) ? (int)c : -1;
 }
 
 // Squared distance with the rounding sequence pinned:

@@ -23,18 +23,11 @@ struct PlGrid {
     float x0, y0, vx, vy;
 };
 
-// Cell of one coordinate as the reference computes it: floor((x - x0) / v) in fp32 with an IEEE division (not a reciprocal
-// multiply: 0.16 is no power of two).  Returns -1 outside [0, n) and for NaN.
-__device__ __forceinline__ int pl_cell_1d(float x, float x0, float v, int n) {
-    const float c = floorf(__fdiv_rn(__fsub_rn(x, x0), v));
-    return (c >= 0.0f && c < (float)n) ? (int)c : -1;
-}
-
 // key of the row's cell, or -1 when the row is dropped (outside in x or y, a sample index outside [0, B), NaN); z is not tested
 __device__ __forceinline__ int pl_key(const float *__restrict__ row, const PlGrid &g) {
     const float bf = row[0];
     if (!(bf >= 0.0f && bf < (float)g.B)) return -1;
-    const int cx = pl_cell_1d(row[1], g.x0, g.vx, g.nx), cy = pl_cell_1d(row[2], g.y0, g.vy, g.ny);
+    const int cx = cell_1d(row[1], g.x0, g.vx, g.nx), cy = cell_1d(row[2], g.y0, g.vy, g.ny);
     if (cx < 0 || cy < 0) return -1;
     return ((int)bf * g.nx + cx) * g.ny + cy;
 }
@@ -81,30 +74,16 @@ __global__ __launch_bounds__(PL_T) void pl_cell_total_kernel(int ncell, const in
     if (threadIdx.x == 0) { ctile_occ[blockIdx.x] = s_occ; ctile_cnt[blockIdx.x] = s_cnt; }
 }
 
-// exclusive scan of n tile totals in place by one workgroup; returns the grand total to every thread
-__device__ int pl_scan_totals(int n, int *__restrict__ v, int *s_wave) {
-    int carry = 0;
-    for (int base = 0; base < n; base += PL_T) {
-        const int i = base + threadIdx.x;
-        const int x = i < n ? v[i] : 0;
-        int total;
-        const int excl = block_scan<PL_T>(x, s_wave, &total);
-        if (i < n) v[i] = carry + excl;
-        carry += total;
-    }
-    return carry;
-}
-
 // workgroup 0: the point tiles -> record[0] = N'; workgroup 1: the cell tiles -> record[1] = P, seg_start[P] = N'
 __global__ __launch_bounds__(PL_T) void pl_scan_totals_kernel(int ntp, int *__restrict__ ptile, int ntc, int *__restrict__ ctile_occ,
                                                               int *__restrict__ ctile_cnt, int *__restrict__ record, int *__restrict__ seg_start) {
     __shared__ int s_wave[PL_T / 64];
     if (blockIdx.x == 0) {
-        const int kept = pl_scan_totals(ntp, ptile, s_wave);
+        const int kept = scan_totals<PL_T>(ntp, ptile, s_wave);
         if (threadIdx.x == 0) record[0] = kept;
     } else {
-        const int P = pl_scan_totals(ntc, ctile_occ, s_wave);
-        const int kept = pl_scan_totals(ntc, ctile_cnt, s_wave);
+        const int P = scan_totals<PL_T>(ntc, ctile_occ, s_wave);
+        const int kept = scan_totals<PL_T>(ntc, ctile_cnt, s_wave);
         if (threadIdx.x == 0) { record[1] = P; seg_start[P] = kept; }
     }
 }

@@ -137,6 +137,36 @@ POINT_PILLAR_CFG = {
     'POST_PROCESSING': copy.deepcopy(CENTER_PILLAR_CFG['POST_PROCESSING']),
 }
 
+# SECOND: DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle on the KITTI voxel grid
+# (VOXEL_SIZE, GRID_SIZE, range [0, -40, -3, 70.4, 40, 1]): the encoded tensor is 128 channels x 2 heights on 200 x 176 cells
+# of 0.4 m (stride 8).  The 2-D backbone and head values are the upstream project's published KITTI SECOND settings (its
+# tools/cfgs/kitti_models/second.yaml) restated as a dict; the anchors are POINT_PILLAR_CFG's at feature_map_stride 8.  The
+# voxel backbone runs in eval mode only.
+SECOND_CFG = {
+    'NAME': 'SECONDNet',
+    'VFE': {'NAME': 'DynamicMeanVFE'},
+    'BACKBONE_3D': {'NAME': 'VoxelBackBone8x'},
+    'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256},
+    'BACKBONE_2D': {'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [5, 5], 'LAYER_STRIDES': [1, 2], 'NUM_FILTERS': [128, 256],
+                    'UPSAMPLE_STRIDES': [1, 2], 'NUM_UPSAMPLE_FILTERS': [256, 256]},
+    'DENSE_HEAD': copy.deepcopy(POINT_PILLAR_CFG['DENSE_HEAD']),
+    'POST_PROCESSING': copy.deepcopy(POINT_PILLAR_CFG['POST_PROCESSING']),
+}
+for _anchor_cfg in SECOND_CFG['DENSE_HEAD']['ANCHOR_GENERATOR_CONFIG']:
+    _anchor_cfg['feature_map_stride'] = 8
+
+# CenterPoint on voxels: SECOND_CFG's front with the residual backbone, then CenterHead at FEATURE_MAP_STRIDE 8 (the head of
+# CENTER_PDM_CFG, whose map has the same 200 x 176 cells).
+CENTER_VOXEL_CFG = {
+    'NAME': 'CenterPoint',
+    'VFE': {'NAME': 'DynamicMeanVFE'},
+    'BACKBONE_3D': {'NAME': 'VoxelResBackBone8x'},
+    'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256},
+    'BACKBONE_2D': copy.deepcopy(SECOND_CFG['BACKBONE_2D']),
+    'DENSE_HEAD': copy.deepcopy(CENTER_PDM_CFG['DENSE_HEAD']),
+    'POST_PROCESSING': copy.deepcopy(CENTER_PDM_CFG['POST_PROCESSING']),
+}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -188,3 +218,27 @@ def build_point_pillar(model_cfg=None, num_point_features=4, dataset=None):
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(POINT_PILLAR_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillar_dataset(num_point_features) if dataset is None else dataset)
+
+
+def voxel_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None, grid_size=None):
+    """The voxel detectors' dataset namespace: the KITTI range on VOXEL_SIZE / GRID_SIZE unless other values are given."""
+    return SimpleNamespace(class_names=CLASS_NAMES, grid_size=list(GRID_SIZE if grid_size is None else grid_size),
+                           voxel_size=list(VOXEL_SIZE if voxel_size is None else voxel_size),
+                           point_cloud_range=list(synthetic.KITTI_RANGE if point_cloud_range is None else point_cloud_range),
+                           point_feature_encoder=SimpleNamespace(num_point_features=num_point_features))
+
+
+def build_second(model_cfg=None, num_point_features=4, dataset=None):
+    """SECONDNet from SECOND_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone ->
+    AnchorHeadSingle, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(SECOND_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_center_voxel(model_cfg=None, num_point_features=4, dataset=None):
+    """CenterPoint from CENTER_VOXEL_CFG (or a dict like it): DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression ->
+    BaseBEVBackbone -> CenterHead, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(CENTER_VOXEL_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

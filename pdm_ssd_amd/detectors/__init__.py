@@ -7,6 +7,7 @@ from .centerpoint import CenterPoint
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
+from .second_net import SECONDNet
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
@@ -14,6 +15,7 @@ __all__ = {
     'PointRCNN': PointRCNN,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,
+    'SECONDNet': SECONDNet,
 }
 
 

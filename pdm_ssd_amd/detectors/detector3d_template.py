@@ -4,21 +4,22 @@ Contract restated from /root/reference/pcdet/models/detectors/detector3d_templat
 `build_<slot>` per slot, modules chosen by `NAME` from registry dicts, `model_info_dict` threading channel counts),
 :178-263 (post_processing: per-sample class-agnostic NMS over the head's boxes) and :330-359 (shape-filtered
 checkpoint loading).  The reference's template cannot be imported on this platform (it pulls in spconv,
-pcdet/utils/spconv_utils.py:3).  The vfe, map_to_bev and backbone_2d slots build the pillar family (DynamicPillarVFE ->
-PointPillarScatter -> BaseBEVBackbone), which needs no spconv; a NAME outside the registries (MeanVFE, ...) and the pfe
-slot are refused.  The roi_head slot builds the point-based RoI heads of roi_heads/ (PointRCNN's second stage).
+pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
+(DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and, in eval mode, the voxel family (DynamicMeanVFE ->
+VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
+outside the registries (MeanVFE, PillarVFE, ...) and the pfe slot are refused.  The roi_head slot builds the point-based RoI heads of roi_heads/ (PointRCNN's second stage).
 """
 import torch
 import torch.nn as nn
 
-from .. import backbones_2d, dense_heads, roi_heads, vfe
+from .. import backbones_2d, backbones_3d, dense_heads, roi_heads, vfe
 from ..backbones_2d import map_to_bev
 from ..iou3d_nms import iou3d_nms_utils
 from ..pdm_neck import PDMNeck
 from ..pointnet2_backbone import PointNet2MSG
 
 # registries keyed by NAME, as pcdet/models/backbones_3d/__init__.py:10-22 and map_to_bev/__init__.py:5-10
-BACKBONES_3D = {'PointNet2MSG': PointNet2MSG}
+BACKBONES_3D = {'PointNet2MSG': PointNet2MSG, **backbones_3d.__all__}
 MAP_TO_BEV = {'PDMNeck': PDMNeck, **map_to_bev.__all__}
 VFE = {k: v for k, v in vfe.__all__.items() if k != 'VFETemplate'}
 BACKBONES_2D = dict(backbones_2d.__all__)

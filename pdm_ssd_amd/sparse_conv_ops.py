@@ -1,0 +1,164 @@
+"""The voxel path's device operators (csrc/sparse_conv.hip, csrc/sparse_conv_mfma.hip): points -> dynamic voxels with
+means (voxel_assign), the rulebook of a sparse 3-D convolution (rulebook), the convolution itself on the exact f32 MFMA
+(sparse_conv) and the dense canvas of a sparse tensor (to_dense).  An occupancy bitmap with scanned popcounts numbers
+voxels and output sites in ascending key order: no host loop, no sort, no hash, no float atomics, so every result is a
+function of the input alone and two runs give the same bits.  Eval mode only: nothing here has a gradient yet.
+
+Host reads: voxel_assign() copies the two ints {N', P} to the host, and a STRIDED rulebook() copies the one int P_out;
+a submanifold rulebook, sparse_conv() and to_dense() read nothing.  HOST_READS counts the copies.
+
+The torch formulations these stand for (torch.unique + scatter_mean, and per offset index_select -> mm -> index_add_) are
+what the tests and tools/sparse_conv_rate.py compare with.
+"""
+from collections import namedtuple
+
+import torch
+
+from . import _native
+
+HOST_READS = 0              # device-to-host copies this module has made
+CIN_SUPPORTED = (3, 4, 5, 6, 7, 8, 16, 32, 64, 128)
+COUT_SUPPORTED = (16, 32, 64, 128)
+
+Voxels = namedtuple('Voxels', ['kept_idx', 'unq_inv', 'voxel_coords', 'voxel_count', 'voxel_mean', 'num_kept', 'num_voxels'])
+Rulebook = namedtuple('Rulebook', ['out_indices', 'nbr', 'out_shape', 'kernel_size', 'subm'])
+
+
+def _triple(v):
+    return (int(v),) * 3 if isinstance(v, int) else tuple(int(x) for x in v)
+
+
+@torch.no_grad()
+def voxel_assign(points, batch_size, point_cloud_range, voxel_size, grid_size):
+    """points (N, 1 + C) fp32 rows (batch_idx, x, y, z, ...) in any row order -> Voxels (pdm_voxel_assign):
+      kept_idx (N') int32       the rows whose cell is inside the grid on x, y and z, in input order: the reference's points[mask]
+      unq_inv (N') int32        the voxel of each kept row
+      voxel_coords (P, 4)       int32 (b, cz, cy, cx); voxels ascend in ((b nx + cx) ny + cy) nz + cz (torch.unique's order)
+      voxel_count (P) int32, voxel_mean (P, C) = float(double(sum of llrint(v 2^20)) 2^-20 / count) of every column
+    cell = floor((v - v0) / size) in fp32 with an IEEE division.  The outputs are allocated at capacity and sliced after ONE
+    device-to-host copy of {N', P}."""
+    global HOST_READS
+    assert points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] >= 4, \
+        'points: fp32 (N, 1 + C) rows (batch_idx, x, y, z, ...) on the GPU'
+    points = points if points.is_contiguous() else points.contiguous()
+    nx, ny, nz = (int(v) for v in grid_size)
+    N, C1, B, dev = points.shape[0], points.shape[1], int(batch_size), points.device
+    nbytes = _native.lib().pdm_voxel_assign_workspace_bytes(N, C1, B, nx, ny, nz)
+    cap = min(N, B * nx * ny * nz) if nbytes else 0     # (0: the call below rejects the sizes; nothing is allocated for it)
+    i32 = dict(dtype=torch.int32, device=dev)
+    kept_idx, unq_inv = (torch.empty(N, **i32) for _ in range(2))
+    voxel_coords = torch.empty((cap, 4), **i32)
+    voxel_count = torch.empty(cap, **i32)
+    voxel_mean = torch.empty((cap, C1 - 1), dtype=torch.float32, device=dev)
+    record = torch.empty(2, **i32)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    _native.call("pdm_voxel_assign", _native.stream(dev), N, C1, points.data_ptr(), B, nx, ny, nz, *(float(v) for v in point_cloud_range[:3]),
+                 *(float(v) for v in voxel_size[:3]), kept_idx.data_ptr(), unq_inv.data_ptr(), voxel_coords.data_ptr(), voxel_count.data_ptr(),
+                 voxel_mean.data_ptr(), record.data_ptr(), ws.data_ptr(), nbytes)
+    HOST_READS += 1
+    n_kept, P = (int(v) for v in record.cpu().tolist())
+    return Voxels(kept_idx[:n_kept], unq_inv[:n_kept], voxel_coords[:P], voxel_count[:P], voxel_mean[:P], n_kept, P)
+
+
+def conv_out_shape(spatial_shape, kernel_size, stride=1, padding=0, subm=False):
+    """(D, H, W) of the output grid: the input's for a submanifold convolution, else (in + 2 p - k) // s + 1 per axis"""
+    k, s, p = _triple(kernel_size), _triple(stride), _triple(padding)
+    if subm:
+        return tuple(int(v) for v in spatial_shape)
+    return tuple((int(n) + 2 * p[d] - k[d]) // s[d] + 1 for d, n in enumerate(spatial_shape))
+
+
+@torch.no_grad()
+def rulebook(indices, batch_size, spatial_shape, kernel_size, stride=1, padding=0, subm=False):
+    """indices (P, 4) int32 (b, z, y, x), distinct sites in any row order on the grid spatial_shape = (D, H, W) -> Rulebook
+    (pdm_sparse_sites, pdm_sparse_rulebook):
+      out_indices (P_out, 4)   subm: `indices` itself (the output sites are the input rows, in input row order); strided: the
+                               sites o for which some offset k has an input at o s - p + k, ascending in the key
+                               ((b W' + x) H' + y) D' + z of the output grid (spconv's own order comes from a hash)
+      nbr (P_out, kvol) int32  the input row under every offset, (kz, ky, kx) ascending with kx fastest, or -1; subm: the row
+                               at coord + k - K // 2 (stride 1, padding unused, as spconv)
+    Neighbours never cross a sample and never wrap from the end of a grid row into the next.  ONE host read (P_out) for a
+    strided convolution, none for a submanifold one."""
+    global HOST_READS
+    assert indices.is_cuda and indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4, \
+        'indices: int32 (P, 4) rows (b, z, y, x) on the GPU'
+    indices = indices if indices.is_contiguous() else indices.contiguous()
+    k, s, p = _triple(kernel_size), _triple(stride), _triple(padding)
+    if subm:
+        s = (1, 1, 1)
+    D, H, W = (int(v) for v in spatial_shape)
+    P, B, dev = indices.shape[0], int(batch_size), indices.device
+    geom = (B, D, H, W, *k, *s, *p, 1 if subm else 0)
+    nbytes = _native.lib().pdm_sparse_rulebook_workspace_bytes(P, *geom)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    record = torch.empty(1, dtype=torch.int32, device=dev)
+    _native.call("pdm_sparse_sites", _native.stream(dev), P, indices.data_ptr(), *geom, record.data_ptr(), ws.data_ptr(), nbytes)
+    kvol = k[0] * k[1] * k[2]
+    if subm:
+        P_out, out_indices = P, indices
+    else:
+        HOST_READS += 1
+        P_out = int(record.cpu())
+        out_indices = torch.empty((P_out, 4), dtype=torch.int32, device=dev)
+    nbr = torch.empty((P_out, kvol), dtype=torch.int32, device=dev)
+    _native.call("pdm_sparse_rulebook", _native.stream(dev), P, indices.data_ptr(), P_out, *geom,
+                 None if subm else out_indices.data_ptr(), nbr.data_ptr(), ws.data_ptr(), nbytes)
+    return Rulebook(out_indices, nbr, conv_out_shape((D, H, W), k, s, p, subm), k, bool(subm))
+
+
+def pack_weight(weight):
+    """weight (Cout, kz, ky, kx, Cin) (spconv 2.x's layout) -> the kernel's packed form, a flat fp32 tensor
+    [k][kb][nb][lane][j] = W[cout = 16 nb + (lane & 15)][k][cin = 16 kb + 4 (lane >> 4) + j], zero past Cin: the A fragments
+    of mfma_f32_16x16x4f32 in the order the kernel reads them.  Device arithmetic only."""
+    cout, cin = weight.shape[0], weight.shape[-1]
+    if cin not in CIN_SUPPORTED or cout not in COUT_SUPPORTED:
+        raise ValueError(f'sparse_conv: {cin} -> {cout} channels; Cin in {CIN_SUPPORTED}, Cout in {COUT_SUPPORTED}')
+    w = weight.detach().float().reshape(cout, -1, cin)
+    kvol, nkb, nb = w.shape[1], (cin + 15) // 16, cout // 16
+    w = torch.nn.functional.pad(w, (0, 16 * nkb - cin))                        # (cout, kvol, 16 nkb)
+    w = w.reshape(nb, 16, kvol, nkb, 4, 4).permute(2, 3, 0, 4, 1, 5)           # (kvol, nkb, nb, g, i, j)
+    out = w.contiguous().reshape(-1)
+    assert out.numel() == _native.lib().pdm_sparse_conv_packed_floats(kvol, cin, cout)
+    return out
+
+
+@torch.no_grad()
+def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residual=None, relu=False, out=None):
+    """out[i, :] = epilogue(sum over k ascending of W[k] features[nbr[i, k], :]) (pdm_sparse_conv): features (P_in, cin) fp32,
+    nbr (P_out, kvol) int32, wpack = pack_weight(weight); epilogue = * scale + shift (the folded BatchNorm, both or neither),
+    + residual (P_out, cout), ReLU.  Output-stationary on the exact f32 MFMA, no atomics: two runs and a graph replay give
+    the same bits.  No host read."""
+    assert features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[1] == cin, tuple(features.shape)
+    assert nbr.dtype == torch.int32 and nbr.dim() == 2
+    features, nbr = features.contiguous(), nbr.contiguous()
+    P_out, kvol = nbr.shape
+    if out is None:
+        out = torch.empty((P_out, cout), dtype=torch.float32, device=features.device)
+    assert out.shape == (P_out, cout) and out.is_contiguous() and out.dtype == torch.float32
+    if residual is not None:
+        assert residual.shape == (P_out, cout) and residual.dtype == torch.float32
+        residual = residual.contiguous()
+    opt = [None if t is None else t.detach().float().contiguous() for t in (scale, shift)]
+    _native.call("pdm_sparse_conv", _native.stream(features), P_out, features.shape[0], kvol, cin, cout, features.data_ptr(), nbr.data_ptr(),
+                 wpack.data_ptr(), *(None if t is None else t.data_ptr() for t in opt), None if residual is None else residual.data_ptr(),
+                 1 if relu else 0, out.data_ptr())
+    return out
+
+
+@torch.no_grad()
+def to_dense(features, indices, batch_size, spatial_shape, out=None):
+    """features (P, C) fp32, indices (P, 4) int32 (b, z, y, x) -> (B, C, D, H, W): SparseConvTensor.dense().  One launch
+    writes every element, zeros included, behind a small cell table (pdm_sparse_to_dense).  No host read."""
+    assert features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[0] == indices.shape[0]
+    assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4
+    features, indices = features.contiguous(), indices.contiguous()
+    D, H, W = (int(v) for v in spatial_shape)
+    B, (P, C), dev = int(batch_size), features.shape, features.device
+    if out is None:
+        out = torch.empty((B, C, D, H, W), dtype=torch.float32, device=dev)
+    assert out.shape == (B, C, D, H, W) and out.is_contiguous() and out.dtype == torch.float32
+    nbytes = _native.lib().pdm_sparse_to_dense_workspace_bytes(B, D, H, W)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    _native.call("pdm_sparse_to_dense", _native.stream(dev), P, C, features.data_ptr(), indices.data_ptr(), B, D, H, W, out.data_ptr(),
+                 ws.data_ptr(), nbytes)
+    return out

@@ -1,0 +1,159 @@
+"""A small stand-in for spconv 2.x's `spconv.pytorch` names on the device operators of sparse_conv_ops, so that the voxel
+backbones read like the reference's: SparseConvTensor, SubMConv3d, SparseConv3d, SparseSequential, SparseModule.  Weights
+keep spconv 2.x's layout (Cout, kz, ky, kx, Cin) and its state_dict keys (weight, bias).
+
+Eval mode only.  A convolution followed by BatchNorm1d and ReLU inside a SparseSequential is ONE pdm_sparse_conv launch (the
+BatchNorm folded into the epilogue on the device); a module in training mode, or an input that requires grad, raises
+NotImplementedError: the convolution's gradients and BatchNorm over active rows are the next step.  SparseInverseConv3d is
+not built.
+
+A rulebook is built once per indice_key per forward and shared by the layers that name the key (the tensors of one forward
+share one indice_dict), as spconv shares them.  Row orders: a submanifold convolution keeps its input's rows; a strided one
+numbers its output sites in ascending key order of the output grid, which is build-defined (spconv's comes from a hash).
+"""
+import math
+
+import torch
+import torch.nn as nn
+
+from .. import sparse_conv_ops
+
+NEXT_STEP = ("the voxel path runs in eval mode only: the sparse convolution's data and weight gradients and BatchNorm over "
+             "active rows are the next step")
+
+
+class SparseConvTensor:
+    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None):
+        """features (P, C) fp32, indices (P, 4) int32 (b, z, y, x), spatial_shape (D, H, W)"""
+        self.features = features
+        self.indices = indices
+        self.spatial_shape = [int(v) for v in spatial_shape]
+        self.batch_size = int(batch_size)
+        self.indice_dict = {} if indice_dict is None else indice_dict      # indice_key -> sparse_conv_ops.Rulebook
+
+    def replace_feature(self, feature):
+        return SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict)
+
+    def dense(self):
+        """(B, C, D, H, W), zeros where no site is active: one launch writes every element"""
+        return sparse_conv_ops.to_dense(self.features, self.indices, self.batch_size, self.spatial_shape)
+
+
+def replace_feature(out, new_features):
+    return out.replace_feature(new_features)
+
+
+class SparseModule(nn.Module):
+    """marks a module that takes and returns a SparseConvTensor"""
+
+
+def fold_norm(norm, bias, cout, like):
+    """(scale, shift) of `conv bias -> eval BatchNorm1d` as one multiply-add per channel, device arithmetic only:
+    scale = gamma rsqrt(var + eps), shift = beta - mean scale + bias scale; without a norm (1, bias); (None, None) for neither"""
+    if norm is None:
+        return (None, None) if bias is None else (torch.ones_like(bias), bias)
+    gamma = norm.weight if norm.weight is not None else torch.ones(cout, dtype=like.dtype, device=like.device)
+    scale = gamma * torch.rsqrt(norm.running_var + norm.eps)
+    shift = (norm.bias if norm.bias is not None else 0) - norm.running_mean * scale
+    if bias is not None:
+        shift = shift + bias * scale
+    return scale, shift
+
+
+class SparseConvolution(SparseModule):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, indice_key=None, subm=False):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size = sparse_conv_ops._triple(kernel_size)
+        self.stride = sparse_conv_ops._triple(stride)
+        self.padding = sparse_conv_ops._triple(padding)
+        self.indice_key = indice_key
+        self.subm = subm
+        self.weight = nn.Parameter(torch.empty(out_channels, *self.kernel_size, in_channels))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self._cache = {}        # 'pack' / 'fold' -> (parameter versions, tensors)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight.view(self.out_channels, -1), a=math.sqrt(5))
+        if self.bias is not None:
+            bound = 1 / math.sqrt(self.in_channels * self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2])
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def _cached(self, slot, sources, make):
+        """make() once per version of the source tensors (in-place updates, load_state_dict and .to() all change the key),
+        as train_gemm.py caches its packed pairs"""
+        key = tuple((t.data_ptr(), t._version) for t in sources if t is not None)
+        hit = self._cache.get(slot)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                hit = (key, make())
+            self._cache[slot] = hit
+        return hit[1]
+
+    def get_rulebook(self, x):
+        rb = x.indice_dict.get(self.indice_key) if self.indice_key is not None else None
+        if rb is not None:
+            assert rb.subm == self.subm and rb.kernel_size == self.kernel_size and (not self.subm or rb.nbr.shape[0] == x.indices.shape[0]), \
+                f'indice_key {self.indice_key}: another convolution geometry built this rulebook'
+            return rb
+        rb = sparse_conv_ops.rulebook(x.indices, x.batch_size, x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)
+        if self.indice_key is not None:
+            x.indice_dict[self.indice_key] = rb
+        return rb
+
+    def forward(self, x, norm=None, relu=False, residual=None):
+        """x -> SparseConvTensor of epilogue(conv(x)): one launch.  norm: an eval BatchNorm1d folded into the epilogue;
+        residual: (P_out, Cout) added behind it; relu last."""
+        if self.training or (norm is not None and norm.training) or x.features.requires_grad:
+            raise NotImplementedError(NEXT_STEP)
+        assert x.features.shape[1] == self.in_channels, (tuple(x.features.shape), self.in_channels)
+        rb = self.get_rulebook(x)
+        wpack = self._cached('pack', [self.weight], lambda: sparse_conv_ops.pack_weight(self.weight))
+        sources = [self.bias] + ([norm.weight, norm.bias, norm.running_mean, norm.running_var] if norm is not None else [])
+        scale, shift = self._cached('fold', sources, lambda: fold_norm(norm, self.bias, self.out_channels, self.weight))
+        out = sparse_conv_ops.sparse_conv(x.features, rb.nbr, wpack, self.in_channels, self.out_channels, scale, shift, residual, relu)
+        return SparseConvTensor(out, rb.out_indices, rb.out_shape, x.batch_size, x.indice_dict)
+
+
+class SubMConv3d(SparseConvolution):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None, **kwargs):
+        assert dilation == 1 and groups == 1, 'dilation and groups are not built'
+        super().__init__(in_channels, out_channels, kernel_size, 1, padding, bias, indice_key, subm=True)
+
+
+class SparseConv3d(SparseConvolution):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None, **kwargs):
+        assert dilation == 1 and groups == 1, 'dilation and groups are not built'
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, subm=False)
+
+
+class SparseSequential(SparseModule, nn.Sequential):
+    """nn.Sequential over SparseConvTensors: sparse modules take the tensor, plain nn modules its features.  In eval mode
+    a convolution takes the BatchNorm1d and the ReLU behind it into its own launch."""
+
+    def forward(self, x):
+        mods = list(self)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, SparseConvolution):
+                norm = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm1d) else None
+                j = i + 1 + (norm is not None)
+                relu = j < len(mods) and isinstance(mods[j], nn.ReLU)
+                x = m(x, norm=norm, relu=relu)
+                i = j + relu
+                continue
+            if isinstance(m, SparseModule):
+                x = m(x)
+            elif isinstance(x, SparseConvTensor):
+                if self.training or x.features.requires_grad:
+                    raise NotImplementedError(NEXT_STEP)
+                x = x.replace_feature(m(x.features))
+            else:
+                x = m(x)
+            i += 1
+        return x
+
+
+__all__ = ['SparseConvTensor', 'SparseModule', 'SparseSequential', 'SubMConv3d', 'SparseConv3d', 'replace_feature']

@@ -124,6 +124,42 @@ def host_array(ctype, values):
     return (ctype * max(len(values), 1))(*values)
 
 
+def check_map(name, t, B, H, W, channels=None):
+    """A head's map as an operator takes it: fp32 or bf16 (B, C, H, W) on the GPU with any strides; C = channels when given."""
+    assert t.is_cuda and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16), f'{name}: fp32 or bf16 (B, C, H, W) on the GPU'
+    if channels is None:
+        assert t.shape[0] == B and t.shape[2] == H and t.shape[3] == W, f'{name}: {tuple(t.shape)}'
+    else:
+        assert tuple(t.shape) == (B, channels, H, W), f'{name}: {tuple(t.shape)}, expected {(B, channels, H, W)}'
+
+
+def map_tables(maps, slots=None):
+    """The host tables an entry point takes for a list of maps (csrc/loss_kit.h MapRef): device pointers, bf16 flags and
+    4 element strides (b, c, y, x) per entry.  A None entry, and the padding up to `slots` entries, is a null pointer with
+    flag 0 and zero strides."""
+    maps = list(maps)
+    if slots is not None:
+        assert len(maps) <= slots, f'{len(maps)} maps for {slots} slots'
+        maps += [None] * (slots - len(maps))
+    ptrs = host_array(ctypes.c_void_p, [None if t is None else t.data_ptr() for t in maps])
+    bf = host_array(ctypes.c_int, [0 if t is None else int(t.dtype == torch.bfloat16) for t in maps])
+    st = host_array(ctypes.c_longlong, [s for t in maps for s in ((0, 0, 0, 0) if t is None else t.stride())])
+    return ptrs, bf, st
+
+
+def channel_tables(maps):
+    """map_tables' sibling for an entry point that takes every channel of the maps as a (B, H, W) plane of its own, in
+    order: the planes' device pointers, bf16 flags and 3 element strides (b, y, x) per plane."""
+    ptrs, bf, st = [], [], []
+    for t in maps:
+        sb, sc, sh, sw = t.stride()
+        for c in range(t.shape[1]):
+            ptrs.append(t.data_ptr() + c * sc * t.element_size())
+            bf.append(int(t.dtype == torch.bfloat16))
+            st += [sb, sh, sw]
+    return host_array(ctypes.c_void_p, ptrs), host_array(ctypes.c_int, bf), host_array(ctypes.c_longlong, st)
+
+
 # Cooperating-workgroup FPS calls (n > 16384) whose status word has not been read yet: (workspace, b, n, event).
 # The word is read without stalling the caller: when a later call finds the event complete, or in fps_check().
 _fps_pending = []

@@ -49,36 +49,23 @@ def anchor_targets(anchors, set_of_slot, set_of_class, matched, unmatched, gt_bo
     return labels, targets, weights, num_pos
 
 
-def _check_map(name, t, B, H, W, channels):
-    assert t.is_cuda and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16), f'{name}: fp32 or bf16 (B, C, H, W) on the GPU'
-    assert tuple(t.shape) == (B, channels, H, W), f'{name}: {tuple(t.shape)}, expected {(B, channels, H, W)}'
-
-
-def _map_tables(maps, slots):
-    ptrs = _native.host_array(ctypes.c_void_p, [None if t is None else t.data_ptr() for t in maps])
-    bf = _native.host_array(ctypes.c_int, [0 if t is None else int(t.dtype == torch.bfloat16) for t in maps])
-    st = _native.host_array(ctypes.c_longlong, [s for t in maps for s in ((0, 0, 0, 0) if t is None else t.stride())])
-    assert len(maps) == slots
-    return ptrs, bf, st
-
-
 class _AnchorHeadLoss(Function):
     @staticmethod
     def forward(ctx, labels, targets, num_pos, anchor_rot, code_weights, scalars, num_class, num_dir_bins, cls_map, box_map, dir_map):
         B, _, H, W = box_map.shape
         A_loc = len(anchor_rot)
         assert 1 <= A_loc <= MAX_SLOTS and len(code_weights) == 7
-        _check_map('cls_preds', cls_map, B, H, W, A_loc * num_class)
-        _check_map('box_preds', box_map, B, H, W, A_loc * 7)
+        _native.check_map('cls_preds', cls_map, B, H, W, A_loc * num_class)
+        _native.check_map('box_preds', box_map, B, H, W, A_loc * 7)
         if dir_map is not None:
             assert 1 <= num_dir_bins <= MAX_DIR_BINS, f'NUM_DIR_BINS {num_dir_bins}: 1 .. {MAX_DIR_BINS}'
-            _check_map('dir_cls_preds', dir_map, B, H, W, A_loc * num_dir_bins)
+            _native.check_map('dir_cls_preds', dir_map, B, H, W, A_loc * num_dir_bins)
         A = H * W * A_loc
         assert labels.shape == (B, A) and labels.dtype == torch.int32 and targets.shape == (B, A, 7) and targets.dtype == torch.float32
         assert num_pos.shape == (B,) and num_pos.dtype == torch.int32
         labels, targets, num_pos = labels.contiguous(), targets.contiguous(), num_pos.contiguous()
         dev = box_map.device
-        ptrs, bf, st = _map_tables([cls_map, box_map, dir_map], 3)
+        ptrs, bf, st = _native.map_tables([cls_map, box_map, dir_map], 3)
         out = torch.empty(3, dtype=torch.float32, device=dev)
         g_cls = torch.empty(cls_map.shape, dtype=torch.float32, device=dev)
         g_box = torch.empty(box_map.shape, dtype=torch.float32, device=dev)
@@ -124,14 +111,14 @@ def anchor_decode(box_preds, dir_cls_preds, anchors, num_dir_bins=2, dir_offset=
     B, ch, H, W = box_preds.shape
     assert ch % 7 == 0
     A_loc = ch // 7
-    _check_map('box_preds', box_preds, B, H, W, A_loc * 7)
+    _native.check_map('box_preds', box_preds, B, H, W, A_loc * 7)
     if dir_cls_preds is not None:
         assert 1 <= num_dir_bins <= MAX_DIR_BINS, f'NUM_DIR_BINS {num_dir_bins}: 1 .. {MAX_DIR_BINS}'
-        _check_map('dir_cls_preds', dir_cls_preds, B, H, W, A_loc * num_dir_bins)
+        _native.check_map('dir_cls_preds', dir_cls_preds, B, H, W, A_loc * num_dir_bins)
     assert anchors.is_cuda and anchors.dtype == torch.float32 and tuple(anchors.shape) == (H * W * A_loc, 7), tuple(anchors.shape)
     anchors = anchors.contiguous()
     out = torch.empty((B, H * W * A_loc, 7), dtype=torch.float32, device=box_preds.device)
-    ptrs, bf, st = _map_tables([box_preds.detach(), None if dir_cls_preds is None else dir_cls_preds.detach()], 2)
+    ptrs, bf, st = _native.map_tables([box_preds.detach(), None if dir_cls_preds is None else dir_cls_preds.detach()], 2)
     _native.call("pdm_anchor_decode", _native.stream(out), B, H, W, A_loc, int(num_dir_bins), ptrs, bf, st, anchors.data_ptr(),
                  float(dir_offset), float(dir_limit_offset), out.data_ptr())
     return out

@@ -41,11 +41,6 @@ def center_targets(gt_boxes, local_of, num_head_classes, H, W, x0, y0, vx, vy, s
     return hm, tb, inds, mask, src
 
 
-def _check_map(name, t, B, H, W):
-    assert t.is_cuda and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16), f'{name}: fp32 or bf16 (B, C, H, W) on the GPU'
-    assert t.shape[0] == B and t.shape[2] == H and t.shape[3] == W, f'{name}: {tuple(t.shape)}'
-
-
 @torch.no_grad()
 def center_decode(hm, center, center_z, dim, rot, vel, K, score_thresh, post_center_limit_range, x0, y0, vx, vy, stride,
                   global_of):
@@ -61,16 +56,14 @@ def center_decode(hm, center, center_z, dim, rot, vel, K, score_thresh, post_cen
         raise ValueError(f'center_decode: at most {MAX_K} candidates per sample (K = {K})')
     maps = [hm, center, center_z, dim, rot] + ([vel] if vel is not None else [])
     for name, t in zip(('hm',) + _HEAD_ORDER, maps):
-        _check_map(name, t.detach(), B, H, W)
+        _native.check_map(name, t.detach(), B, H, W)
         assert name == 'hm' or t.shape[1] == _CHANNELS[name], f'{name}: {tuple(t.shape)}'
     dev, E = hm.device, 2 if vel is not None else 0
     boxes = torch.empty((B, K, 7 + E), dtype=torch.float32, device=dev)
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     labels = torch.empty((B, K), dtype=torch.int64, device=dev)
     count = torch.empty((B,), dtype=torch.int32, device=dev)
-    ptrs = _native.host_array(ctypes.c_void_p, [t.data_ptr() for t in maps] + [None] * (6 - len(maps)))
-    bf = _native.host_array(ctypes.c_int, [1 if t.dtype == torch.bfloat16 else 0 for t in maps] + [0] * (6 - len(maps)))
-    st = _native.host_array(ctypes.c_longlong, [s for t in maps for s in t.stride()] + [0] * (4 * (6 - len(maps))))
+    ptrs, bf, st = _native.map_tables(maps, slots=6)
     lim = _native.host_array(ctypes.c_float, post_center_limit_range)
     gl = _native.host_array(ctypes.c_int, global_of)
     assert len(global_of) == C and len(post_center_limit_range) == 6
@@ -87,7 +80,7 @@ class _CenterRegLoss(Function):
         inds / mask (B, N) int64; target (B, N, D) fp32 -> (loc_loss 0-dim, loss_per_code (D))."""
         B, _, H, W = maps[0].shape
         for i, t in enumerate(maps):
-            _check_map(f'map {i}', t, B, H, W)
+            _native.check_map(f'map {i}', t, B, H, W)
         D = sum(t.shape[1] for t in maps)
         N = inds.shape[1]
         assert inds.shape == (B, N) and mask.shape == (B, N) and inds.dtype == torch.int64 and mask.dtype == torch.int64
@@ -96,16 +89,7 @@ class _CenterRegLoss(Function):
             raise ValueError(f'center_reg_loss: at most {MAX_OBJS} slots per sample (NUM_MAX_OBJS = {N})')
         inds, mask, target = inds.contiguous(), mask.contiguous(), target.contiguous()
         dev = maps[0].device
-        ptrs, bf, st = [], [], []
-        for t in maps:
-            sb, sc, sh, sw = t.stride()
-            for c in range(t.shape[1]):
-                ptrs.append(t.data_ptr() + c * sc * t.element_size())
-                bf.append(1 if t.dtype == torch.bfloat16 else 0)
-                st += [sb, sh, sw]
-        ptrs = _native.host_array(ctypes.c_void_p, ptrs)
-        bf = _native.host_array(ctypes.c_int, bf)
-        st = _native.host_array(ctypes.c_longlong, st)
+        ptrs, bf, st = _native.channel_tables(maps)
         cw = _native.host_array(ctypes.c_float, code_weights)
         nbytes = _native.lib().pdm_center_reg_loss_workspace_bytes(B, D)
         ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)

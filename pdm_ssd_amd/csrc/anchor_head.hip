@@ -21,7 +21,7 @@
 // pdm_anchor_decode     one launch: residual decode against the anchor table, arg-max direction bin (lower bin on equal
 //                       logits), heading folded into the bin's period; a workgroup's piece of the table and of the output
 //                       passes through LDS, so both move in whole lines.
-#include "common.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -38,19 +38,11 @@ constexpr int AH_REC = 8;            // words per prepared box: x1 y1 x2 y2 area
 #define AH_PI_4 0.785398185253143311f        // fp32(pi / 4)
 #define AH_2PI 6.28318548202514648f          // fp32(2 pi)
 
-struct AhMap {
-    const void *p;
-    int bf16;
-    long long sb, sc, sh, sw;        // element strides
-};
-
-__device__ __forceinline__ float ah_load1(const AhMap &m, long long off) {
-    return m.bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(m.p)[off] << 16) : static_cast<const float *>(m.p)[off];
-}
-
-// V = 2: two neighbours along W in one access (the host checked sw == 1, even strides and the alignment)
+// V cells along W from (b, c, y, x).  V = 2: two neighbours in one access (the host checked sw == 1, even strides and the
+// alignment: ah_pair_ok)
 template <int V>
-__device__ __forceinline__ void ah_load(const AhMap &m, long long off, float *v) {
+__device__ __forceinline__ void ah_load(const MapRef &m, int b, int c, int y, int x, float *v) {
+    const long long off = map_offset(m, b, c, y, x);
     if (V == 2) {
         if (m.bf16) {
             const unsigned u = *reinterpret_cast<const unsigned *>(static_cast<const unsigned short *>(m.p) + off);
@@ -62,7 +54,7 @@ __device__ __forceinline__ void ah_load(const AhMap &m, long long off, float *v)
             v[V - 1] = f.y;
         }
     } else {
-        v[0] = ah_load1(m, off);
+        v[0] = load_f32_or_bf16(m.p, off, m.bf16);
     }
 }
 
@@ -257,15 +249,9 @@ __global__ __launch_bounds__(AH_T) void at_assign_kernel(AtArgs a) {
             atomicAdd(&s_pos, 1);
             const float *g = a.gt + ((size_t)b * a.M + s_src[arg]) * a.cols;
             const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-            const float dxg = fmaxf(g[3], 1e-5f), dyg = fmaxf(g[4], 1e-5f), dzg = fmaxf(g[5], 1e-5f);
             const float diag = __fsqrt_rn(__fadd_rn(__fmul_rn(dxa, dxa), __fmul_rn(dya, dya)));
             float *t = a.targets + o * 7;
-            t[0] = __fdiv_rn(__fsub_rn(g[0], an[0]), diag);
-            t[1] = __fdiv_rn(__fsub_rn(g[1], an[1]), diag);
-            t[2] = __fdiv_rn(__fsub_rn(g[2], an[2]), dza);
-            t[3] = logf(__fdiv_rn(dxg, dxa));
-            t[4] = logf(__fdiv_rn(dyg, dya));
-            t[5] = logf(__fdiv_rn(dzg, dza));
+            residual_encode(g, an, dxa, dya, dza, diag, t);
             t[6] = __fsub_rn(g[6], an[6]);
         }
     }
@@ -287,7 +273,7 @@ __global__ __launch_bounds__(AH_T) void at_norm_kernel(AtArgs a) {
 // ---- loss ------------------------------------------------------------------------------------------------------------------
 struct AlArgs {
     int B, H, W, A_loc, C, NB;
-    AhMap cls, box, dir;             // dir.p == nullptr: no direction classifier
+    MapRef cls, box, dir;            // dir.p == nullptr: no direction classifier
     const int *labels;               // (B, A)
     const float *targets;            // (B, A, 7)
     const int *num_pos;              // (B)
@@ -301,7 +287,7 @@ struct AlArgs {
 
 template <int V>
 __global__ __launch_bounds__(AH_T) void al_loss_kernel(AlArgs a) {
-    __shared__ double red[AH_T / 64][3];
+    __shared__ BlockSum<AH_T, 3, double> red;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int Wg = a.W / V;
     const long long t = (long long)blockIdx.x * AH_T + tid, hw = (long long)a.H * a.W, A = hw * a.A_loc;
@@ -326,16 +312,16 @@ __global__ __launch_bounds__(AH_T) void al_loss_kernel(AlArgs a) {
             // sigmoid focal loss over the anchors with label >= 0
             for (int c = 0; c < C; ++c) {
                 float xv[V], g[V];
-                ah_load<V>(a.cls, b * a.cls.sb + (long long)(s * C + c) * a.cls.sc + y * a.cls.sh + x * a.cls.sw, xv);
+                ah_load<V>(a.cls, b, s * C + c, y, x, xv);
 #pragma unroll
                 for (int i = 0; i < V; ++i) {
                     g[i] = 0.0f;
                     if (lab[i] < 0) continue;
                     const bool hit = lab[i] > 0 && (C == 1 || lab[i] == c + 1);
                     const float xx = xv[i], tt = hit ? 1.0f : 0.0f;
-                    const float p = __fdiv_rn(1.0f, 1.0f + expf(-xx));
+                    const float p = sigmoid_rn(xx);
                     const float miss = hit ? 1.0f - p : p, bal = hit ? a.alpha : 1.0f - a.alpha;
-                    const float bce = fmaxf(xx, 0.0f) - xx * tt + log1pf(expf(-fabsf(xx)));
+                    const float bce = bce_with_logits(xx, tt);
                     const float mg = powf(miss, a.gamma);
                     acc[0] += (double)(bal * mg * bce * w);
                     const float dmiss = (hit ? -1.0f : 1.0f) * p * (1.0f - p);
@@ -358,12 +344,12 @@ __global__ __launch_bounds__(AH_T) void al_loss_kernel(AlArgs a) {
                 float pk[7][V], lg[AH_MAX_BINS][V];
 #pragma unroll
                 for (int k = 0; k < 7; ++k)
-                    ah_load<V>(a.box, b * a.box.sb + (long long)(s * 7 + k) * a.box.sc + y * a.box.sh + x * a.box.sw, pk[k]);
+                    ah_load<V>(a.box, b, s * 7 + k, y, x, pk[k]);
                 if (a.dir.p) {
 #pragma unroll
                     for (int j = 0; j < AH_MAX_BINS; ++j) {
                         if (j >= NB) break;
-                        ah_load<V>(a.dir, b * a.dir.sb + (long long)(s * NB + j) * a.dir.sc + y * a.dir.sh + x * a.dir.sw, lg[j]);
+                        ah_load<V>(a.dir, b, s * NB + j, y, x, lg[j]);
                     }
                 }
 #pragma unroll
@@ -380,11 +366,8 @@ __global__ __launch_bounds__(AH_T) void al_loss_kernel(AlArgs a) {
                             dpv = cp * ct + sp * st;
                         }
                         if (tv != tv) continue;                     // a NaN target switches its element off
-                        const float d = (pv - tv) * a.cw[k], m = fabsf(d);
                         float loss, dl;
-                        if (a.beta < 1e-5f) { loss = m; dl = d > 0.0f ? 1.0f : d < 0.0f ? -1.0f : 0.0f; }
-                        else if (m < a.beta) { loss = m * m * (0.5f / a.beta); dl = d / a.beta; }
-                        else { loss = m - 0.5f * a.beta; dl = d > 0.0f ? 1.0f : -1.0f; }
+                        smooth_l1((pv - tv) * a.cw[k], a.beta, &loss, &dl);
                         acc[1] += (double)(loss * w);
                         gb[k][i] = dl * a.cw[k] * dpv * gs_loc;
                     }
@@ -426,45 +409,25 @@ __global__ __launch_bounds__(AH_T) void al_loss_kernel(AlArgs a) {
             }
         }
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        double v = acc[d];
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) red[wave][d] = v;
-    }
-    __syncthreads();
-    if (tid < 3) {
-        double s = 0.0;
-        for (int w = 0; w < AH_T / 64; ++w) s += red[w][tid];
-        a.partials[((size_t)b * gridDim.x + blockIdx.x) * 3 + tid] = s;
-    }
+    red.reduce(acc);
+    if (tid < 3) a.partials[((size_t)b * gridDim.x + blockIdx.x) * 3 + tid] = red.total(tid);
 }
 
-// one workgroup: thread t adds partials t, t + AH_T, ... in order, then a fixed tree over the threads
+// one workgroup folds the block partials (FoldSum)
 __global__ __launch_bounds__(AH_T) void al_finish_kernel(AlArgs a) {
-    __shared__ double red[AH_T][3];
+    __shared__ FoldSum<AH_T, 3> sum;
     const int tid = threadIdx.x;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int i = tid; i < a.num_partials; i += AH_T)
-        for (int d = 0; d < 3; ++d) acc[d] += a.partials[(size_t)i * 3 + d];
-    for (int d = 0; d < 3; ++d) red[tid][d] = acc[d];
-    __syncthreads();
-    for (int half = AH_T / 2; half >= 1; half >>= 1) {
-        if (tid < half)
-            for (int d = 0; d < 3; ++d) red[tid][d] += red[tid + half][d];
-        __syncthreads();
-    }
+    sum.fold(a.partials, a.num_partials);
     if (tid < 3) {
         const float weight = tid == 0 ? a.cls_weight : tid == 1 ? a.loc_weight : a.dir_weight;
-        a.out[tid] = (float)(red[0][tid] / (double)(a.B > 0 ? a.B : 1)) * weight;
+        a.out[tid] = (float)(sum.total(tid) / (double)(a.B > 0 ? a.B : 1)) * weight;
     }
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------
 struct AdArgs {
     int B, H, W, A_loc, NB;
-    AhMap box, dir;                  // dir.p == nullptr: no direction classifier
+    MapRef box, dir;                 // dir.p == nullptr: no direction classifier
     const float *anchors;            // (H W A_loc, 7)
     float dir_offset, dir_limit_offset;
     float *out;                      // (B, H W A_loc, 7)
@@ -500,7 +463,7 @@ __global__ __launch_bounds__(AD_T) void ad_decode_kernel(AdArgs a) {
             float pk[7][V];
 #pragma unroll
             for (int k = 0; k < 7; ++k)
-                ah_load<V>(a.box, b * a.box.sb + (long long)(s * 7 + k) * a.box.sc + y * a.box.sh + x * a.box.sw, pk[k]);
+                ah_load<V>(a.box, b, s * 7 + k, y, x, pk[k]);
             int bin[V];
 #pragma unroll
             for (int i = 0; i < V; ++i) bin[i] = 0;
@@ -510,7 +473,7 @@ __global__ __launch_bounds__(AD_T) void ad_decode_kernel(AdArgs a) {
                 for (int j = 0; j < AH_MAX_BINS; ++j) {
                     if (j >= NB) break;
                     float lg[V];
-                    ah_load<V>(a.dir, b * a.dir.sb + (long long)(s * NB + j) * a.dir.sc + y * a.dir.sh + x * a.dir.sw, lg);
+                    ah_load<V>(a.dir, b, s * NB + j, y, x, lg);
 #pragma unroll
                     for (int i = 0; i < V; ++i)
                         if (j == 0 || lg[i] > top[i]) { top[i] = lg[i]; bin[i] = j; }      // the lower bin on equal logits
@@ -543,13 +506,8 @@ __global__ __launch_bounds__(AD_T) void ad_decode_kernel(AdArgs a) {
     for (int i = n4 * 4 + tid; i < nfl; i += AD_T) dst[i] = s_box[i];
 }
 
-static void ah_map(AhMap *m, const void *p, int bf16, const long long *st) {
-    m->p = p; m->bf16 = bf16;
-    m->sb = st[0]; m->sc = st[1]; m->sh = st[2]; m->sw = st[3];
-}
-
 // two neighbours along W in one access: unit stride along W, every other stride even, the first element on a pair boundary
-static bool ah_pair_ok(const AhMap &m) {
+static bool ah_pair_ok(const MapRef &m) {
     if (!m.p) return true;
     const uintptr_t pair = m.bf16 ? 4 : 8;
     return m.sw == 1 && m.sb % 2 == 0 && m.sc % 2 == 0 && m.sh % 2 == 0 && (reinterpret_cast<uintptr_t>(m.p) % pair) == 0;
@@ -644,9 +602,9 @@ extern "C" int pdm_anchor_head_loss(void *stream, int B, int H, int W, int A_loc
     PDM_REQUIRE(gamma > 0.0f && beta >= 0.0f, PDM_E_BADARG, "anchor_head_loss: gamma must be positive and beta non-negative");
     AlArgs a{};
     a.B = B; a.H = H; a.W = W; a.A_loc = A_loc; a.C = num_class; a.NB = maps[2] ? num_dir_bins : 0;
-    ah_map(&a.cls, maps[0], bf16[0], strides);
-    ah_map(&a.box, maps[1], bf16[1], strides + 4);
-    ah_map(&a.dir, maps[2], bf16[2], strides + 8);
+    a.cls = map_ref(maps[0], bf16[0], strides);
+    a.box = map_ref(maps[1], bf16[1], strides + 4);
+    a.dir = map_ref(maps[2], bf16[2], strides + 8);
     a.labels = labels; a.targets = targets; a.num_pos = num_pos;
     for (int s = 0; s < A_loc; ++s) a.rot[s] = anchor_rot[s];
     for (int k = 0; k < 7; ++k) a.cw[k] = code_weights[k];
@@ -685,8 +643,8 @@ extern "C" int pdm_anchor_decode(void *stream, int B, int H, int W, int A_loc, i
     PDM_REQUIRE(maps[0] && anchors && batch_box_preds, PDM_E_BADARG, "anchor_decode: null pointer");
     AdArgs a{};
     a.B = B; a.H = H; a.W = W; a.A_loc = A_loc; a.NB = maps[1] ? num_dir_bins : 0;
-    ah_map(&a.box, maps[0], bf16[0], strides);
-    ah_map(&a.dir, maps[1], bf16[1], strides + 4);
+    a.box = map_ref(maps[0], bf16[0], strides);
+    a.dir = map_ref(maps[1], bf16[1], strides + 4);
     a.anchors = anchors; a.dir_offset = dir_offset; a.dir_limit_offset = dir_limit_offset; a.out = batch_box_preds;
     a.vec4 = (reinterpret_cast<uintptr_t>(anchors) % 16 == 0 && reinterpret_cast<uintptr_t>(batch_box_preds) % 16 == 0 &&
               ((long long)H * W * A_loc * 7) % 4 == 0) ? 1 : 0;

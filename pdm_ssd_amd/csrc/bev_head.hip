@@ -5,7 +5,7 @@
 // storage (B, H, W, C), so a cell is one contiguous row of C floats: a thread owns four channels of one cell (of a strip
 // of four cells when the map row holds eight or more), a workgroup a run of cells; the nine taps of neighbouring cells hit L1 / L2 (three map rows = 270 KB per cloud), so
 // HBM sees the map once in and once out.  Bound: HBM (8 * C bytes per cell).
-#include "common.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void point_head_decode_kernel(long long n, int
         const float v = c[k];
         if (v > best) { best = v; arg = k; }     // first maximum, as torch.max
     }
-    scores[i] = 1.0f / (1.0f + expf(-best));
+    scores[i] = sigmoid_rn(best);
     const float4 t0 = *reinterpret_cast<const float4 *>(code + i * code_stride);
     const float4 t1 = *reinterpret_cast<const float4 *>(code + i * code_stride + 4);
     const float dxa = mean_size[arg * 3], dya = mean_size[arg * 3 + 1], dza = mean_size[arg * 3 + 2];

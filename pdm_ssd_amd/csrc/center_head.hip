@@ -18,6 +18,7 @@
 //                      contributions of every masked slot of that cell in slot order: no atomics, two runs give the
 //                      same bits; cells no slot names keep the fill's zeros)
 #include "heatmap_draw.h"
+#include "loss_kit.h"
 #include "rank_select.h"
 
 namespace pdm {
@@ -26,10 +27,6 @@ constexpr int CT_T = 256;
 constexpr int CH_MAX_CLASSES = 32;   // global classes a head's tables hold
 constexpr int CH_MAX_CODE = 16;      // 8 + E regression channels
 constexpr int CH_MAX_OBJS = 8192;    // slots whose cells the gradient kernel holds in LDS
-
-__device__ __forceinline__ float ch_load(const void *p, int bf16, long long i) {
-    return bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(p)[i] << 16) : static_cast<const float *>(p)[i];
-}
 
 // ---- targets -------------------------------------------------------------------------------------------------------------
 struct CtArgs {
@@ -100,12 +97,6 @@ __global__ __launch_bounds__(CT_T) void ct_draw_kernel(CtArgs a) {
 }
 
 // ---- decode --------------------------------------------------------------------------------------------------------------
-struct MapRef {
-    const void *p;
-    int bf16;
-    long long sb, sc, sh, sw;        // element strides
-};
-
 struct CdArgs {
     int B, C, H, W, K, E;
     MapRef hm, center, center_z, dim, rot, vel;   // vel.p == nullptr without velocity
@@ -119,12 +110,7 @@ struct CdArgs {
 
 __device__ __forceinline__ float cd_score(const CdArgs &a, int b, int i) {
     const int hw = a.H * a.W, c = i / hw, cell = i - c * hw, y = cell / a.W, x = cell - y * a.W;
-    const float logit = ch_load(a.hm.p, a.hm.bf16, b * a.hm.sb + c * a.hm.sc + y * a.hm.sh + x * a.hm.sw);
-    return __fdiv_rn(1.0f, 1.0f + expf(-logit));
-}
-
-__device__ __forceinline__ float cd_at(const MapRef &m, int b, int c, int y, int x) {
-    return ch_load(m.p, m.bf16, b * m.sb + c * m.sc + y * m.sh + x * m.sw);
+    return sigmoid_rn(map_load(a.hm, b, c, y, x));
 }
 
 __global__ __launch_bounds__(TK_THREADS) void cd_decode_kernel(CdArgs a) {
@@ -147,16 +133,16 @@ __global__ __launch_bounds__(TK_THREADS) void cd_decode_kernel(CdArgs a) {
             c = i / hw;
             const int cell = i - c * hw, y = cell / a.W, x = cell - y * a.W;
             score = cd_score(a, b, i);
-            const float px = __fadd_rn((float)x, cd_at(a.center, b, 0, y, x)), py = __fadd_rn((float)y, cd_at(a.center, b, 1, y, x));
+            const float px = __fadd_rn((float)x, map_load(a.center, b, 0, y, x)), py = __fadd_rn((float)y, map_load(a.center, b, 1, y, x));
             box[0] = __fadd_rn(__fmul_rn(__fmul_rn(px, a.stride), a.vx), a.x0);
             box[1] = __fadd_rn(__fmul_rn(__fmul_rn(py, a.stride), a.vy), a.y0);
-            box[2] = cd_at(a.center_z, b, 0, y, x);
-            box[3] = expf(cd_at(a.dim, b, 0, y, x));
-            box[4] = expf(cd_at(a.dim, b, 1, y, x));
-            box[5] = expf(cd_at(a.dim, b, 2, y, x));
-            box[6] = atan2f(cd_at(a.rot, b, 1, y, x), cd_at(a.rot, b, 0, y, x));
+            box[2] = map_load(a.center_z, b, 0, y, x);
+            box[3] = expf(map_load(a.dim, b, 0, y, x));
+            box[4] = expf(map_load(a.dim, b, 1, y, x));
+            box[5] = expf(map_load(a.dim, b, 2, y, x));
+            box[6] = atan2f(map_load(a.rot, b, 1, y, x), map_load(a.rot, b, 0, y, x));
             box[7] = box[8] = 0.0f;
-            if (a.E == 2) { box[7] = cd_at(a.vel, b, 0, y, x); box[8] = cd_at(a.vel, b, 1, y, x); }
+            if (a.E == 2) { box[7] = map_load(a.vel, b, 0, y, x); box[8] = map_load(a.vel, b, 1, y, x); }
             keep = score > a.score_thresh;
 #pragma unroll
             for (int d = 0; d < 3; ++d) keep = keep && box[d] >= a.lo[d] && box[d] <= a.hi[d];
@@ -179,15 +165,9 @@ __global__ __launch_bounds__(TK_THREADS) void cd_decode_kernel(CdArgs a) {
 }
 
 // ---- regression loss -------------------------------------------------------------------------------------------------------
-struct ChanRef {
-    const void *p;                   // the channel's (B, H, W) plane
-    int bf16;
-    long long sb, sh, sw;
-};
-
 struct RlArgs {
     int B, nmax, D, H, W;
-    ChanRef ch[CH_MAX_CODE];
+    MapRef ch[CH_MAX_CODE];          // a regression channel's (B, H, W) plane: sc = 0
     const long long *inds, *mask;    // (B, nmax)
     const float *target;             // (B, nmax, D)
     float w[CH_MAX_CODE], loc_weight;
@@ -198,11 +178,11 @@ struct RlArgs {
 
 __device__ __forceinline__ float rl_pred(const RlArgs &a, int d, int b, long long ind) {
     const long long y = ind / a.W, x = ind - y * a.W;
-    return ch_load(a.ch[d].p, a.ch[d].bf16, b * a.ch[d].sb + y * a.ch[d].sh + x * a.ch[d].sw);
+    return map_load(a.ch[d], b, 0, y, x);
 }
 
 __global__ __launch_bounds__(CT_T) void rl_partial_kernel(RlArgs a) {
-    __shared__ double red[CT_T / 64][CH_MAX_CODE + 1];
+    __shared__ BlockSum<CT_T, CH_MAX_CODE + 1, double> red;
     const int b = blockIdx.x, tid = threadIdx.x, D = a.D;
     const long long hw = (long long)a.H * a.W;
     double acc[CH_MAX_CODE + 1];
@@ -222,20 +202,8 @@ __global__ __launch_bounds__(CT_T) void rl_partial_kernel(RlArgs a) {
             acc[d] += (double)fabsf(__fsub_rn(__fmul_rn(rl_pred(a, d, b, ind), mf), __fmul_rn(gt, mf)));
         }
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 0; d <= CH_MAX_CODE; ++d) {
-        double v = acc[d];
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) red[wave][d] = v;
-    }
-    __syncthreads();
-    if (tid <= D) {
-        const int d = tid < D ? tid : CH_MAX_CODE;
-        double s = 0.0;
-        for (int w = 0; w < CT_T / 64; ++w) s += red[w][d];
-        a.partials[(size_t)b * (D + 1) + tid] = s;
-    }
+    red.reduce(acc);                                                // all 17, whatever D is
+    if (tid <= D) a.partials[(size_t)b * (D + 1) + tid] = red.total(tid < D ? tid : CH_MAX_CODE);
 }
 
 __global__ __launch_bounds__(64) void rl_finalize_kernel(RlArgs a) {
@@ -302,12 +270,6 @@ __global__ __launch_bounds__(CT_T) void rl_grad_kernel(RlArgs a) {
     }
 }
 
-static int ch_map(MapRef *m, const void *p, int bf16, const long long *strides) {
-    m->p = p; m->bf16 = bf16;
-    m->sb = strides[0]; m->sc = strides[1]; m->sh = strides[2]; m->sw = strides[3];
-    return 0;
-}
-
 }  // namespace pdm
 
 using namespace pdm;
@@ -362,7 +324,7 @@ extern "C" int pdm_center_decode(void *stream, int B, int C, int H, int W, int K
     CdArgs a{};
     a.B = B; a.C = C; a.H = H; a.W = W; a.K = K; a.E = maps[5] ? 2 : 0;
     MapRef *refs[6] = {&a.hm, &a.center, &a.center_z, &a.dim, &a.rot, &a.vel};
-    for (int m = 0; m < 6; ++m) ch_map(refs[m], maps[m], bf16[m], strides + 4 * m);
+    for (int m = 0; m < 6; ++m) *refs[m] = map_ref(maps[m], bf16[m], strides + 4 * m);
     a.score_thresh = score_thresh;
     for (int d = 0; d < 3; ++d) { a.lo[d] = limit_range[d]; a.hi[d] = limit_range[3 + d]; }
     a.x0 = x0; a.y0 = y0; a.vx = vx; a.vy = vy; a.stride = stride;
@@ -397,7 +359,7 @@ extern "C" int pdm_center_reg_loss(void *stream, int B, int num_max_objs, int D,
     a.B = B; a.nmax = num_max_objs; a.D = D; a.H = H; a.W = W;
     for (int d = 0; d < D; ++d) {
         PDM_REQUIRE(B == 0 || chans[d], PDM_E_BADARG, "center_reg_loss: null channel %d", d);
-        a.ch[d] = ChanRef{chans[d], bf16[d], strides[3 * d], strides[3 * d + 1], strides[3 * d + 2]};
+        a.ch[d] = MapRef{chans[d], bf16[d], strides[3 * d], 0, strides[3 * d + 1], strides[3 * d + 2]};
         a.w[d] = code_weights[d];
     }
     a.inds = inds; a.mask = mask; a.target = target; a.loc_weight = loc_weight;

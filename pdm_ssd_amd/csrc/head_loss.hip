@@ -13,8 +13,7 @@
 // Launch 1 counts the positives (and checks the classes against the mean-size table: the reference asserts there; here the box
 // loss turns NaN).  Launch 2 forms labels, loss partials (one pair per workgroup, folded in double in a fixed order by the
 // third, one-workgroup launch: bit-reproducible) and d L / d pred for both stacks, in the predictions' dtype.
-#include "bf16.h"
-#include "common.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -39,9 +38,6 @@ struct HeadLossArgs {
     float *out;                                       // [0] L_cls, [1] L_box, [2] #positives
 };
 
-__device__ __forceinline__ float hl_load(const void *p, long long i, int bf16) {
-    return bf16 ? bf16_to_f32(static_cast<const unsigned short *>(p)[i]) : static_cast<const float *>(p)[i];
-}
 __device__ __forceinline__ void hl_store(void *p, long long i, float v, int bf16) {
     if (bf16) static_cast<unsigned short *>(p)[i] = f32_to_bf16(v);
     else static_cast<float *>(p)[i] = v;
@@ -69,9 +65,9 @@ __global__ __launch_bounds__(HL_T) void head_loss_count_kernel(HeadLossArgs a) {
 }
 
 __global__ __launch_bounds__(HL_T) void head_loss_main_kernel(HeadLossArgs a) {
-    __shared__ float red[2][HL_T / 64];
+    __shared__ BlockSum<HL_T, 2, float, true> red;
     const long long i = (long long)blockIdx.x * HL_T + threadIdx.x;
-    float lc = 0.f, lb = 0.f;
+    float acc[2] = {0.f, 0.f};                           // classification, box
     if (i < a.n_total) {
         const float inv_pos = 1.0f / fmaxf((float)a.counts[0], 1.0f);
         const int bi = a.box_idx[i], ei = a.ext_idx[i];
@@ -85,14 +81,14 @@ __global__ __launch_bounds__(HL_T) void head_loss_main_kernel(HeadLossArgs a) {
         // ---- classification: sigmoid focal loss over the classes, weight 1 / #positives for every non-ignored point
         const float wc = label >= 0 ? inv_pos : 0.f;
         for (int c = 1; c <= a.num_class; ++c) {
-            const float x = hl_load(a.cls_preds, i * a.cls_stride + (c - 1), a.pred_bf16);
+            const float x = load_f32_or_bf16(a.cls_preds, i * a.cls_stride + (c - 1), a.pred_bf16);
             const float t = label == c ? 1.f : 0.f;
-            const float p = 1.0f / (1.0f + expf(-x));
+            const float p = sigmoid_rn(x);
             const float miss = p + t * ((1.0f - p) - p);                         // torch.lerp(p, 1 - p, t)
             const float balance = (1.0f - a.alpha) + t * (2.0f * a.alpha - 1.0f);
-            const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));    // binary_cross_entropy_with_logits
+            const float bce = bce_with_logits(x, t);
             const float mg = a.gamma == 2.0f ? miss * miss : powf(miss, a.gamma);
-            lc += balance * mg * bce * wc;
+            acc[0] += balance * mg * bce * wc;
             const float dmg = a.gamma == 2.0f ? 2.0f * miss : a.gamma * powf(miss, a.gamma - 1.0f);
             const float dper = balance * (dmg * (1.0f - 2.0f * t) * p * (1.0f - p) * bce + mg * (p - t));
             hl_store(a.dcls, i * a.num_class + (c - 1), dper * wc * a.cls_weight, a.pred_bf16);
@@ -102,22 +98,16 @@ __global__ __launch_bounds__(HL_T) void head_loss_main_kernel(HeadLossArgs a) {
             int ac = cls < 1 ? 1 : cls > a.n_mean ? a.n_mean : cls;                 // gt_classes.clamp(1, n_mean)
             const float dxa = a.mean_size[(ac - 1) * 3], dya = a.mean_size[(ac - 1) * 3 + 1], dza = a.mean_size[(ac - 1) * 3 + 2];
             const float diag = sqrtf(dxa * dxa + dya * dya);
-            const float px = a.xyz[i * a.xyz_stride], py = a.xyz[i * a.xyz_stride + 1], pz = a.xyz[i * a.xyz_stride + 2];
-            const float dxg = fmaxf(gb[3], 1e-5f), dyg = fmaxf(gb[4], 1e-5f), dzg = fmaxf(gb[5], 1e-5f);
             float tgt[8];
-            tgt[0] = (gb[0] - px) / diag; tgt[1] = (gb[1] - py) / diag; tgt[2] = (gb[2] - pz) / dza;
-            tgt[3] = logf(dxg / dxa); tgt[4] = logf(dyg / dya); tgt[5] = logf(dzg / dza);
+            residual_encode(gb, a.xyz + i * a.xyz_stride, dxa, dya, dza, diag, tgt);
             tgt[6] = cosf(gb[6]); tgt[7] = sinf(gb[6]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const float x = hl_load(a.box_preds, i * a.box_stride + k, a.pred_bf16);
+                const float x = load_f32_or_bf16(a.box_preds, i * a.box_stride + k, a.pred_bf16);
                 const float r = (x - tgt[k]) * a.code_w[k];
-                const float mag = fabsf(r);
                 float l, d;
-                if (a.beta < 1e-5f) { l = mag; d = r > 0.f ? 1.f : r < 0.f ? -1.f : 0.f; }
-                else if (mag < a.beta) { l = mag * mag * (0.5f / a.beta); d = r / a.beta; }
-                else { l = mag - 0.5f * a.beta; d = r > 0.f ? 1.f : -1.f; }
-                lb += l * inv_pos;
+                smooth_l1(r, a.beta, &l, &d);
+                acc[1] += l * inv_pos;
                 hl_store(a.dbox, i * 8 + k, d * a.code_w[k] * inv_pos * a.box_weight, a.pred_bf16);
             }
         } else {
@@ -125,28 +115,16 @@ __global__ __launch_bounds__(HL_T) void head_loss_main_kernel(HeadLossArgs a) {
             for (int k = 0; k < 8; ++k) hl_store(a.dbox, i * 8 + k, 0.f, a.pred_bf16);
         }
     }
-    for (int off = 32; off >= 1; off >>= 1) { lc += __shfl_xor(lc, off, 64); lb += __shfl_xor(lb, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lc; red[1][threadIdx.x >> 6] = lb; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.partials[(size_t)blockIdx.x * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        a.partials[(size_t)blockIdx.x * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    red.reduce(acc);
+    if (threadIdx.x < 2) a.partials[(size_t)blockIdx.x * 2 + threadIdx.x] = red.total(threadIdx.x);
 }
 
 __global__ __launch_bounds__(HL_T) void head_loss_finalize_kernel(HeadLossArgs a, int nblocks) {
-    __shared__ double sh[2][HL_T];
-    double sc = 0.0, sb = 0.0;
-    for (int k = threadIdx.x; k < nblocks; k += HL_T) { sc += a.partials[(size_t)k * 2]; sb += a.partials[(size_t)k * 2 + 1]; }
-    sh[0][threadIdx.x] = sc; sh[1][threadIdx.x] = sb;
-    __syncthreads();
-    for (int half = HL_T / 2; half >= 1; half >>= 1) {
-        if ((int)threadIdx.x < half) { sh[0][threadIdx.x] += sh[0][threadIdx.x + half]; sh[1][threadIdx.x] += sh[1][threadIdx.x + half]; }
-        __syncthreads();
-    }
+    __shared__ FoldSum<HL_T, 2> sum;
+    sum.fold(a.partials, nblocks);
     if (threadIdx.x == 0) {
-        a.out[0] = (float)sh[0][0] * a.cls_weight;
-        a.out[1] = a.counts[1] ? __builtin_nanf("") : (float)sh[1][0] * a.box_weight;
+        a.out[0] = (float)sum.total(0) * a.cls_weight;
+        a.out[1] = a.counts[1] ? __builtin_nanf("") : (float)sum.total(1) * a.box_weight;
         a.out[2] = (float)a.counts[0];
     }
 }

@@ -17,6 +17,7 @@
 // element; launch 3 (one workgroup) folds the partials in double in a fixed order (bit-reproducible), leaving L and the factor
 // - weight / max(#peaks, 1) that backward() multiplies the stored d S / d x by.
 #include "heatmap_draw.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -42,8 +43,7 @@ __global__ __launch_bounds__(HM_T) void hm_target_kernel(HmTargetArgs a) {
 struct HmLossArgs {
     long long n;                    // B C H W
     int C, H, W;
-    const void *logits; int logits_bf16;
-    long long sb, sc, sh, sw;       // element strides of the logits
+    MapRef logits;                  // (B, C, H, W) fp32 or bf16, any strides
     const float *heatmap;           // (B, C, H, W) contiguous
     float *dlogits;                 // (B, C, H, W) contiguous fp32: d S / d logit
     double *partials;               // (blocks, 3): peak term, other term, peaks
@@ -52,16 +52,13 @@ struct HmLossArgs {
 };
 
 __global__ __launch_bounds__(HM_T) void hm_loss_kernel(HmLossArgs a) {
-    __shared__ double red[3][HM_T / 64];
-    double s_peak = 0.0, s_else = 0.0, n_peak = 0.0;
+    __shared__ BlockSum<HM_T, 3, double> red;
+    double acc[3] = {0.0, 0.0, 0.0};                     // peak term, other term, peaks
     const long long hw = (long long)a.H * a.W, chw = hw * a.C;
     for (long long i = (long long)blockIdx.x * HM_T + threadIdx.x; i < a.n; i += (long long)gridDim.x * HM_T) {
         const long long b = i / chw, r0 = i - b * chw, c = r0 / hw, r1 = r0 - c * hw, y = r1 / a.W, x = r1 - y * a.W;
-        const long long li = b * a.sb + c * a.sc + y * a.sh + x * a.sw;
-        const float xl = a.logits_bf16 ? __uint_as_float((unsigned)static_cast<const unsigned short *>(a.logits)[li] << 16)
-                                       : static_cast<const float *>(a.logits)[li];
         const float gt = a.heatmap[i];
-        const float praw = __fdiv_rn(1.0f, 1.0f + expf(-xl));
+        const float praw = sigmoid_rn(map_load(a.logits, b, c, y, x));
         const float lo = 1e-4f, hi = 1.0f - 1e-4f;
         const float p = fminf(fmaxf(praw, lo), hi);
         const float dp = (praw >= lo && praw <= hi) ? praw * (1.0f - praw) : 0.0f;      // clamp passes the gradient inside [lo, hi]
@@ -69,27 +66,18 @@ __global__ __launch_bounds__(HM_T) void hm_loss_kernel(HmLossArgs a) {
         float ds;
         if (gt == 1.0f) {
             const float lp = logf(p);
-            s_peak += (double)(q * q * lp);
-            n_peak += 1.0;
+            acc[0] += (double)(q * q * lp);
+            acc[2] += 1.0;
             ds = -2.0f * q * lp + q * q / p;
         } else {
             const float w4 = powf(1.0f - gt, 4.0f), lq = logf(q);
-            s_else += (double)(w4 * (p * p) * lq);
+            acc[1] += (double)(w4 * (p * p) * lq);
             ds = w4 * (2.0f * p * lq - p * p / q);
         }
         a.dlogits[i] = ds * dp;
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        s_peak += __shfl_xor(s_peak, off, 64); s_else += __shfl_xor(s_else, off, 64); n_peak += __shfl_xor(n_peak, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[0][wave] = s_peak; red[1][wave] = s_else; red[2][wave] = n_peak; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double s = 0.0;
-        for (int w = 0; w < HM_T / 64; ++w) s += red[threadIdx.x][w];
-        a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = s;
-    }
+    red.reduce(acc);
+    if (threadIdx.x < 3) a.partials[(size_t)blockIdx.x * 3 + threadIdx.x] = red.total(threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void hm_loss_finalize_kernel(int blocks, const double *__restrict__ partials, float weight, float *__restrict__ out) {
@@ -148,7 +136,7 @@ extern "C" int pdm_heatmap_focal_loss(void *stream, int B, int C, int H, int W, 
         PDM_REQUIRE(workspace_bytes >= pdm_heatmap_focal_loss_workspace_bytes(n) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                     PDM_E_BADARG, "heatmap_focal_loss: workspace of %zu bytes, need %zu (8-byte aligned)", workspace_bytes,
                     pdm_heatmap_focal_loss_workspace_bytes(n));
-        HmLossArgs a{n, C, H, W, logits, logits_bf16, sb, sc, sh, sw, heatmap, dlogits, static_cast<double *>(workspace), weight, out};
+        HmLossArgs a{n, C, H, W, MapRef{logits, logits_bf16, sb, sc, sh, sw}, heatmap, dlogits, static_cast<double *>(workspace), weight, out};
         hipLaunchKernelGGL(hm_loss_kernel, dim3((unsigned)blocks), dim3(HM_T), 0, as_stream(stream), a);
         if (int rc = check_launch("heatmap_focal_loss")) return rc;
     }

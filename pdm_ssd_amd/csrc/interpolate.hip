@@ -9,8 +9,8 @@
 // 1e40 and compares a float candidate with strict '<' (:37, :44-55); float bests initialised to
 // +inf decide identically (every finite float is < 1e40 and < inf; inf and NaN are < neither) and
 // narrow to the same outputs ((float)1e40 == inf).
-#include "bf16.h"
 #include "csr.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -199,10 +199,6 @@ using namespace pdm;
 // cast of the concatenated fp32 tensor holds.  known (B, m, C2) and skip (B, n, C1) are point-major rows, fp32 or bf16.
 namespace pdm {
 
-__device__ __forceinline__ float icr_load(const void *p, size_t i, bool bf16) {
-    return bf16 ? bf16_to_f32(static_cast<const unsigned short *>(p)[i]) : static_cast<const float *>(p)[i];
-}
-
 __global__ __launch_bounds__(256) void interp_concat_rows_kernel(long long total, int n, int m, int c2, int c1, int ld,
                                                                  const void *__restrict__ known, int known_bf16,
                                                                  const void *__restrict__ skip, int skip_bf16,
@@ -216,12 +212,12 @@ __global__ __launch_bounds__(256) void interp_concat_rows_kernel(long long total
             const long long b = row / n;
             const int *id = idx + row * 3;
             const float *w = weight + row * 3;
-            const float p0 = icr_load(known, ((size_t)b * m + id[0]) * c2 + ch, known_bf16);
-            const float p1 = icr_load(known, ((size_t)b * m + id[1]) * c2 + ch, known_bf16);
-            const float p2 = icr_load(known, ((size_t)b * m + id[2]) * c2 + ch, known_bf16);
+            const float p0 = load_f32_or_bf16(known, ((size_t)b * m + id[0]) * c2 + ch, known_bf16);
+            const float p1 = load_f32_or_bf16(known, ((size_t)b * m + id[1]) * c2 + ch, known_bf16);
+            const float p2 = load_f32_or_bf16(known, ((size_t)b * m + id[2]) * c2 + ch, known_bf16);
             v = __fmaf_rn(w[2], p2, __fmaf_rn(w[1], p1, __fmul_rn(w[0], p0)));
         } else if (ch < c2 + c1) {
-            v = icr_load(skip, (size_t)row * c1 + (ch - c2), skip_bf16);
+            v = load_f32_or_bf16(skip, (size_t)row * c1 + (ch - c2), skip_bf16);
         }
         out[e] = f32_to_bf16(v);
     }
@@ -264,7 +260,7 @@ __global__ __launch_bounds__(256) void interp_concat_rows8_kernel(long long tota
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const int c = ch + t - c2;
-                v[t] = c < c1 ? icr_load(skip, (size_t)row * c1 + c, skip_bf16) : 0.0f;
+                v[t] = c < c1 ? load_f32_or_bf16(skip, (size_t)row * c1 + c, skip_bf16) : 0.0f;
             }
         }
         *reinterpret_cast<uint4 *>(out + e * 8) = pack_bf16x8(v);

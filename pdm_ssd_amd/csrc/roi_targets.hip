@@ -59,6 +59,7 @@
 // second launch: bit-reproducible.  Every workgroup counts #fg and #valid itself over all rows (integers; n <= 262144).
 #include "box_geometry.h"
 #include "draws.h"
+#include "loss_kit.h"
 
 namespace pdm {
 
@@ -298,38 +299,28 @@ __device__ __forceinline__ float rl_label(const RLArgs &a, long long i) {
     return a.labels_float ? static_cast<const float *>(a.labels)[i] : (float)static_cast<const long long *>(a.labels)[i];
 }
 
-__device__ __forceinline__ void rl_smooth_l1(float r, float beta, float *l, float *d) {
-    const float mag = fabsf(r);
-    if (beta < 1e-5f) { *l = mag; *d = r > 0.f ? 1.f : r < 0.f ? -1.f : 0.f; }
-    else if (mag < beta) { *l = mag * mag * (0.5f / beta); *d = r / beta; }
-    else { *l = mag - 0.5f * beta; *d = r > 0.f ? 1.f : -1.f; }
-}
-
 __global__ __launch_bounds__(RL_T) void rcnn_loss_main_kernel(RLArgs a) {
-    __shared__ int s_cnt[2][RL_T / 64];
-    __shared__ float red[3][RL_T / 64];
+    __shared__ BlockSum<RL_T, 2, int, true> s_cnt;
+    __shared__ BlockSum<RL_T, 3, float, true> red;
     const int tid = threadIdx.x;
-    int nf = 0, nv = 0;
+    int cnt[2] = {0, 0};                                 // #fg, #valid
     for (long long k = tid; k < a.n; k += RL_T) {
-        nf += a.mask[k] > 0 ? 1 : 0;
-        nv += rl_label(a, k) >= 0.f ? 1 : 0;
+        cnt[0] += a.mask[k] > 0 ? 1 : 0;
+        cnt[1] += rl_label(a, k) >= 0.f ? 1 : 0;
     }
-    for (int off = 32; off >= 1; off >>= 1) { nf += __shfl_xor(nf, off, 64); nv += __shfl_xor(nv, off, 64); }
-    if ((tid & 63) == 0) { s_cnt[0][tid >> 6] = nf; s_cnt[1][tid >> 6] = nv; }
-    __syncthreads();
-    nf = (s_cnt[0][0] + s_cnt[0][1]) + (s_cnt[0][2] + s_cnt[0][3]);
-    nv = (s_cnt[1][0] + s_cnt[1][1]) + (s_cnt[1][2] + s_cnt[1][3]);
+    s_cnt.reduce(cnt);
+    const int nf = s_cnt.total(0), nv = s_cnt.total(1);
     if (blockIdx.x == 0 && tid == 0) { a.counts[0] = nf; a.counts[1] = nv; }
     const float den_fg = fmaxf((float)nf, 1.f), den_valid = fmaxf((float)nv, 1.f);
 
     const long long i = (long long)blockIdx.x * RL_T + tid;
-    float lc = 0.f, lr = 0.f, lk = 0.f;
+    float acc[3] = {0.f, 0.f, 0.f};                      // classification, regression, corner
     if (i < a.n) {
         // ---- classification
         const float x = a.cls[i], t = rl_label(a, i);
         if (t >= 0.f) {
-            lc = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-            const float p = 1.0f / (1.0f + expf(-x));
+            acc[0] = bce_with_logits(x, t);
+            const float p = sigmoid_rn(x);
             a.dcls[i] = (p - t) / den_valid * a.w_cls;
         } else {
             a.dcls[i] = 0.f;
@@ -343,15 +334,15 @@ __global__ __launch_bounds__(RL_T) void rcnn_loss_main_kernel(RLArgs a) {
             for (int k = 0; k < 7; ++k) p[k] = pr[k];
             const float dxa = fmaxf(ro[3], 1e-5f), dya = fmaxf(ro[4], 1e-5f), dza = fmaxf(ro[5], 1e-5f);
             const float diag = sqrtf(dxa * dxa + dya * dya);
+            const float origin[3] = {0.f, 0.f, 0.f};               // the ground truth is already canonical
             float tg[7];
-            tg[0] = g[0] / diag; tg[1] = g[1] / diag; tg[2] = g[2] / dza;
-            tg[3] = logf(fmaxf(g[3], 1e-5f) / dxa); tg[4] = logf(fmaxf(g[4], 1e-5f) / dya); tg[5] = logf(fmaxf(g[5], 1e-5f) / dza);
+            residual_encode(g, origin, dxa, dya, dza, diag, tg);
             tg[6] = g[6];
             for (int k = 0; k < 7; ++k) {
                 const float r = tg[k] != tg[k] ? 0.f : (p[k] - tg[k]) * a.cw[k];
                 float l, d;
-                rl_smooth_l1(r, a.beta, &l, &d);
-                lr += l;
+                smooth_l1(r, a.beta, &l, &d);
+                acc[1] += l;
                 dr[k] = tg[k] != tg[k] ? 0.f : d * a.cw[k] / den_fg * a.w_reg;
             }
             if (a.use_corner) {
@@ -392,7 +383,7 @@ __global__ __launch_bounds__(RL_T) void rcnn_loss_main_kernel(RLArgs a) {
                     dS[2] += uz * gzz;
                     dR += gx * (-sh * qx - ch * qy) + gy * (ch * qx - sh * qy);
                 }
-                lk = sum / 8.f;
+                acc[2] = sum / 8.f;
                 const float sc = a.w_corner / 8.f / den_fg;
                 dk[0] = sc * dg * (dC[0] * c + dC[1] * s);
                 dk[1] = sc * dg * (dC[1] * c - dC[0] * s);
@@ -405,33 +396,18 @@ __global__ __launch_bounds__(RL_T) void rcnn_loss_main_kernel(RLArgs a) {
         }
         for (int k = 0; k < 7; ++k) { a.dreg[i * 7 + k] = dr[k]; a.dcorner[i * 7 + k] = dk[k]; }
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        lc += __shfl_xor(lc, off, 64);
-        lr += __shfl_xor(lr, off, 64);
-        lk += __shfl_xor(lk, off, 64);
-    }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = lc; red[1][tid >> 6] = lr; red[2][tid >> 6] = lk; }
-    __syncthreads();
-    if (tid < 3) a.partials[(size_t)blockIdx.x * 3 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    red.reduce(acc);
+    if (tid < 3) a.partials[(size_t)blockIdx.x * 3 + tid] = red.total(tid);
 }
 
 __global__ __launch_bounds__(RL_T) void rcnn_loss_finalize_kernel(RLArgs a, int nblocks) {
-    __shared__ double sh[3][RL_T];
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int k = threadIdx.x; k < nblocks; k += RL_T)
-        for (int j = 0; j < 3; ++j) acc[j] += a.partials[(size_t)k * 3 + j];
-    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = acc[j];
-    __syncthreads();
-    for (int half = RL_T / 2; half >= 1; half >>= 1) {
-        if ((int)threadIdx.x < half)
-            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + half];
-        __syncthreads();
-    }
+    __shared__ FoldSum<RL_T, 3> sum;
+    sum.fold(a.partials, nblocks);
     if (threadIdx.x == 0) {
         const int nf = a.counts[0], nv = a.counts[1];
-        *a.o_cls = (float)sh[0][0] / fmaxf((float)nv, 1.f) * a.w_cls;
-        *a.o_reg = (float)sh[1][0] / fmaxf((float)nf, 1.f) * a.w_reg;
-        *a.o_corner = nf > 0 && a.use_corner ? (float)sh[2][0] / (float)nf * a.w_corner : 0.f;
+        *a.o_cls = (float)sum.total(0) / fmaxf((float)nv, 1.f) * a.w_cls;
+        *a.o_reg = (float)sum.total(1) / fmaxf((float)nf, 1.f) * a.w_reg;
+        *a.o_corner = nf > 0 && a.use_corner ? (float)sum.total(2) / (float)nf * a.w_corner : 0.f;
         *a.o_fg = (float)nf;
     }
 }

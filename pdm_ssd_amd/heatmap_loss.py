@@ -26,19 +26,18 @@ class _HeatmapFocalLoss(Function):
     @staticmethod
     def forward(ctx, logits, heatmap, weight):
         """logits (B, C, H, W) fp32 or bf16, any strides; heatmap (B, C, H, W) fp32 contiguous -> 0-dim fp32 loss."""
-        assert logits.dim() == 4 and logits.dtype in (torch.float32, torch.bfloat16)
-        assert heatmap.shape == logits.shape and heatmap.dtype == torch.float32 and heatmap.is_contiguous()
-        B, C, H, W = logits.shape
+        assert heatmap.dim() == 4 and heatmap.dtype == torch.float32 and heatmap.is_contiguous()
+        B, C, H, W = heatmap.shape
+        _native.check_map('logits', logits, B, H, W, C)
         dev = logits.device
         l = _native.lib()
         nbytes = l.pdm_heatmap_focal_loss_workspace_bytes(logits.numel())
         ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
         dl = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        sb, sc, sh, sw = logits.stride()
-        _native.call("pdm_heatmap_focal_loss", _native.stream(dev), B, C, H, W, logits.data_ptr(),
-                     1 if logits.dtype == torch.bfloat16 else 0, sb, sc, sh, sw, heatmap.data_ptr(), float(weight), dl.data_ptr(),
-                     out.data_ptr(), ws.data_ptr(), nbytes)
+        ptrs, bf, st = _native.map_tables([logits])
+        _native.call("pdm_heatmap_focal_loss", _native.stream(dev), B, C, H, W, ptrs[0], bf[0], *st[:4], heatmap.data_ptr(),
+                     float(weight), dl.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes)
         ctx.save_for_backward(dl, out)
         ctx.in_dtype = logits.dtype
         return out[0]

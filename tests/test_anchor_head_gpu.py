@@ -293,6 +293,37 @@ def test_two_calls_agree_bit_for_bit(dev):
     assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 
+def test_loss_folds_more_block_partials_than_the_finish_kernel_has_threads(dev):
+    """B = 1 on a 257 x 257 map: odd W takes the one-cell path, 66 049 cells make 259 workgroups, so the finish kernel's
+    threads 0 .. 2 add a second partial (rows t, t + 256) and the rest one: a ragged second pass.  Two slots, one class,
+    direction map on; against the torch formulation at the standing tolerance, and twice for the same bits."""
+    def edit(cfg):
+        cfg['ANCHOR_GENERATOR_CONFIG'] = cfg['ANCHOR_GENERATOR_CONFIG'][:1]
+    hh = ww = 257
+    head = case.build_head(num_class=1, grid_size=[2 * ww, 2 * hh, 1], pc_range=[0.0, -51.4, -3.0, 102.8, 51.4, 1.0], edit=edit)
+    assert len(head._anchor_rot) == 2 and head._flat_anchors.shape[0] == hh * ww * 2
+    assert 256 < -(-hh * ww // 256) < 512 and -(-hh * ww // 256) % 64 != 0
+    rng = np.random.default_rng(11)
+    gt = np.zeros((1, 24, 8), dtype=np.float32)
+    gt[0, :, :7] = np.stack([rng.uniform(2, 100, 24), rng.uniform(-49, 49, 24), rng.uniform(-1.2, -0.6, 24), rng.uniform(3.5, 4.3, 24),
+                             rng.uniform(1.5, 1.7, 24), rng.uniform(1.4, 1.7, 24), rng.uniform(-3.1, 3.1, 24)], 1)
+    gt[0, :, 7] = 1
+    head = head.to(dev)
+    td = head.assign_targets(torch.from_numpy(gt).to(dev))
+    assert int(td['num_pos'][0]) > 0
+    g = torch.Generator().manual_seed(12)
+    plain = [torch.randn((1, 2 * c, hh, ww), generator=g) * s for c, s in ((1, 2.0), (7, 0.7), (2, 1.5))]
+    want_terms, want_grads = case.torch_losses(head, plain, td)
+    maps = [t.to(dev) for t in plain]
+    terms, grads = fused_losses(head, maps, td)
+    again_terms, again_grads = fused_losses(head, maps, td)
+    assert all(torch.equal(a, b) for a, b in zip(terms + grads, again_terms + again_grads)), 'two runs must give the same bits'
+    for got, want in zip(terms, want_terms):
+        close(float(got), float(want))
+    for got, want in zip(grads, want_grads):
+        close_grad(got.cpu().numpy(), want.numpy())
+
+
 def small_step(head, feats, gt):
     """forward, get_loss, backward to the parameters -> loss and the gradients on the three conv outputs"""
     head({'batch_size': feats.shape[0], 'spatial_features_2d': feats, 'gt_boxes': gt})

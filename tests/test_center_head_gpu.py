@@ -278,6 +278,39 @@ def test_fused_reg_loss_matches_the_torch_formulation(dev, dtype, layout, extras
         close(t.grad.float().cpu().numpy(), r.grad.cpu().numpy(), tol=1e-4 if dtype == torch.float32 else 2.0 ** -8)   # one bf16 rounding
 
 
+def test_fused_reg_loss_sums_all_seventeen_accumulators_over_a_ragged_pass(dev):
+    """D = 10 (velocity head) of the 17 accumulators the partial kernel always sums, 257 slots (the workgroup's second pass
+    over the slots holds one), the heads' channels of one bf16 channels-last map (every channel's plane has a non-unit
+    stride along W), two masked slots on one cell, one NaN target element; against RegLossCenterNet as above."""
+    g = torch.Generator().manual_seed(257)
+    hh, ww, D, N = 13, 21, 10, 257
+    pred = torch.randn((2, D, hh, ww), generator=g).to(torch.bfloat16).to(dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    maps = list(torch.split(pred, [2, 1, 3, 2, 2], dim=1))                     # the five heads' channels of one channels-last map
+    assert all(t.stride(3) == D for t in maps)
+    inds = torch.randint(0, hh * ww, (2, N), generator=g)
+    mask = (torch.rand((2, N), generator=g) < 0.7).long()
+    inds[0, 256], mask[0, 256], mask[0, 3] = inds[0, 3], 1, 1                  # the last slot shares slot 3's cell
+    target = torch.randn((2, N, D), generator=g)
+    target[0, 256, 9] = float('nan')
+    inds, mask, target = inds.to(dev), mask.to(dev), target.to(dev)
+    w = [1.0, 1.0, 0.5, 1.0, 1.0, 1.0, 2.0, 1.0, 0.2, 0.2]
+    runs = []
+    for _ in range(2):
+        pred.grad = None
+        loc, per_code = center_head_ops.center_reg_loss(maps, inds, mask, target, w, 2.0)
+        loc.backward()
+        runs.append((loc.detach().clone(), per_code.clone(), pred.grad.clone()))
+    assert all(torch.equal(a, b) for a, b in zip(*runs)), 'two runs must give the same bits'
+    ref = pred.detach().float().requires_grad_(True)
+    want = loss_utils.RegLossCenterNet()(ref, mask, inds, target)
+    want_loc = (want * want.new_tensor(w)).sum() * 2.0
+    want_loc.backward()
+    close(per_code.cpu().numpy(), want.detach().cpu().numpy())
+    close(float(loc.detach()), float(want_loc.detach()))
+    assert pred.grad.dtype == torch.bfloat16 and pred.grad.shape == pred.shape
+    close(pred.grad.float().cpu().numpy(), ref.grad.cpu().numpy(), tol=2.0 ** -8)          # one bf16 rounding
+
+
 # ---- the head and the detector ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tag", ["one", "two"])
 def test_head_on_the_gpu_matches_the_reference(dev, tag):

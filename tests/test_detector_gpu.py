@@ -118,6 +118,43 @@ def test_point_head_fused_loss_equals_torch_formulation(dev, bf16):
 
 
 @pytest.mark.gpu
+def test_point_head_fused_loss_folds_more_block_partials_than_the_finalize_kernel_has_threads(dev):
+    """N = 256 * 257 + 3 points make 258 workgroups: the finalize kernel's threads 0 and 1 add a second partial, the rest one
+    (a ragged second pass).  fp32, the bounds of test_point_head_fused_loss_equals_torch_formulation, and twice for the
+    same bits."""
+    torch.manual_seed(6)
+    n = 256 * 257 + 3
+    assert 256 < -(-n // 256) < 512 and -(-n // 256) % 64 != 0
+    gt = scene_boxes(1, 5, 13)
+    rng = np.random.default_rng(7)
+    xyz = np.stack([rng.uniform(0, 70, n), rng.uniform(-40, 40, n), rng.uniform(-3, 1, n)], -1).astype(np.float32)
+    for k in range(3):
+        xyz[3000 * k:3000 * (k + 1)] = gt[0, k, :3] + rng.normal(0, 1.0, (3000, 3)).astype(np.float32) * gt[0, k, 3:6] * 0.4
+    coords = np.concatenate([np.zeros((n, 1), dtype=np.float32), xyz], 1)
+    head = PointHeadBox(num_class=3, input_channels=16, model_cfg=HEAD_CFG).to(dev).train()
+    bd = {'batch_size': 1, 'point_features': torch.randn(n, 16, device=dev), 'point_coords': torch.from_numpy(coords).to(dev),
+          'gt_boxes': torch.from_numpy(gt).to(dev), 'points_per_sample_checked': True}
+    res = []
+    for fused_on in (True, True, False):
+        head.use_fused_loss = fused_on
+        head.zero_grad(set_to_none=True)
+        head(dict(bd))
+        assert ('fused_loss_inputs' in head.forward_ret_dict) == fused_on
+        loss, tb = head.get_loss()
+        loss.backward()
+        res.append((loss.detach().clone(), {k: float(v) for k, v in tb.items()}, head.forward_ret_dict['point_cls_labels'].clone(),
+                    {k: p.grad.clone() for k, p in head.named_parameters()}))
+    (la, ta, laba, ga), (la2, ta2, _, ga2), (lb, tb_, labb, gb) = res
+    assert torch.equal(la, la2) and ta == ta2 and all(torch.equal(ga[k], ga2[k]) for k in ga), 'two runs must give the same bits'
+    assert torch.equal(laba, labb) and int((laba > 0).sum()) > 50
+    assert abs(float(la) - float(lb)) <= 1e-5 * abs(float(lb))
+    for k in ('point_loss_cls', 'point_loss_box'):
+        assert abs(ta[k] - tb_[k]) <= 1e-5 * abs(tb_[k]) + 1e-7, k
+    for k in ga:
+        assert float((ga[k] - gb[k]).abs().max()) <= 1e-4 * float(gb[k].abs().max()) + 1e-9, k
+
+
+@pytest.mark.gpu
 def test_point_head_fused_inference_equals_torch_layers(dev):
     torch.manual_seed(0)
     head = build_pdm_ssd().point_head.to(dev).eval()

@@ -213,6 +213,38 @@ def test_fused_rcnn_loss_equals_torch_formulation(dev, fix):
 
 
 @pytest.mark.gpu
+def test_fused_rcnn_loss_folds_more_block_partials_than_the_finalize_kernel_has_threads(dev, fix):
+    """n = 256 * 257 + 3 rows make 258 workgroups: the finalize kernel's threads 0 and 1 add a second partial, the rest one
+    (a ragged second pass).  The fixture's rows repeated with seeded predictions; the bounds of
+    test_fused_rcnn_loss_equals_torch_formulation, and twice for the same bits."""
+    n = 256 * 257 + 3
+    assert 256 < -(-n // 256) < 512 and -(-n // 256) % 64 != 0
+    fused, plain = host.template_head(fix).to(dev), host.template_head(fix).to(dev)
+    plain.use_fused_loss = False
+    small = host.loss_inputs(fix, 'cls', dev)
+    rows = torch.arange(n, device=dev) % small['reg_valid_mask'].numel()
+    g = torch.Generator().manual_seed(n)
+    res = []
+    for head in (fused, fused, plain):
+        ret = {k: small[k].flatten(0, 1)[rows][None].contiguous() for k in ('rois', 'gt_of_rois', 'gt_of_rois_src', 'reg_valid_mask', 'rcnn_cls_labels')}
+        g.manual_seed(n)
+        ret['rcnn_cls'] = torch.randn((n, 1), generator=g).to(dev).requires_grad_(True)
+        ret['rcnn_reg'] = (torch.randn((n, 7), generator=g) * 0.3).to(dev).requires_grad_(True)
+        assert head._fused_loss_applies(ret) == (head is fused)
+        loss_cls, tb_cls = head.get_box_cls_layer_loss(ret)
+        loss_reg, tb_reg = head.get_box_reg_layer_loss(ret)
+        grads = torch.autograd.grad(loss_cls + loss_reg, [ret['rcnn_cls'], ret['rcnn_reg']])
+        res.append((dict(tb_cls, **tb_reg), grads))
+    (tb_f, g_f), (tb_again, g_again), (tb_p, g_p) = res
+    for key in ('rcnn_loss_cls', 'rcnn_loss_reg', 'rcnn_loss_corner'):
+        assert torch.equal(tb_f[key], tb_again[key]), 'two runs must give the same bits'
+        host.close(tb_f[key], tb_p[key], 1e-5, key)
+    assert torch.equal(g_f[0], g_again[0]) and torch.equal(g_f[1], g_again[1]), 'two runs must give the same bits'
+    host.grad_close(g_f[0], g_p[0].cpu().numpy(), 'd / d rcnn_cls')
+    host.grad_close(g_f[1], g_p[1].cpu().numpy(), 'd / d rcnn_reg')
+
+
+@pytest.mark.gpu
 def test_limits_and_refusals(dev, fix):
     from pdm_ssd_amd import _native, roi_targets
     from pdm_ssd_amd.roi_heads.target_assigner import ProposalTargetLayer

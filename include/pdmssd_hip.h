@@ -1118,6 +1118,31 @@ size_t pdm_sparse_to_dense_workspace_bytes(int B, int D, int H, int W);
 int pdm_sparse_to_dense(void *stream, int P, int C, const float *features, const int *indices, int B, int D, int H, int W, float *out,
                         void *workspace, size_t workspace_bytes);
 
+/* Voxel R-CNN's RoI-grid pooling (csrc/sparse_conv.hip, csrc/roi_grid_pool.hip).
+ * pdm_sparse_index: indices (P, 4) int32 rows (b, z, y, x), distinct sites in any row order on the grid (B, D, H, W) -> the
+ *   level's site index in `workspace` (>= pdm_sparse_index_workspace_bytes, 8-byte aligned): occupancy bitmap, group prefixes
+ *   and row_of_rank, so that row_of_rank[rank(key)] is the row at a cell.  Six launches, no host read, graph-capturable.  Up to
+ *   2^35 cells (PDM_E_TOOLARGE beyond; the size query returns 0).
+ * pdm_roi_grid_pool: one launch per (level, scale).  rois (B, n, roi_stride >= 7) rows (x, y, z, dx, dy, dz, heading, ...); grid
+ *   point g of RoI r (g = (ix G + iy) G + iz) is local = (i + 0.5) / G size - size / 2 turned by the heading plus the centre, its
+ *   cell floor(floor((p - p0) / voxel) / stride) per axis, its sample r / n.  The window of (2 rz + 1)(2 ry + 1)(2 rx + 1) cells
+ *   around it is walked z outermost, x innermost; a set cell whose centre (c + 0.5) (voxel stride) + p0 lies within `radius` of
+ *   the grid point is a hit, the first nsample hits are the group.  pooled[c] = max over the group of
+ *   relu(features_in[row][c] + fma(dot(wp[c], centre - p), scale_p[c], shift_p[c])), relu(shift_p[c]) for an empty group;
+ *   out[r G^3 + g][out_offset + j] = relu(fma(dot(wout[j], pooled), scale_o[j], shift_o[j])) on the exact f32 MFMA, rows of
+ *   out_stride floats.  site_index: what pdm_sparse_index left for the same P and grid.  features_in (P, C1); wp (C1, 3); wout:
+ *   the (C2, C1) weight in pdm_sparse_conv's packed order with kvol = 1.  C1, C2 in {16, 32, 64}, G <= 8, rz, ry, rx <= 4,
+ *   nsample <= 32 (PDM_E_BADARG otherwise).  No atomics: two runs give the same bits. */
+/* align: any (4-byte accesses, 16-byte ones only where the pointer allows), except wout: 16 B and the workspaces: 8 B
+ * (PDM_E_BADARG otherwise). */
+size_t pdm_sparse_index_workspace_bytes(int P, int B, int D, int H, int W);
+int pdm_sparse_index(void *stream, int P, const int *indices, int B, int D, int H, int W, void *workspace, size_t workspace_bytes);
+int pdm_roi_grid_pool(void *stream, int B, int n, int roi_stride, const float *rois, int G, int D, int H, int W, int stride, float vx,
+                      float vy, float vz, float x0, float y0, float z0, int P, const void *site_index, size_t site_index_bytes, int C1,
+                      const float *features_in, const float *wp, const float *scale_p, const float *shift_p, int rz, int ry, int rx,
+                      float radius, int nsample, int C2, const float *wout, const float *scale_o, const float *shift_o, float *out,
+                      int out_stride, int out_offset);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -1,0 +1,267 @@
+// Voxel R-CNN's RoI-grid pooling over one level of the voxel backbone, one launch per (level, scale): for every
+// grid point of every RoI, the voxel-window query, the gather of the level's features after mlps_in, the position term, ReLU,
+// the max over the group and the output layer.  None of the composed formulation's intermediates exists: no dense
+// (B, Z, Y, X) table (the level's occupancy index of sc_index.h answers "which row is at this cell"), no (M, nsample) index
+// rows, no grouped (M, C, nsample) tensors.
+//
+// A wave owns a tile of 16 consecutive grid points, formed one per lane and handed round by shuffles.  Per point: 64 window
+// cells a step in the reference's order (z outer, x inner), the sphere tested first (it needs no memory), then the bit, the rank
+// taken for set cells only, a ballot compaction of the hits into the first nsample, early exit at nsample.  Then the lanes turn
+// into channels: lane c gathers channel c of every hit row, adds the position term and keeps the maximum of the ReLUs (C1 < 64:
+// 64 / C1 hits at a time and a cross-lane maximum, which is exact).  The pooled row goes to LDS; after 16 rows the wave runs C1 -> C2 on mfma_f32_16x16x4f32 (weights in the packed
+// fragment order of sparse_conv_mfma.hip, staged once per workgroup) and the epilogue relu(acc * scale + shift), written at
+// a column offset into rows of the full stride.  No atomics and nothing summed across waves: two runs and a graph replay give
+// the same bits.
+#include "sc_index.h"
+
+namespace pdm {
+
+typedef float gf4 __attribute__((ext_vector_type(4)));
+
+constexpr int RGP_T = 256;          // 4 waves
+constexpr int RGP_TILE = 16;        // grid points per wave tile: the MFMA's 16 columns
+constexpr int RGP_MAXS = 32;        // nsample at most
+constexpr int RGP_HS = 24;          // LDS row stride of a 16-channel slice of the pooled rows (sparse_conv_mfma.hip's SCV_HS)
+constexpr int RGP_MAXBLOCKS = 2048; // workgroups at most; waves walk the tiles with this stride
+
+struct RgpArgs {
+    long long M;            // B n G^3 grid points
+    int n, G, roi_stride;   // rois per sample, grid size, floats per roi row
+    int B, D, H, W, P, stride;
+    float vox[3], r0[3];    // (x, y, z): the BASE voxel size and the range minimum
+    int rz, ry, rx, nsample;
+    float radius;
+    int out_stride, out_offset;
+    const float *rois;
+    const unsigned *bits;
+    const int *gprefix, *row_of_rank;
+    const float *feat;      // (P, C1)
+    const float *wp, *scale_p, *shift_p;    // (C1, 3), (C1), (C1)
+    const float *wout, *scale_o, *shift_o;  // packed (C2, C1), (C2), (C2)
+    float *out;
+};
+
+// floor(a / s) for s >= 1
+__device__ __forceinline__ int floor_div(int a, int s) {
+    const int q = a / s;
+    return (a % s != 0 && a < 0) ? q - 1 : q;
+}
+// floor((g - r0) / voxel) as an int; far outside (and NaN) -> a cell no window reaches
+__device__ __forceinline__ int rgp_cell0(float g, float r0, float voxel) {
+    const float c = floorf(__fdiv_rn(__fsub_rn(g, r0), voxel));
+    return (c > -1.0e9f && c < 1.0e9f) ? (int)c : -(1 << 30);
+}
+
+template <int C1, int NB>
+__global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
+    constexpr int NKB = C1 / 16, SUB = 64 / C1;
+    __shared__ __attribute__((aligned(16))) float s_w[NKB * NB * 256];
+    __shared__ __attribute__((aligned(16))) float s_pool[RGP_T / 64][NKB * RGP_TILE * RGP_HS];
+    __shared__ int s_hrow[RGP_T / 64][RGP_MAXS];
+    __shared__ float s_hd[RGP_T / 64][RGP_MAXS * 3];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    for (int q = tid; q < NKB * NB * 64; q += RGP_T) reinterpret_cast<gf4 *>(s_w)[q] = reinterpret_cast<const gf4 *>(a.wout)[q];
+    __syncthreads();
+
+    const int c = lane % C1, sub = lane / C1;       // gather role: channel c of the hits sub, sub + SUB, ...
+    const float wpx = a.wp[c * 3], wpy = a.wp[c * 3 + 1], wpz = a.wp[c * 3 + 2], sp = a.scale_p[c], hp = a.shift_p[c];
+    const float r2 = __fmul_rn(a.radius, a.radius);
+    const float sx = __fmul_rn(a.vox[0], (float)a.stride), sy = __fmul_rn(a.vox[1], (float)a.stride), sz = __fmul_rn(a.vox[2], (float)a.stride);
+    const int wy = 2 * a.ry + 1, wx = 2 * a.rx + 1, window = (2 * a.rz + 1) * wy * wx;
+    const int mzyx = (1 << 20) / (wy * wx) + 1, mx = (1 << 20) / wx + 1;       // w / d = (w m) >> 20 exactly for w < 1024, d <= 81
+    const int G = a.G, G3 = G * G * G;
+    const long long ntiles = (a.M + RGP_TILE - 1) / RGP_TILE;
+    float *pool = s_pool[wave];
+    int *hrow = s_hrow[wave];
+    float *hd = s_hd[wave];
+
+    for (long long tile = (long long)blockIdx.x * (RGP_T / 64) + wave; tile < ntiles; tile += (long long)gridDim.x * (RGP_T / 64)) {
+        // the tile's 16 grid points, one per lane (lanes 16 and up repeat them): the trigonometry runs once a point, not once a lane
+        float pgx, pgy, pgz;
+        int pcx, pcy, pcz, pb;
+        {
+            const int m = (int)min(tile * RGP_TILE + (lane & 15), a.M - 1);
+            const int r = m / G3, gi = m - r * G3, ix = gi / (G * G), iy = (gi / G) % G, iz = gi % G;      // nonzero()'s order
+            const float *roi = a.rois + (size_t)r * a.roi_stride;
+            const float dxs = roi[3], dys = roi[4], dzs = roi[5], head = roi[6];
+            const float lx = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)ix, 0.5f), (float)G), dxs), __fdiv_rn(dxs, 2.0f));
+            const float ly = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iy, 0.5f), (float)G), dys), __fdiv_rn(dys, 2.0f));
+            const float lz = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iz, 0.5f), (float)G), dzs), __fdiv_rn(dzs, 2.0f));
+            const float cs = cosf(head), sn = sinf(head);
+            pgx = __fadd_rn(__fsub_rn(__fmul_rn(lx, cs), __fmul_rn(ly, sn)), roi[0]);
+            pgy = __fadd_rn(__fadd_rn(__fmul_rn(lx, sn), __fmul_rn(ly, cs)), roi[1]);
+            pgz = __fadd_rn(lz, roi[2]);
+            pb = r / a.n;
+            pcx = floor_div(rgp_cell0(pgx, a.r0[0], a.vox[0]), a.stride);
+            pcy = floor_div(rgp_cell0(pgy, a.r0[1], a.vox[1]), a.stride);
+            pcz = floor_div(rgp_cell0(pgz, a.r0[2], a.vox[2]), a.stride);
+        }
+        for (int i = 0; i < RGP_TILE; ++i) {
+            if (tile * RGP_TILE + i >= a.M) break;
+            const float gx = __shfl(pgx, i, 64), gy = __shfl(pgy, i, 64), gz = __shfl(pgz, i, 64);
+            const int cx = __shfl(pcx, i, 64), cy = __shfl(pcy, i, 64), cz = __shfl(pcz, i, 64), b = __shfl(pb, i, 64);
+
+            // the first nsample in-radius voxels of the window, in window order
+            int cnt = 0;
+            for (int base = 0; base < window && cnt < a.nsample; base += 64) {
+                const int w = base + lane;
+                bool hit = false;
+                int row = -1;
+                float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+                if (w < window) {
+                    const int wz = (w * mzyx) >> 20, rem = w - wz * (wy * wx), wyy = (rem * mx) >> 20;
+                    const int z = cz + wz - a.rz, y = cy + wyy - a.ry, x = cx + (rem - wyy * wx) - a.rx;
+                    if (z >= 0 && z < a.D && y >= 0 && y < a.H && x >= 0 && x < a.W) {
+                        // the sphere first: it needs no memory, and most cells of a window fail it
+                        ddx = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)x, 0.5f), sx), a.r0[0]), gx);
+                        ddy = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)y, 0.5f), sy), a.r0[1]), gy);
+                        ddz = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)z, 0.5f), sz), a.r0[2]), gz);
+                        if (!(sqdist(ddx, ddy, ddz) > r2)) {
+                            const long long key = rb_key(b, z, y, x, a.D, a.H, a.W);
+                            if (sc_test(a.bits, key)) {
+                                row = a.row_of_rank[sc_rank(a.bits, a.gprefix, key)];
+                                hit = row >= 0 && row < a.P;
+                            }
+                        }
+                    }
+                }
+                const unsigned long long mask = __ballot(hit);
+                if (mask == 0) continue;
+                const int slot = cnt + lanes_below(mask, lane);
+                if (hit && slot < a.nsample) {
+                    hrow[slot] = row;
+                    hd[slot * 3] = ddx; hd[slot * 3 + 1] = ddy; hd[slot * 3 + 2] = ddz;
+                }
+                cnt += __popcll(mask);
+            }
+            cnt = min(cnt, a.nsample);
+            __builtin_amdgcn_wave_barrier();
+
+            // lanes are channels: max over the group of relu(feature + position term); an empty group is relu(shift_p)
+            float v = 0.0f;
+            if (cnt == 0) {
+                v = hp < 0.0f ? 0.0f : hp;
+            } else {
+#pragma unroll 4
+                for (int h = sub; h < cnt; h += SUB) {
+                    const float f = a.feat[(size_t)hrow[h] * C1 + c];
+                    const float dot = __fmaf_rn(wpz, hd[h * 3 + 2], __fmaf_rn(wpy, hd[h * 3 + 1], __fmul_rn(wpx, hd[h * 3])));
+                    const float t = __fadd_rn(f, __fmaf_rn(dot, sp, hp));
+                    v = fmaxf(v, t < 0.0f ? 0.0f : t);
+                }
+#pragma unroll
+                for (int off = C1; off < 64; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+            }
+            if (lane < C1) pool[((c >> 4) * RGP_TILE + i) * RGP_HS + (c & 15)] = v;
+            __builtin_amdgcn_wave_barrier();
+        }
+
+        // out rows of the tile: C1 -> C2 on the exact f32 MFMA; lane (pos, g), register j of block nb = channel 16 nb + 4 g + j
+        const int pos = lane & 15, g = lane >> 4;
+        gf4 acc[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = gf4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            const gf4 fb = *reinterpret_cast<const gf4 *>(&pool[(kb * RGP_TILE + pos) * RGP_HS + 4 * g]);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const gf4 fa = reinterpret_cast<const gf4 *>(s_w)[(kb * NB + nb) * 64 + lane];
+                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb.x, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb.y, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb.z, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb.w, acc[nb], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();        // the next tile's rows overwrite `pool`
+        const long long m = tile * RGP_TILE + pos;
+        if (m >= a.M) continue;
+        float *orow = a.out + (size_t)m * a.out_stride + a.out_offset;
+        const bool vec_o = ((reinterpret_cast<uintptr_t>(a.out) & 15) | ((a.out_stride | a.out_offset) & 3)) == 0;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int c0 = 16 * nb + 4 * g;
+            float o[4] = {acc[nb].x, acc[nb].y, acc[nb].z, acc[nb].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = __fmaf_rn(o[j], a.scale_o[c0 + j], a.shift_o[c0 + j]);
+                o[j] = o[j] < 0.0f ? 0.0f : o[j];
+            }
+            if (vec_o) {
+                *reinterpret_cast<gf4 *>(orow + c0) = gf4{o[0], o[1], o[2], o[3]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) orow[c0 + j] = o[j];
+            }
+        }
+    }
+}
+
+template <int C1>
+static void rgp_launch(int C2, dim3 grid, hipStream_t s, const RgpArgs &a) {
+    switch (C2 / 16) {
+        case 1: hipLaunchKernelGGL((roi_grid_pool_kernel<C1, 1>), grid, dim3(RGP_T), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((roi_grid_pool_kernel<C1, 2>), grid, dim3(RGP_T), 0, s, a); break;
+        default: hipLaunchKernelGGL((roi_grid_pool_kernel<C1, 4>), grid, dim3(RGP_T), 0, s, a); break;
+    }
+}
+
+}  // namespace pdm
+
+using namespace pdm;
+
+// rois (B, n, roi_stride >= 7) fp32 rows (x, y, z, dx, dy, dz, heading, ...); the level's grid (B, D, H, W) at `stride` times
+// the base voxel (vx, vy, vz) from the range minimum (x0, y0, z0); site_index: the workspace pdm_sparse_index filled for the
+// level's P rows on that grid; features_in (P, C1): the level's features after mlps_in; wp (C1, 3), scale_p, shift_p (C1): the
+// folded mlps_pos; window half-widths (rz, ry, rx), radius, nsample; wout: the folded mlps_out weight (C2, C1) in
+// pdm_sparse_conv's packed order (kvol = 1), scale_o, shift_o (C2).  Writes columns [out_offset, out_offset + C2) of the rows
+// r G^3 + g of out (B n G^3, out_stride).
+extern "C" int pdm_roi_grid_pool(void *stream, int B, int n, int roi_stride, const float *rois, int G, int D, int H, int W, int stride, float vx,
+                                 float vy, float vz, float x0, float y0, float z0, int P, const void *site_index, size_t site_index_bytes, int C1,
+                                 const float *features_in, const float *wp, const float *scale_p, const float *shift_p, int rz, int ry, int rx,
+                                 float radius, int nsample, int C2, const float *wout, const float *scale_o, const float *shift_o, float *out,
+                                 int out_stride, int out_offset) {
+    PDM_REQUIRE(B >= 0 && n >= 0 && P >= 0 && D >= 1 && H >= 1 && W >= 1 && roi_stride >= 7, PDM_E_BADARG, "roi_grid_pool: bad size");
+    PDM_REQUIRE(G >= 1 && G <= 8, PDM_E_BADARG, "roi_grid_pool: grid size %d (1 to 8)", G);
+    PDM_REQUIRE(C1 == 16 || C1 == 32 || C1 == 64, PDM_E_BADARG, "roi_grid_pool: %d pooled channels (16, 32 or 64)", C1);
+    PDM_REQUIRE(C2 == 16 || C2 == 32 || C2 == 64, PDM_E_BADARG, "roi_grid_pool: %d output channels (16, 32 or 64)", C2);
+    PDM_REQUIRE(rz >= 0 && ry >= 0 && rx >= 0 && rz <= 4 && ry <= 4 && rx <= 4, PDM_E_BADARG,
+                "roi_grid_pool: query range (%d, %d, %d): a window of at most 9 x 9 x 9", rz, ry, rx);
+    PDM_REQUIRE(nsample >= 1 && nsample <= RGP_MAXS, PDM_E_BADARG, "roi_grid_pool: nsample %d (1 to %d)", nsample, RGP_MAXS);
+    PDM_REQUIRE(stride >= 1 && vx > 0.0f && vy > 0.0f && vz > 0.0f && radius >= 0.0f, PDM_E_BADARG, "roi_grid_pool: bad stride, voxel size or radius");
+    PDM_REQUIRE(out_offset >= 0 && out_stride >= 1 && (long long)out_offset + C2 <= out_stride, PDM_E_BADARG,
+                "roi_grid_pool: columns [%d, %d) do not fit rows of %d", out_offset, out_offset + C2, out_stride);
+    PDM_REQUIRE(si_grid_ok(B, D, H, W), PDM_E_TOOLARGE, "roi_grid_pool: more than 2^35 cells");
+    const long long M = (long long)B * n * G * G * G;
+    PDM_REQUIRE(M <= 0x7fffffffll && (long long)B * n * roi_stride <= 0x7fffffffll && (long long)P * C1 <= 0x7fffffffll, PDM_E_TOOLARGE,
+                "roi_grid_pool: %lld grid points, roi or feature elements exceed int32", M);
+    if (M == 0) return 0;
+    PDM_REQUIRE(rois && site_index && wp && scale_p && shift_p && wout && scale_o && shift_o && out && (P == 0 || features_in), PDM_E_BADARG,
+                "roi_grid_pool: null pointer");
+    PDM_WS_ALIGNED("roi_grid_pool", site_index);
+    PDM_REQUIRE((reinterpret_cast<uintptr_t>(wout) & 15) == 0, PDM_E_BADARG, "roi_grid_pool: packed weights must be 16-byte aligned");
+    const SiWorkspace w = si_workspace(P, B, D, H, W);
+    PDM_REQUIRE(site_index_bytes >= w.total, PDM_E_BADARG, "roi_grid_pool: site index too small (%zu bytes, need %zu)", site_index_bytes, w.total);
+    char *ws = const_cast<char *>(static_cast<const char *>(site_index));
+    const ScIndex ix = sc_index_at(ws + w.index, w.isz);
+    RgpArgs a{};
+    a.M = M; a.n = n; a.G = G; a.roi_stride = roi_stride;
+    a.B = B; a.D = D; a.H = H; a.W = W; a.P = P; a.stride = stride;
+    a.vox[0] = vx; a.vox[1] = vy; a.vox[2] = vz; a.r0[0] = x0; a.r0[1] = y0; a.r0[2] = z0;
+    a.rz = rz; a.ry = ry; a.rx = rx; a.nsample = nsample; a.radius = radius;
+    a.out_stride = out_stride; a.out_offset = out_offset;
+    a.rois = rois; a.bits = ix.bits; a.gprefix = ix.gprefix; a.row_of_rank = reinterpret_cast<const int *>(ws + w.row_of_rank);
+    a.feat = features_in; a.wp = wp; a.scale_p = scale_p; a.shift_p = shift_p; a.wout = wout; a.scale_o = scale_o; a.shift_o = shift_o;
+    a.out = out;
+    const long long ntiles = (M + RGP_TILE - 1) / RGP_TILE;
+    const dim3 grid((unsigned)min((long long)RGP_MAXBLOCKS, (ntiles + RGP_T / 64 - 1) / (RGP_T / 64)));
+    hipStream_t s = as_stream(stream);
+    switch (C1) {
+        case 16: rgp_launch<16>(C2, grid, s, a); break;
+        case 32: rgp_launch<32>(C2, grid, s, a); break;
+        default: rgp_launch<64>(C2, grid, s, a); break;
+    }
+    return check_launch("roi_grid_pool");
+}

@@ -167,6 +167,28 @@ CENTER_VOXEL_CFG = {
     'POST_PROCESSING': copy.deepcopy(CENTER_PDM_CFG['POST_PROCESSING']),
 }
 
+# Voxel R-CNN: SECOND_CFG's front as it is, plus VoxelRCNNHead on the backbone's x_conv2 / x_conv3 / x_conv4 levels.  The
+# snapshot this repository was modelled on holds no YAML for this detector, so the ROI_HEAD values are BUILD-DEFINED: they
+# restate the upstream project's KITTI setting for Voxel R-CNN as far as it is remembered here (class-agnostic head, 6 x 6 x 6
+# grid, one scale of 32 -> 32 channels per level with a 9 x 9 x 9 window and 16 samples, radii 0.4 / 0.8 / 1.6 m, three FC
+# stacks of 256 -> 256, dropout 0.3, 100 test-time proposals at NMS 0.7) and were not checked against that file.  The second
+# stage runs in eval mode only: of TARGET_CONFIG it holds the box coder alone.
+_VOXEL_RCNN_POOL = {'MLPS': [[32, 32]], 'QUERY_RANGES': [[4, 4, 4]], 'NSAMPLE': [16], 'POOL_METHOD': 'max_pool'}
+VOXEL_RCNN_CFG = copy.deepcopy(SECOND_CFG)
+VOXEL_RCNN_CFG['NAME'] = 'VoxelRCNN'
+VOXEL_RCNN_CFG['ROI_HEAD'] = {
+    'NAME': 'VoxelRCNNHead', 'CLASS_AGNOSTIC': True,
+    'SHARED_FC': [256, 256], 'CLS_FC': [256, 256], 'REG_FC': [256, 256], 'DP_RATIO': 0.3,
+    'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                             'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                   'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 2048,
+                            'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+    'ROI_GRID_POOL': {'FEATURES_SOURCE': ['x_conv2', 'x_conv3', 'x_conv4'], 'GRID_SIZE': 6,
+                      'POOL_LAYERS': {'x_conv2': dict(copy.deepcopy(_VOXEL_RCNN_POOL), POOL_RADIUS=[0.4]),
+                                      'x_conv3': dict(copy.deepcopy(_VOXEL_RCNN_POOL), POOL_RADIUS=[0.8]),
+                                      'x_conv4': dict(copy.deepcopy(_VOXEL_RCNN_POOL), POOL_RADIUS=[1.6])}},
+    'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -241,4 +263,12 @@ def build_center_voxel(model_cfg=None, num_point_features=4, dataset=None):
     BaseBEVBackbone -> CenterHead, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(CENTER_VOXEL_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_voxel_rcnn(model_cfg=None, num_point_features=4, dataset=None):
+    """VoxelRCNN from VOXEL_RCNN_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone ->
+    AnchorHeadSingle -> VoxelRCNNHead, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(VOXEL_RCNN_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

@@ -8,6 +8,7 @@ from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
 from .second_net import SECONDNet
+from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
@@ -16,6 +17,7 @@ __all__ = {
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,
     'SECONDNet': SECONDNet,
+    'VoxelRCNN': VoxelRCNN,
 }
 
 

@@ -7,7 +7,8 @@ checkpoint loading).  The reference's template cannot be imported on this platfo
 pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
 (DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and, in eval mode, the voxel family (DynamicMeanVFE ->
 VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
-outside the registries (MeanVFE, PillarVFE, ...) and the pfe slot are refused.  The roi_head slot builds the point-based RoI heads of roi_heads/ (PointRCNN's second stage).
+outside the registries (MeanVFE, PillarVFE, ...) and the pfe slot are refused.  The roi_head slot builds the RoI heads of
+roi_heads/ (PointRCNN's second stage; Voxel R-CNN's, in eval mode).
 """
 import torch
 import torch.nn as nn
@@ -101,12 +102,15 @@ class Detector3DTemplate(nn.Module):
         return module, model_info_dict
 
     def build_roi_head(self, model_info_dict):
-        """ref :159-176: the point-based RoI heads need no spconv; built by NAME from roi_heads.__all__."""
+        """ref :159-176: built by NAME from roi_heads.__all__; backbone_channels, point_cloud_range and voxel_size are what the
+        voxel-based head (VoxelRCNNHead) reads, the point-based ones take them as unused keywords."""
         cfg = _get(self.model_cfg, 'ROI_HEAD', None)
         if cfg is None:
             return None, model_info_dict
         module = roi_heads.__all__[_get(cfg, 'NAME')](
             model_cfg=cfg, input_channels=model_info_dict['num_point_features'],
+            backbone_channels=model_info_dict.get('backbone_channels', {}), point_cloud_range=model_info_dict['point_cloud_range'],
+            voxel_size=model_info_dict['voxel_size'],
             num_class=self.num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1)
         model_info_dict['module_list'].append(module)
         return module, model_info_dict

@@ -1,8 +1,10 @@
 """RoI (second-stage) heads, registered by NAME as /root/reference/pcdet/models/roi_heads/__init__.py does."""
 from .pointrcnn_head import PointRCNNHead
 from .roi_head_template import RoIHeadTemplate
+from .voxelrcnn_head import VoxelRCNNHead
 
 __all__ = {
     'RoIHeadTemplate': RoIHeadTemplate,
     'PointRCNNHead': PointRCNNHead,
+    'VoxelRCNNHead': VoxelRCNNHead,
 }

@@ -1,11 +1,12 @@
 """The voxel path's device operators (csrc/sparse_conv.hip, csrc/sparse_conv_mfma.hip): points -> dynamic voxels with
 means (voxel_assign), the rulebook of a sparse 3-D convolution (rulebook), the convolution itself on the exact f32 MFMA
-(sparse_conv) and the dense canvas of a sparse tensor (to_dense).  An occupancy bitmap with scanned popcounts numbers
+(sparse_conv), the dense canvas of a sparse tensor (to_dense), the site index of a level as an object of its own (site_index)
+and Voxel R-CNN's RoI-grid pooling over it (roi_grid_pool, csrc/roi_grid_pool.hip).  An occupancy bitmap with scanned popcounts numbers
 voxels and output sites in ascending key order: no host loop, no sort, no hash, no float atomics, so every result is a
 function of the input alone and two runs give the same bits.  Eval mode only: nothing here has a gradient yet.
 
 Host reads: voxel_assign() copies the two ints {N', P} to the host, and a STRIDED rulebook() copies the one int P_out;
-a submanifold rulebook, sparse_conv() and to_dense() read nothing.  HOST_READS counts the copies.
+a submanifold rulebook, sparse_conv(), to_dense(), site_index() and roi_grid_pool() read nothing.  HOST_READS counts the copies.
 
 The torch formulations these stand for (torch.unique + scatter_mean, and per offset index_select -> mm -> index_add_) are
 what the tests and tools/sparse_conv_rate.py compare with.
@@ -22,6 +23,7 @@ COUT_SUPPORTED = (16, 32, 64, 128)
 
 Voxels = namedtuple('Voxels', ['kept_idx', 'unq_inv', 'voxel_coords', 'voxel_count', 'voxel_mean', 'num_kept', 'num_voxels'])
 Rulebook = namedtuple('Rulebook', ['out_indices', 'nbr', 'out_shape', 'kernel_size', 'subm'])
+SiteIndex = namedtuple('SiteIndex', ['workspace', 'nbytes', 'num_rows', 'batch_size', 'spatial_shape'])
 
 
 def _triple(v):
@@ -104,6 +106,52 @@ def rulebook(indices, batch_size, spatial_shape, kernel_size, stride=1, padding=
     _native.call("pdm_sparse_rulebook", _native.stream(dev), P, indices.data_ptr(), P_out, *geom,
                  None if subm else out_indices.data_ptr(), nbr.data_ptr(), ws.data_ptr(), nbytes)
     return Rulebook(out_indices, nbr, conv_out_shape((D, H, W), k, s, p, subm), k, bool(subm))
+
+
+@torch.no_grad()
+def site_index(indices, batch_size, spatial_shape):
+    """indices (P, 4) int32 (b, z, y, x), distinct sites in any row order on the grid spatial_shape = (D, H, W) -> SiteIndex
+    (pdm_sparse_index): the level's occupancy bitmap, group prefixes and row_of_rank in one workspace tensor, with the geometry
+    it was built for.  roi_grid_pool() looks rows up in it: row_of_rank[rank(key)] is the row at a cell.  1 bit a cell plus 4
+    bytes a row, against the 4 bytes a cell of a dense (B, D, H, W) table.  No host read; can be captured in a graph."""
+    assert indices.is_cuda and indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4, \
+        'indices: int32 (P, 4) rows (b, z, y, x) on the GPU'
+    indices = indices if indices.is_contiguous() else indices.contiguous()
+    D, H, W = (int(v) for v in spatial_shape)
+    P, B, dev = indices.shape[0], int(batch_size), indices.device
+    nbytes = _native.lib().pdm_sparse_index_workspace_bytes(P, B, D, H, W)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    _native.call("pdm_sparse_index", _native.stream(dev), P, indices.data_ptr(), B, D, H, W, ws.data_ptr(), nbytes)
+    return SiteIndex(ws, nbytes, P, B, (D, H, W))
+
+
+@torch.no_grad()
+def roi_grid_pool(rois, grid_size, index, stride, voxel_size, point_cloud_range, features_in, wp, scale_p, shift_p, query_range, radius,
+                  nsample, wout_pack, scale_o, shift_o, c_out, out=None, out_offset=0):
+    """Voxel R-CNN's RoI-grid pooling over one level, one launch (pdm_roi_grid_pool): rois (B, n, 7 + ...) fp32,
+    index = site_index() of the level's rows, features_in (P, C1) the level's features after mlps_in, wp (C1, 3), scale_p,
+    shift_p the folded mlps_pos, query_range (rz, ry, rx), wout_pack = pack_weight of the folded mlps_out weight as
+    (C2, 1, 1, 1, C1), scale_o, shift_o (C2) -> columns [out_offset, out_offset + c_out) of out (B n G^3, row stride), rows
+    r G^3 + g.  No host read, no atomics: two runs and a graph replay give the same bits."""
+    assert rois.is_cuda and rois.dtype == torch.float32 and rois.dim() == 3 and rois.shape[2] >= 7, 'rois: fp32 (B, n, 7 + C) on the GPU'
+    rois = rois if rois.is_contiguous() else rois.contiguous()
+    B, n, G = rois.shape[0], rois.shape[1], int(grid_size)
+    assert B == index.batch_size, (B, index.batch_size)
+    P, C1 = features_in.shape
+    assert features_in.is_cuda and features_in.dtype == torch.float32 and features_in.is_contiguous() and P == index.num_rows
+    M = B * n * G ** 3
+    if out is None:
+        out = torch.empty((M, out_offset + c_out), dtype=torch.float32, device=rois.device)
+    assert out.dim() == 2 and out.shape[0] == M and out.dtype == torch.float32 and out.stride(1) == 1, tuple(out.shape)
+    small = [t.detach().float().contiguous() for t in (wp, scale_p, shift_p, scale_o, shift_o)]
+    rz, ry, rx = (int(v) for v in query_range)
+    D, H, W = index.spatial_shape
+    _native.call("pdm_roi_grid_pool", _native.stream(rois), B, n, rois.shape[2], rois.data_ptr(), G, D, H, W, int(stride),
+                 *(float(v) for v in voxel_size[:3]), *(float(v) for v in point_cloud_range[:3]), P, index.workspace.data_ptr(), index.nbytes,
+                 C1, features_in.data_ptr(), small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr(), rz, ry, rx, float(radius),
+                 int(nsample), int(c_out), wout_pack.data_ptr(), small[3].data_ptr(), small[4].data_ptr(), out.data_ptr(),
+                 out.stride(0) if M else max(out_offset + c_out, 1), int(out_offset))
+    return out
 
 
 def pack_weight(weight):

@@ -16,6 +16,26 @@ def rotate_points_along_z(points, angle):
     return out
 
 
+def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_range):
+    """voxel_coords (N, 3) (z, y, x) of a level at stride downsample_times -> (N, 3) fp32 centres (x, y, z):
+    (float(c) + 0.5) * (float(voxel_size) * downsample_times) + range minimum, three fp32 roundings (the reference's function
+    of this name; the RoI-grid pooling kernel forms the same bits from the cell it visits)."""
+    assert voxel_coords.shape[1] == 3
+    voxel_centers = voxel_coords[:, [2, 1, 0]].float()
+    voxel_size = torch.tensor(voxel_size, device=voxel_centers.device).float() * downsample_times
+    pc_range = torch.tensor(point_cloud_range[0:3], device=voxel_centers.device).float()
+    return (voxel_centers + 0.5) * voxel_size + pc_range
+
+
+def generate_voxel2pinds(sparse_tensor):
+    """A sparse tensor's rows -> the dense (B, D, H, W) int32 table of the row at every cell, -1 where none (the reference's
+    function of this name): 4 bytes a cell, what the composed RoI-grid pooling reads and the fused operator does without."""
+    indices = sparse_tensor.indices.long()
+    table = torch.full([sparse_tensor.batch_size] + list(sparse_tensor.spatial_shape), -1, dtype=torch.int32, device=indices.device)
+    table[indices[:, 0], indices[:, 1], indices[:, 2], indices[:, 3]] = torch.arange(indices.shape[0], device=indices.device, dtype=torch.int32)
+    return table
+
+
 def limit_period(val, offset=0.5, period=np.pi):
     """val folded into [-offset * period, (1 - offset) * period) (the reference's common_utils.limit_period on tensors)"""
     turns = torch.floor(val / period + offset)

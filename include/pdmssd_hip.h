@@ -1118,6 +1118,31 @@ size_t pdm_sparse_to_dense_workspace_bytes(int B, int D, int H, int W);
 int pdm_sparse_to_dense(void *stream, int P, int C, const float *features, const int *indices, int B, int D, int H, int W, float *out,
                         void *workspace, size_t workspace_bytes);
 
+/* The gradients of pdm_sparse_conv (csrc/sparse_conv.hip, csrc/sparse_conv_wgrad.hip).  No float atomics: two
+ * runs and a graph replay give the same bits.
+ * pdm_sparse_rulebook_transpose: nbr (P_out, kvol) -> nbr_t (P_in, kvol), nbr_t[nbr[i][k]][k] = i and -1 elsewhere (at most one
+ *   writer per entry); an entry of nbr outside [0, P_in) counts as -1.  The data gradient of a strided convolution is
+ *   pdm_sparse_conv over nbr_t with the weights packed transposed; a submanifold convolution with odd kernels needs no table
+ *   (nbr_t[j][k] == nbr[j][kvol - 1 - k]).
+ * pdm_sparse_conv_split: pdm_sparse_conv with the same arguments and checks, adding every offset's products in an accumulator of
+ *   their own and that to a running sum (the order of `per offset mm, then add`: about a third of the rounding error of one long
+ *   chain).  The training path's forward and data gradient; as deterministic, but not the same bits as pdm_sparse_conv.
+ * pdm_sparse_conv_wgrad: dy (P_out, Cout), x (P_in, Cin), nbr (P_out, kvol) -> dw (Cout, kvol, Cin) =
+ *   sum over i of dy[i][co] x[nbr[i][k]][ci] on the exact f32 MFMA, every element written (zeros for P_out == 0).  Phase one
+ *   writes one (Cout, Cin padded to 16) partial per (row chunk, offset) to `workspace` (>=
+ *   pdm_sparse_conv_wgrad_workspace_bytes, 8-byte aligned, at most 64 MiB or one chunk's partials), phase two adds the chunks
+ *   in ascending order.  A chunk holds pdm_sparse_conv_wgrad_chunk_rows rows, a function of (P_out, kvol, Cin, Cout) alone.
+ *   Channel sets and kvol <= 27 as pdm_sparse_conv (PDM_E_BADARG otherwise; the two queries return 0). */
+/* align: any (4-byte accesses, 16-byte ones only where the pointer allows), except the workspace: 8 B and wpack: 16 B
+ * (PDM_E_BADARG otherwise). */
+int pdm_sparse_rulebook_transpose(void *stream, int P_out, int P_in, int kvol, const int *nbr, int *nbr_t);
+int pdm_sparse_conv_split(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+                          const float *scale, const float *shift, const float *residual, int relu, float *out);
+int pdm_sparse_conv_wgrad_chunk_rows(int P_out, int kvol, int Cin, int Cout);
+size_t pdm_sparse_conv_wgrad_workspace_bytes(int P_out, int kvol, int Cin, int Cout);
+int pdm_sparse_conv_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
+                          const int *nbr, float *dw, void *workspace, size_t workspace_bytes);
+
 /* Voxel R-CNN's RoI-grid pooling (csrc/sparse_conv.hip, csrc/roi_grid_pool.hip).
  * pdm_sparse_index: indices (P, 4) int32 rows (b, z, y, x), distinct sites in any row order on the grid (B, D, H, W) -> the
  *   level's site index in `workspace` (>= pdm_sparse_index_workspace_bytes, 8-byte aligned): occupancy bitmap, group prefixes

@@ -1,8 +1,9 @@
 """VoxelBackBone8x, VoxelResBackBone8x and SparseBasicBlock of the reference's pcdet/models/backbones_3d/spconv_backbone.py on
-this package's spconv stand-in (hand-written HIP sparse convolution, eval mode): same constructor signatures, config keys
+this package's spconv stand-in (hand-written HIP sparse convolution and its gradients): same constructor signatures, config keys
 (last_pad, USE_BIAS), state_dict keys and batch_dict outputs (encoded_spconv_tensor and its stride, multi_scale_3d_features,
-multi_scale_3d_strides).  Every conv -> BatchNorm1d -> ReLU run is one launch; a SparseBasicBlock is two (conv1 + bn1 + relu,
-conv2 + bn2 + identity + relu).  The four strided convolutions each read their output-site count on the host: four host reads
+multi_scale_3d_strides).  In eval mode without grad every conv -> BatchNorm1d -> ReLU run is one launch; a SparseBasicBlock is
+two (conv1 + bn1 + relu, conv2 + bn2 + identity + relu).  In training mode, or on features that require grad, each convolution
+is an autograd node and BatchNorm1d, the residual and ReLU run in torch behind it (spconv/__init__.py).  The four strided convolutions each read their output-site count on the host: four host reads
 per forward; the submanifold layers read nothing and share one rulebook per indice_key.
 """
 from functools import partial
@@ -40,7 +41,8 @@ class SparseBasicBlock(spconv.SparseModule):
         self.stride = stride
 
     def forward(self, x):
-        """two launches: conv1 + bn1 + relu, then conv2 + bn2 + identity + relu"""
+        """conv1 + bn1 + relu, then conv2 + bn2 + identity + relu: two launches in eval mode without grad, the autograd path of
+        SparseConvolution.forward otherwise"""
         identity = x if self.downsample is None else self.downsample(x)
         out = self.conv1(x, norm=self.bn1, relu=True)
         return self.conv2(out, norm=self.bn2, relu=True, residual=identity.features)

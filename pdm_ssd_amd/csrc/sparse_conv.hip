@@ -231,6 +231,14 @@ __global__ __launch_bounds__(SC_T) void sd_set_kernel(int P, const int *__restri
     const int *c = idx + (size_t)p * 4;
     if (rb_inside(c, B, D, H, W)) table[(((size_t)c[0] * D + c[1]) * H + c[2]) * W + c[3]] = (int)p;
 }
+// the transposed rulebook: nbr_t[nbr[i][k]][k] = i.  For a fixed input row and offset at most one output site exists, so
+// every entry has at most one writer: plain stores, no atomics.  An entry outside [0, P_in) counts as -1, as in the forward.
+__global__ __launch_bounds__(SC_T) void rb_transpose_kernel(long long total, int P_in, int kvol, const int *__restrict__ nbr, int *__restrict__ nbr_t) {
+    const long long t = (long long)blockIdx.x * SC_T + threadIdx.x;
+    if (t >= total) return;
+    const int j = nbr[t];
+    if (j >= 0 && j < P_in) nbr_t[(size_t)j * kvol + (int)(t % kvol)] = (int)(t / kvol);
+}
 // thread = cell of one sample (blockIdx.y): every channel of the cell, zeros included
 __global__ __launch_bounds__(SC_T) void sd_scatter_kernel(int C, long long plane, const float *__restrict__ feat, const int *__restrict__ table,
                                                           float *__restrict__ out) {
@@ -389,6 +397,24 @@ extern "C" int pdm_sparse_rulebook(void *stream, int P_in, const int *in_indices
     hipLaunchKernelGGL(rb_nbr_kernel, dim3((unsigned)divup(total, SC_T)), dim3(SC_T), 0, s, total, a.subm ? in_indices : out_indices, a, in.bits,
                        in.gprefix, row_of_rank, nbr);
     return check_launch("sparse_rulebook(neighbours)");
+}
+
+// nbr (P_out, kvol) input rows or -1 -> nbr_t (P_in, kvol): the output row that reads input row j at offset k, or -1.  What the
+// data gradient of a strided convolution walks: dx[j] = sum over k of W[k]^T dy[nbr_t[j][k]].
+extern "C" int pdm_sparse_rulebook_transpose(void *stream, int P_out, int P_in, int kvol, const int *nbr, int *nbr_t) {
+    PDM_REQUIRE(P_out >= 0 && P_in >= 0, PDM_E_BADARG, "sparse_rulebook_transpose: bad size");
+    PDM_REQUIRE(kvol >= 1 && kvol <= 27, PDM_E_BADARG, "sparse_rulebook_transpose: %d offsets, at most 27", kvol);
+    PDM_REQUIRE((long long)P_out * kvol <= 0x7fffffffll && (long long)P_in * kvol <= 0x7fffffffll, PDM_E_TOOLARGE,
+                "sparse_rulebook_transpose: rows x %d offsets exceed int32", kvol);
+    PDM_REQUIRE((P_out == 0 || nbr) && (P_in == 0 || nbr_t), PDM_E_BADARG, "sparse_rulebook_transpose: null pointer");
+    hipStream_t s = as_stream(stream);
+    const long long n_t = (long long)P_in * kvol, n = (long long)P_out * kvol;
+    if (n_t == 0) return 0;
+    hipLaunchKernelGGL(sd_fill_kernel, dim3((unsigned)divup(n_t, SC_T)), dim3(SC_T), 0, s, n_t, nbr_t);
+    if (int rc = check_launch("sparse_rulebook_transpose(fill)")) return rc;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(rb_transpose_kernel, dim3((unsigned)divup(n, SC_T)), dim3(SC_T), 0, s, n, P_in, kvol, nbr, nbr_t);
+    return check_launch("sparse_rulebook_transpose");
 }
 
 extern "C" size_t pdm_sparse_index_workspace_bytes(int P, int B, int D, int H, int W) {

@@ -6,6 +6,9 @@
 // the A operand of mfma_f32_16x16x4f32 in the packed fragment order of rows_gemm.hip, so that a lane's accumulator holds 4
 // consecutive channels of one row.  No atomics and no split over k: two runs and a graph replay give the same bits.
 // Two LDS stages; the global loads of step s + 2 are in flight while step s computes.
+// SPLIT (pdm_sparse_conv_split, the training path's forward and data gradient): every offset's products are added
+// in an accumulator of their own, which is then added to the running sum: the order of `per offset mm, then add`, whose rounding
+// error is about a third of one long chain's.  The same operands, the same skip, no atomics; other bits than the plain form.
 #include "common.h"
 
 namespace pdm {
@@ -26,7 +29,7 @@ struct ScvArgs {
     float *out;             // (P_out, cout)
 };
 
-template <int NB>
+template <int NB, bool SPLIT>
 __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
     __shared__ int s_nbr[SCV_ROWS * SCV_MAXK];
     __shared__ unsigned s_mask;
@@ -100,9 +103,12 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
         }
     };
 
-    sf4 acc[NB];
+    sf4 acc[NB], sum[SPLIT ? NB : 1];       // SPLIT: acc holds the current offset's products, sum the offsets before it
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int nb = 0; nb < (SPLIT ? NB : 1); ++nb) sum[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+    int kb_of_step = 0;
 
     Regs regs{};
     if (steps > 0) {
@@ -113,6 +119,17 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
     if (steps > 1) { regs = load(lk, lkb); advance(); }
     for (int s = 0; s < steps; ++s) {
         const int cur = s & 1;
+        if (SPLIT) {        // a new offset begins every nkb steps
+            if (kb_of_step == a.nkb) {
+                kb_of_step = 0;
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    sum[nb] += acc[nb];
+                    acc[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+            ++kb_of_step;
+        }
         const sf4 fb = *reinterpret_cast<const sf4 *>(&s_x[cur][(16 * wave + pos) * SCV_HS + 4 * g]);
         sf4 fa[NB];
 #pragma unroll
@@ -126,6 +143,10 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
         __syncthreads();
     }
 
+    if (SPLIT) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = sum[nb] + acc[nb];
+    }
     // lane (pos, g), register j of block nb = out[r0 + 16 wave + pos][16 nb + 4 g + j]
     const int lrow = 16 * wave + pos;
     if (lrow >= live) return;
@@ -176,8 +197,9 @@ extern "C" size_t pdm_sparse_conv_packed_floats(int kvol, int Cin, int Cout) {
 
 // x (P_in, Cin), nbr (P_out, kvol) input rows or -1 (an entry outside [0, P_in) counts as -1), wpack as above (16-byte
 // aligned) -> out (P_out, Cout).  scale and shift come together or not at all; residual (P_out, Cout) or null.
-extern "C" int pdm_sparse_conv(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
-                               const float *scale, const float *shift, const float *residual, int relu, float *out) {
+template <bool SPLIT>
+static int scv_run(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+                   const float *scale, const float *shift, const float *residual, int relu, float *out) {
     PDM_REQUIRE(P_out >= 0 && P_in >= 0, PDM_E_BADARG, "sparse_conv: bad size");
     PDM_REQUIRE(kvol >= 1 && kvol <= SCV_MAXK, PDM_E_BADARG, "sparse_conv: %d offsets, at most %d", kvol, SCV_MAXK);
     PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128, PDM_E_BADARG,
@@ -192,10 +214,22 @@ extern "C" int pdm_sparse_conv(void *stream, int P_out, int P_in, int kvol, int 
     const dim3 grid((unsigned)divup(P_out, SCV_ROWS)), block(SCV_T);
     hipStream_t s = as_stream(stream);
     switch (Cout / 16) {
-        case 1: hipLaunchKernelGGL(sparse_conv_kernel<1>, grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(sparse_conv_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(sparse_conv_kernel<4>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(sparse_conv_kernel<8>, grid, block, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((sparse_conv_kernel<1, SPLIT>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((sparse_conv_kernel<2, SPLIT>), grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((sparse_conv_kernel<4, SPLIT>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((sparse_conv_kernel<8, SPLIT>), grid, block, 0, s, a); break;
     }
     return check_launch("sparse_conv");
+}
+
+extern "C" int pdm_sparse_conv(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+                               const float *scale, const float *shift, const float *residual, int relu, float *out) {
+    return scv_run<false>(stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
+}
+
+// pdm_sparse_conv with one accumulator per offset added to a running sum (the SPLIT form above): what the training path runs in
+// its forward and its data gradient.  Same arguments, same checks, as deterministic; not the same bits as pdm_sparse_conv.
+extern "C" int pdm_sparse_conv_split(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr,
+                                     const float *wpack, const float *scale, const float *shift, const float *residual, int relu, float *out) {
+    return scv_run<true>(stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
 }

@@ -140,8 +140,7 @@ POINT_PILLAR_CFG = {
 # SECOND: DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle on the KITTI voxel grid
 # (VOXEL_SIZE, GRID_SIZE, range [0, -40, -3, 70.4, 40, 1]): the encoded tensor is 128 channels x 2 heights on 200 x 176 cells
 # of 0.4 m (stride 8).  The 2-D backbone and head values are the upstream project's published KITTI SECOND settings (its
-# tools/cfgs/kitti_models/second.yaml) restated as a dict; the anchors are POINT_PILLAR_CFG's at feature_map_stride 8.  The
-# voxel backbone runs in eval mode only.
+# tools/cfgs/kitti_models/second.yaml) restated as a dict; the anchors are POINT_PILLAR_CFG's at feature_map_stride 8.
 SECOND_CFG = {
     'NAME': 'SECONDNet',
     'VFE': {'NAME': 'DynamicMeanVFE'},
@@ -252,7 +251,7 @@ def voxel_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None,
 
 def build_second(model_cfg=None, num_point_features=4, dataset=None):
     """SECONDNet from SECOND_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone ->
-    AnchorHeadSingle, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    AnchorHeadSingle, on voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and takes training steps."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(SECOND_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
@@ -260,7 +259,8 @@ def build_second(model_cfg=None, num_point_features=4, dataset=None):
 
 def build_center_voxel(model_cfg=None, num_point_features=4, dataset=None):
     """CenterPoint from CENTER_VOXEL_CFG (or a dict like it): DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression ->
-    BaseBEVBackbone -> CenterHead, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    BaseBEVBackbone -> CenterHead, on voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and takes
+    training steps."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(CENTER_VOXEL_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

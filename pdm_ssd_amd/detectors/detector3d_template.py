@@ -5,7 +5,7 @@ Contract restated from /root/reference/pcdet/models/detectors/detector3d_templat
 :178-263 (post_processing: per-sample class-agnostic NMS over the head's boxes) and :330-359 (shape-filtered
 checkpoint loading).  The reference's template cannot be imported on this platform (it pulls in spconv,
 pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
-(DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and, in eval mode, the voxel family (DynamicMeanVFE ->
+(DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and the voxel family (DynamicMeanVFE ->
 VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
 outside the registries (MeanVFE, PillarVFE, ...) and the pfe slot are refused.  The roi_head slot builds the RoI heads of
 roi_heads/ (PointRCNN's second stage; Voxel R-CNN's, in eval mode).

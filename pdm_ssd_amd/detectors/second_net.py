@@ -1,6 +1,6 @@
 """SECONDNet: dynamic mean VFE -> sparse 3-D backbone -> height compression -> 2-D backbone -> anchor head, the forward and
 get_training_loss of the reference's pcdet/models/detectors/second_net.py on this repository's template; post_processing is
-the template's.  The voxel backbone runs in eval mode only (spconv/__init__.py).
+the template's.  The voxel backbone trains through the sparse convolution's autograd node (spconv/__init__.py).
 """
 from .detector3d_template import Detector3DTemplate
 
@@ -11,7 +11,7 @@ class SECONDNet(Detector3DTemplate):
         self.module_list = self.build_networks()
 
     def forward(self, batch_dict):
-        """eval: (pred_dicts, recall_dict); training: ({'loss': loss}, tb_dict, disp_dict) once the backbone trains"""
+        """eval: (pred_dicts, recall_dict); training: ({'loss': loss}, tb_dict, disp_dict)"""
         from .. import fused_bn
         with fused_bn.counter_scope():      # the BatchNorm step counters of every stack: one multi-tensor add
             for cur_module in self.module_list:

@@ -1,12 +1,15 @@
 """The voxel path's device operators (csrc/sparse_conv.hip, csrc/sparse_conv_mfma.hip): points -> dynamic voxels with
 means (voxel_assign), the rulebook of a sparse 3-D convolution (rulebook), the convolution itself on the exact f32 MFMA
-(sparse_conv), the dense canvas of a sparse tensor (to_dense), the site index of a level as an object of its own (site_index)
-and Voxel R-CNN's RoI-grid pooling over it (roi_grid_pool, csrc/roi_grid_pool.hip).  An occupancy bitmap with scanned popcounts numbers
+(sparse_conv) with its gradients (rulebook_transpose, pack_weight_transposed, sparse_conv_dgrad, sparse_conv_wgrad of
+csrc/sparse_conv_wgrad.hip, and the autograd node SparseConvFunction over them), the dense canvas of a sparse tensor (to_dense,
+differentiable in the features), the site index of a level as an object of its own (site_index) and Voxel R-CNN's RoI-grid
+pooling over it (roi_grid_pool, csrc/roi_grid_pool.hip).  An occupancy bitmap with scanned popcounts numbers
 voxels and output sites in ascending key order: no host loop, no sort, no hash, no float atomics, so every result is a
-function of the input alone and two runs give the same bits.  Eval mode only: nothing here has a gradient yet.
+function of the input alone and two runs give the same bits, the gradients' included.  voxel_assign, the site index and the
+RoI-grid pooling have no gradient.
 
 Host reads: voxel_assign() copies the two ints {N', P} to the host, and a STRIDED rulebook() copies the one int P_out;
-a submanifold rulebook, sparse_conv(), to_dense(), site_index() and roi_grid_pool() read nothing.  HOST_READS counts the copies.
+a submanifold rulebook, sparse_conv(), to_dense(), site_index(), roi_grid_pool() and the gradients read nothing.  HOST_READS counts the copies.
 
 The torch formulations these stand for (torch.unique + scatter_mean, and per offset index_select -> mm -> index_add_) are
 what the tests and tools/sparse_conv_rate.py compare with.
@@ -171,11 +174,12 @@ def pack_weight(weight):
 
 
 @torch.no_grad()
-def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residual=None, relu=False, out=None):
+def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residual=None, relu=False, out=None, split=False):
     """out[i, :] = epilogue(sum over k ascending of W[k] features[nbr[i, k], :]) (pdm_sparse_conv): features (P_in, cin) fp32,
     nbr (P_out, kvol) int32, wpack = pack_weight(weight); epilogue = * scale + shift (the folded BatchNorm, both or neither),
     + residual (P_out, cout), ReLU.  Output-stationary on the exact f32 MFMA, no atomics: two runs and a graph replay give
-    the same bits.  No host read."""
+    the same bits.  No host read.  split: pdm_sparse_conv_split, which adds every offset's products in an accumulator of their own
+    and that to a running sum (about a third of the rounding error of the one long chain; other bits): the training path's form."""
     assert features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[1] == cin, tuple(features.shape)
     assert nbr.dtype == torch.int32 and nbr.dim() == 2
     features, nbr = features.contiguous(), nbr.contiguous()
@@ -187,16 +191,146 @@ def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residua
         assert residual.shape == (P_out, cout) and residual.dtype == torch.float32
         residual = residual.contiguous()
     opt = [None if t is None else t.detach().float().contiguous() for t in (scale, shift)]
-    _native.call("pdm_sparse_conv", _native.stream(features), P_out, features.shape[0], kvol, cin, cout, features.data_ptr(), nbr.data_ptr(),
+    _native.call("pdm_sparse_conv_split" if split else "pdm_sparse_conv", _native.stream(features), P_out, features.shape[0], kvol, cin, cout, features.data_ptr(), nbr.data_ptr(),
                  wpack.data_ptr(), *(None if t is None else t.data_ptr() for t in opt), None if residual is None else residual.data_ptr(),
                  1 if relu else 0, out.data_ptr())
     return out
 
 
+def pack_weight_transposed(weight, flip=False):
+    """weight (Cout, kz, ky, kx, Cin) -> pack_weight of W^T, the convolution Cout -> Cin (padded to 16 when Cin < 16) that the
+    data gradient runs: [k][kb][nb][lane][j] = W[cout = 16 kb + 4 (lane >> 4) + j][k' ][cin = 16 nb + (lane & 15)], zero past Cin,
+    with k' = k, or k' = kvol - 1 - k when `flip` (the offset order reversed: a submanifold layer's data gradient walks the
+    forward's own nbr, since nbr_t[j][k] == nbr[j][kvol - 1 - k]).  Device arithmetic only."""
+    cout, cin = weight.shape[0], weight.shape[-1]
+    if cin not in CIN_SUPPORTED or cout not in COUT_SUPPORTED:
+        raise ValueError(f'sparse_conv: {cin} -> {cout} channels; Cin in {CIN_SUPPORTED}, Cout in {COUT_SUPPORTED}')
+    w = weight.detach().float().reshape(cout, -1, cin)
+    if flip:
+        w = w.flip(1)
+    w = torch.nn.functional.pad(w.permute(2, 1, 0), (0, 0, 0, 0, 0, max(16 - cin, 0)))      # (cin padded, kvol, cout)
+    return pack_weight(w.reshape(w.shape[0], *weight.shape[1:4], cout))
+
+
 @torch.no_grad()
+def rulebook_transpose(nbr, num_in_rows):
+    """nbr (P_out, kvol) int32 -> nbr_t (num_in_rows, kvol) int32: nbr_t[nbr[i, k], k] = i, -1 elsewhere
+    (pdm_sparse_rulebook_transpose).  At most one output site reads an input row at a given offset, so every entry has one
+    writer: a fill and one launch of plain stores.  No host read."""
+    assert nbr.is_cuda and nbr.dtype == torch.int32 and nbr.dim() == 2
+    nbr = nbr.contiguous()
+    P_out, kvol = nbr.shape
+    nbr_t = torch.empty((int(num_in_rows), kvol), dtype=torch.int32, device=nbr.device)
+    _native.call("pdm_sparse_rulebook_transpose", _native.stream(nbr), P_out, int(num_in_rows), kvol, nbr.data_ptr(), nbr_t.data_ptr())
+    return nbr_t
+
+
+def wgrad_chunk_rows(num_out_rows, kvol, cin, cout):
+    """rows of one chunk of sparse_conv_wgrad's first phase: a function of these four numbers alone"""
+    return _native.lib().pdm_sparse_conv_wgrad_chunk_rows(int(num_out_rows), int(kvol), int(cin), int(cout))
+
+
+@torch.no_grad()
+def sparse_conv_wgrad(dy, features, nbr, kernel_size, out=None):
+    """dW (Cout, kz, ky, kx, Cin)[co, k, ci] = sum over i of dy[i, co] features[nbr[i, k], ci] (pdm_sparse_conv_wgrad): dy (P_out,
+    Cout), features (P_in, Cin) fp32, nbr (P_out, kvol) int32.  Rows are the contraction of the exact f32 MFMA; partial blocks
+    per (row chunk, offset) in a workspace, then one launch adds the chunks in ascending order.  No atomics, chunk boundaries a
+    function of the sizes alone: two runs and a graph replay give the same bits.  No host read."""
+    assert dy.is_cuda and dy.dtype == torch.float32 and dy.dim() == 2 and features.dtype == torch.float32 and features.dim() == 2
+    assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == dy.shape[0], (tuple(nbr.shape), tuple(dy.shape))
+    dy, features, nbr = dy.contiguous(), features.contiguous(), nbr.contiguous()
+    k = _triple(kernel_size)
+    (P_out, kvol), cin, cout = nbr.shape, features.shape[1], dy.shape[1]
+    assert kvol == k[0] * k[1] * k[2], (kvol, k)
+    if out is None:
+        out = torch.empty((cout, *k, cin), dtype=torch.float32, device=dy.device)
+    assert out.shape == (cout, *k, cin) and out.is_contiguous() and out.dtype == torch.float32
+    nbytes = _native.lib().pdm_sparse_conv_wgrad_workspace_bytes(P_out, kvol, cin, cout)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dy.device)
+    _native.call("pdm_sparse_conv_wgrad", _native.stream(dy), P_out, features.shape[0], kvol, cin, cout, dy.data_ptr(), features.data_ptr(),
+                 nbr.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes)
+    return out
+
+
+def sparse_conv_dgrad(dy, table, wpack_t, cin, cout):
+    """dx (P_in, cin) = sum over k of W[k]^T dy[table[:, k]]: the forward kernel (its split form) over `table` (P_in, kvol), which is
+    rulebook_transpose(nbr, P_in) with wpack_t = pack_weight_transposed(weight), or a submanifold layer's own nbr with
+    wpack_t = pack_weight_transposed(weight, flip=True).  Sliced to cin when the pack padded it to 16."""
+    cin_p = max(cin, 16)
+    dx = sparse_conv(dy, table, wpack_t, cout, cin_p, split=True)
+    return dx if cin_p == cin else dx[:, :cin].contiguous()
+
+
+class SparseConvFunction(torch.autograd.Function):
+    """out = pdm_sparse_conv_split(features, nbr, W) + bias, with its gradients: dW by sparse_conv_wgrad, dbias = dy.sum(0), and, when
+    the input requires grad, dx by sparse_conv_dgrad.  nbr_t: rulebook_transpose(nbr, P_in), or True for a submanifold layer
+    (odd kernels), whose data gradient walks nbr itself; None when the input takes no gradient.  wpack / wpack_t: the packed
+    weights when the caller keeps them (pack_weight, pack_weight_transposed with flip = nbr_t is True), else packed here."""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, nbr, nbr_t, cin, cout, wpack=None, wpack_t=None):
+        assert weight.shape[0] == cout and weight.shape[-1] == cin and weight.dim() == 5, (tuple(weight.shape), cin, cout)
+        features = features.contiguous()
+        if wpack is None:
+            wpack = pack_weight(weight)
+        shift = None if bias is None else bias.detach()
+        out = sparse_conv(features.detach(), nbr, wpack, cin, cout, None if shift is None else torch.ones_like(shift), shift, split=True)
+        ctx.save_for_backward(features, weight, nbr, nbr_t if torch.is_tensor(nbr_t) else None, wpack_t)
+        ctx.subm_identity, ctx.has_bias, ctx.dims = nbr_t is True, bias is not None, (cin, cout)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        features, weight, nbr, nbr_t, wpack_t = ctx.saved_tensors
+        cin, cout = ctx.dims
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            table = nbr if ctx.subm_identity else nbr_t
+            if table is None:
+                raise RuntimeError('SparseConvFunction: the input requires grad but no transposed rulebook was given')
+            if wpack_t is None:
+                wpack_t = pack_weight_transposed(weight, flip=ctx.subm_identity)
+            dx = sparse_conv_dgrad(dy, table, wpack_t, cin, cout)
+        if ctx.needs_input_grad[1]:
+            dw = sparse_conv_wgrad(dy, features, nbr, weight.shape[1:4])
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum(0)
+        return dx, dw, db, None, None, None, None, None, None
+
+
+class ToDenseFunction(torch.autograd.Function):
+    """to_dense with the gradient of `features`: the canvas gradient gathered at `indices` (rows outside the grid, which the
+    forward skips, take zero).  Torch indexing: no host read, no kernel of its own."""
+
+    @staticmethod
+    def forward(ctx, features, indices, batch_size, spatial_shape):
+        ctx.save_for_backward(indices)
+        ctx.grid = (int(batch_size), *(int(v) for v in spatial_shape))
+        return to_dense(features.detach(), indices, batch_size, spatial_shape)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (indices,) = ctx.saved_tensors
+        i = indices.long()
+        hi = torch.tensor(ctx.grid, dtype=torch.long, device=i.device)
+        inside = ((i >= 0) & (i < hi)).all(1)
+        i = torch.minimum(i.clamp_min(0), hi - 1)
+        g = grad[i[:, 0], :, i[:, 1], i[:, 2], i[:, 3]]
+        return g * inside[:, None].to(g.dtype), None, None, None
+
+
 def to_dense(features, indices, batch_size, spatial_shape, out=None):
     """features (P, C) fp32, indices (P, 4) int32 (b, z, y, x) -> (B, C, D, H, W): SparseConvTensor.dense().  One launch
-    writes every element, zeros included, behind a small cell table (pdm_sparse_to_dense).  No host read."""
+    writes every element, zeros included, behind a small cell table (pdm_sparse_to_dense).  No host read.  Differentiable in
+    `features` (ToDenseFunction) when they require grad and no `out` is given."""
+    if out is None and features.requires_grad and torch.is_grad_enabled():
+        return ToDenseFunction.apply(features, indices, batch_size, spatial_shape)
+    return _to_dense(features, indices, batch_size, spatial_shape, out)
+
+
+@torch.no_grad()
+def _to_dense(features, indices, batch_size, spatial_shape, out=None):
     assert features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[0] == indices.shape[0]
     assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4
     features, indices = features.contiguous(), indices.contiguous()

@@ -2,10 +2,13 @@
 backbones read like the reference's: SparseConvTensor, SubMConv3d, SparseConv3d, SparseSequential, SparseModule.  Weights
 keep spconv 2.x's layout (Cout, kz, ky, kx, Cin) and its state_dict keys (weight, bias).
 
-Eval mode only.  A convolution followed by BatchNorm1d and ReLU inside a SparseSequential is ONE pdm_sparse_conv launch (the
-BatchNorm folded into the epilogue on the device); a module in training mode, or an input that requires grad, raises
-NotImplementedError: the convolution's gradients and BatchNorm over active rows are the next step.  SparseInverseConv3d is
-not built.
+Eval mode without grad: a convolution followed by BatchNorm1d and ReLU inside a SparseSequential is ONE pdm_sparse_conv
+launch (the BatchNorm folded into the epilogue on the device).  A module or its norm in training mode, or an input that
+requires grad, takes the autograd path on CUDA tensors: sparse_conv_ops.SparseConvFunction (forward and data gradient by
+pdm_sparse_conv_split, the forward kernel with one accumulator per offset, the latter over the transposed rulebook; weight
+gradient by pdm_sparse_conv_wgrad), then the BatchNorm1d module itself on the
+(P, C) features (batch statistics over the active rows), + residual, ReLU, all in torch.  CPU tensors there raise
+NotImplementedError.  SparseInverseConv3d is not built.
 
 A rulebook is built once per indice_key per forward and shared by the layers that name the key (the tensors of one forward
 share one indice_dict), as spconv shares them.  Row orders: a submanifold convolution keeps its input's rows; a strided one
@@ -35,7 +38,7 @@ class SparseConvTensor:
         return SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict)
 
     def dense(self):
-        """(B, C, D, H, W), zeros where no site is active: one launch writes every element"""
+        """(B, C, D, H, W), zeros where no site is active: one launch writes every element; differentiable in the features"""
         return sparse_conv_ops.to_dense(self.features, self.indices, self.batch_size, self.spatial_shape)
 
 
@@ -102,14 +105,42 @@ class SparseConvolution(SparseModule):
             x.indice_dict[self.indice_key] = rb
         return rb
 
+    def get_transpose(self, x, rb):
+        """the transposed table of a strided rulebook, built once per forward beside the rulebook it belongs to (under the
+        key (indice_key, 'nbr_t') of the tensors' shared indice_dict)"""
+        key = (self.indice_key, 'nbr_t')
+        nbr_t = x.indice_dict.get(key) if self.indice_key is not None else None
+        if nbr_t is None:
+            nbr_t = sparse_conv_ops.rulebook_transpose(rb.nbr, x.features.shape[0])
+            if self.indice_key is not None:
+                x.indice_dict[key] = nbr_t
+        return nbr_t
+
     def forward(self, x, norm=None, relu=False, residual=None):
-        """x -> SparseConvTensor of epilogue(conv(x)): one launch.  norm: an eval BatchNorm1d folded into the epilogue;
-        residual: (P_out, Cout) added behind it; relu last."""
-        if self.training or (norm is not None and norm.training) or x.features.requires_grad:
+        """x -> SparseConvTensor of epilogue(conv(x)).  norm: a BatchNorm1d; residual: (P_out, Cout) added behind it; relu
+        last.  Eval mode without grad: one launch, the norm folded into the epilogue.  Training mode (the module's or the
+        norm's) or an input that requires grad: the autograd path, norm, residual and ReLU in torch."""
+        grad_path = self.training or (norm is not None and norm.training) or x.features.requires_grad
+        if grad_path and not x.features.is_cuda:
             raise NotImplementedError(NEXT_STEP)
         assert x.features.shape[1] == self.in_channels, (tuple(x.features.shape), self.in_channels)
         rb = self.get_rulebook(x)
         wpack = self._cached('pack', [self.weight], lambda: sparse_conv_ops.pack_weight(self.weight))
+        if grad_path:
+            nbr_t = wpack_t = None
+            if x.features.requires_grad and torch.is_grad_enabled():
+                identity = self.subm and all(k % 2 == 1 for k in self.kernel_size)      # nbr_t[j][k] == nbr[j][kvol - 1 - k]
+                nbr_t = True if identity else self.get_transpose(x, rb)
+                wpack_t = self._cached('pack_t', [self.weight], lambda: sparse_conv_ops.pack_weight_transposed(self.weight, flip=identity))
+            out = sparse_conv_ops.SparseConvFunction.apply(x.features, self.weight, self.bias, rb.nbr, nbr_t, self.in_channels,
+                                                           self.out_channels, wpack, wpack_t)
+            if norm is not None:
+                out = norm(out)
+            if residual is not None:
+                out = out + residual
+            if relu:
+                out = torch.relu(out)
+            return SparseConvTensor(out, rb.out_indices, rb.out_shape, x.batch_size, x.indice_dict)
         sources = [self.bias] + ([norm.weight, norm.bias, norm.running_mean, norm.running_var] if norm is not None else [])
         scale, shift = self._cached('fold', sources, lambda: fold_norm(norm, self.bias, self.out_channels, self.weight))
         out = sparse_conv_ops.sparse_conv(x.features, rb.nbr, wpack, self.in_channels, self.out_channels, scale, shift, residual, relu)
@@ -129,8 +160,9 @@ class SparseConv3d(SparseConvolution):
 
 
 class SparseSequential(SparseModule, nn.Sequential):
-    """nn.Sequential over SparseConvTensors: sparse modules take the tensor, plain nn modules its features.  In eval mode
-    a convolution takes the BatchNorm1d and the ReLU behind it into its own launch."""
+    """nn.Sequential over SparseConvTensors: sparse modules take the tensor, plain nn modules its features.  A convolution
+    takes the BatchNorm1d and the ReLU behind it: into its own launch in eval mode without grad, behind its autograd node
+    otherwise."""
 
     def forward(self, x):
         mods = list(self)
@@ -147,7 +179,7 @@ class SparseSequential(SparseModule, nn.Sequential):
             if isinstance(m, SparseModule):
                 x = m(x)
             elif isinstance(x, SparseConvTensor):
-                if self.training or x.features.requires_grad:
+                if (self.training or x.features.requires_grad) and not x.features.is_cuda:
                     raise NotImplementedError(NEXT_STEP)
                 x = x.replace_feature(m(x.features))
             else:

@@ -1168,6 +1168,44 @@ int pdm_roi_grid_pool(void *stream, int B, int n, int roi_stride, const float *r
                       float radius, int nsample, int C2, const float *wout, const float *scale_o, const float *shift_o, float *out,
                       int out_stride, int out_offset);
 
+/* The training form of the RoI-grid pooling (csrc/roi_grid_train.hip): a query that keeps the groups, a pooling
+ * over the kept groups that records the winning slot, and the gradients.  M = B n G^3 <= 2^22 grid points (PDM_E_TOOLARGE
+ * beyond; the size queries return 0), S = nsample <= 32, C1 in {16, 32, 64} (PDM_E_BADARG otherwise).  No float atomics, no
+ * host read; the three entry points can be captured in a graph from the calling thread: two runs and a graph replay give the
+ * same bits.
+ * pdm_roi_grid_query: the geometry, window and site_index arguments and rules of pdm_roi_grid_pool, the same fp32 operation
+ *   order.  grp_row (M, S) int32: the rows of the group in window order, -1 in unused slots; grp_off (M, S, 3) fp32: centre - p
+ *   as (x, y, z), 0 in unused slots; moments (9) float64: [sum x, y, z, xx, xy, xz, yy, yz, zz] of the offsets over the M S slots
+ *   of the reference's padded tensor (slot s < count once, slot 0 a further S - count times, an empty group S zero offsets).
+ *   One partial per tile of 16 grid points in `workspace` (>= pdm_roi_grid_query_workspace_bytes), added in ascending order by
+ *   one workgroup.  Two launches.
+ * pdm_roi_grid_pool_train: pooled[m][c] = max over the group of relu(features_in[row][c] + fma(dot(wp[c], off), scale_p[c],
+ *   shift_p[c])) with dot = fma(wz, dz, fma(wy, dy, wx dx)), relu(shift_p[c]) for an empty group (grp_row[m][0] == -1): the bits
+ *   of pdm_roi_grid_pool's pooled value.  arg[m][c] uint8: the lowest slot that attains the maximum, 0xFF where pooled is 0, 0
+ *   for an empty group with shift_p[c] > 0.  A slot whose value is NaN (non-finite inputs only) never wins the strict
+ *   comparison: it is passed over, where torch's relu / max_pool would hand the NaN on.  One launch.
+ * pdm_roi_grid_pool_grad: for every (m, c) with s = arg[m][c] != 0xFF and g = gpool[m][c]: dshift_p[c] += g, and unless the
+ *   group is empty dfeatures_in[grp_row[m][s]][c] += g, dscale_p[c] += g dot, dwp[c][:] += g scale_p[c] grp_off[m][s][:].
+ *   dfeatures_in is summed as llrint(g 2^k) in 64 bits with integer atomics, 2^k the power of two that puts max|gpool| (an
+ *   integer maximum on the device) in [2^40, 2^41), and converted once; a non-finite gpool makes all of it NaN.  The parameter
+ *   sums: one partial per pdm_roi_grid_pool_grad_chunk_points(M, C1) grid points, added in ascending order.  Every element of
+ *   the four outputs is written.  Four launches behind one zero fill of `workspace`
+ *   (>= pdm_roi_grid_pool_grad_workspace_bytes). */
+/* align: any (4-byte accesses), except moments and the workspaces: 8 B (PDM_E_BADARG otherwise). */
+size_t pdm_roi_grid_query_workspace_bytes(long long M);
+int pdm_roi_grid_query(void *stream, int B, int n, int roi_stride, const float *rois, int G, int D, int H, int W, int stride, float vx,
+                       float vy, float vz, float x0, float y0, float z0, int P, const void *site_index, size_t site_index_bytes, int rz,
+                       int ry, int rx, float radius, int nsample, int *grp_row, float *grp_off, double *moments, void *workspace,
+                       size_t workspace_bytes);
+int pdm_roi_grid_pool_train(void *stream, long long M, int nsample, int P, int C1, const int *grp_row, const float *grp_off,
+                            const float *features_in, const float *wp, const float *scale_p, const float *shift_p, float *pooled,
+                            unsigned char *arg);
+int pdm_roi_grid_pool_grad_chunk_points(long long M, int C1);
+size_t pdm_roi_grid_pool_grad_workspace_bytes(long long M, int P, int C1);
+int pdm_roi_grid_pool_grad(void *stream, long long M, int nsample, int P, int C1, const float *gpool, const unsigned char *arg,
+                           const int *grp_row, const float *grp_off, const float *wp, const float *scale_p, float *dfeatures_in,
+                           float *dwp, float *dscale_p, float *dshift_p, void *workspace, size_t workspace_bytes);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -12,15 +12,13 @@
 // fragment order of sparse_conv_mfma.hip, staged once per workgroup) and the epilogue relu(acc * scale + shift), written at
 // a column offset into rows of the full stride.  No atomics and nothing summed across waves: two runs and a graph replay give
 // the same bits.
-#include "sc_index.h"
+#include "roi_grid_geom.h"
 
 namespace pdm {
 
 typedef float gf4 __attribute__((ext_vector_type(4)));
 
 constexpr int RGP_T = 256;          // 4 waves
-constexpr int RGP_TILE = 16;        // grid points per wave tile: the MFMA's 16 columns
-constexpr int RGP_MAXS = 32;        // nsample at most
 constexpr int RGP_HS = 24;          // LDS row stride of a 16-channel slice of the pooled rows (sparse_conv_mfma.hip's SCV_HS)
 constexpr int RGP_MAXBLOCKS = 2048; // workgroups at most; waves walk the tiles with this stride
 
@@ -41,17 +39,6 @@ struct RgpArgs {
     float *out;
 };
 
-// floor(a / s) for s >= 1
-__device__ __forceinline__ int floor_div(int a, int s) {
-    const int q = a / s;
-    return (a % s != 0 && a < 0) ? q - 1 : q;
-}
-// floor((g - r0) / voxel) as an int; far outside (and NaN) -> a cell no window reaches
-__device__ __forceinline__ int rgp_cell0(float g, float r0, float voxel) {
-    const float c = floorf(__fdiv_rn(__fsub_rn(g, r0), voxel));
-    return (c > -1.0e9f && c < 1.0e9f) ? (int)c : -(1 << 30);
-}
-
 template <int C1, int NB>
 __global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
     constexpr int NKB = C1 / 16, SUB = 64 / C1;
@@ -67,76 +54,22 @@ __global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
 
     const int c = lane % C1, sub = lane / C1;       // gather role: channel c of the hits sub, sub + SUB, ...
     const float wpx = a.wp[c * 3], wpy = a.wp[c * 3 + 1], wpz = a.wp[c * 3 + 2], sp = a.scale_p[c], hp = a.shift_p[c];
-    const float r2 = __fmul_rn(a.radius, a.radius);
-    const float sx = __fmul_rn(a.vox[0], (float)a.stride), sy = __fmul_rn(a.vox[1], (float)a.stride), sz = __fmul_rn(a.vox[2], (float)a.stride);
-    const int wy = 2 * a.ry + 1, wx = 2 * a.rx + 1, window = (2 * a.rz + 1) * wy * wx;
-    const int mzyx = (1 << 20) / (wy * wx) + 1, mx = (1 << 20) / wx + 1;       // w / d = (w m) >> 20 exactly for w < 1024, d <= 81
-    const int G = a.G, G3 = G * G * G;
+    const RgpWalk k = rgp_walk_of(a);
     const long long ntiles = (a.M + RGP_TILE - 1) / RGP_TILE;
     float *pool = s_pool[wave];
     int *hrow = s_hrow[wave];
     float *hd = s_hd[wave];
 
     for (long long tile = (long long)blockIdx.x * (RGP_T / 64) + wave; tile < ntiles; tile += (long long)gridDim.x * (RGP_T / 64)) {
-        // the tile's 16 grid points, one per lane (lanes 16 and up repeat them): the trigonometry runs once a point, not once a lane
         float pgx, pgy, pgz;
         int pcx, pcy, pcz, pb;
-        {
-            const int m = (int)min(tile * RGP_TILE + (lane & 15), a.M - 1);
-            const int r = m / G3, gi = m - r * G3, ix = gi / (G * G), iy = (gi / G) % G, iz = gi % G;      // nonzero()'s order
-            const float *roi = a.rois + (size_t)r * a.roi_stride;
-            const float dxs = roi[3], dys = roi[4], dzs = roi[5], head = roi[6];
-            const float lx = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)ix, 0.5f), (float)G), dxs), __fdiv_rn(dxs, 2.0f));
-            const float ly = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iy, 0.5f), (float)G), dys), __fdiv_rn(dys, 2.0f));
-            const float lz = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iz, 0.5f), (float)G), dzs), __fdiv_rn(dzs, 2.0f));
-            const float cs = cosf(head), sn = sinf(head);
-            pgx = __fadd_rn(__fsub_rn(__fmul_rn(lx, cs), __fmul_rn(ly, sn)), roi[0]);
-            pgy = __fadd_rn(__fadd_rn(__fmul_rn(lx, sn), __fmul_rn(ly, cs)), roi[1]);
-            pgz = __fadd_rn(lz, roi[2]);
-            pb = r / a.n;
-            pcx = floor_div(rgp_cell0(pgx, a.r0[0], a.vox[0]), a.stride);
-            pcy = floor_div(rgp_cell0(pgy, a.r0[1], a.vox[1]), a.stride);
-            pcz = floor_div(rgp_cell0(pgz, a.r0[2], a.vox[2]), a.stride);
-        }
+        rgp_tile_points(a, k, tile, lane, pgx, pgy, pgz, pcx, pcy, pcz, pb);
         for (int i = 0; i < RGP_TILE; ++i) {
             if (tile * RGP_TILE + i >= a.M) break;
             const float gx = __shfl(pgx, i, 64), gy = __shfl(pgy, i, 64), gz = __shfl(pgz, i, 64);
             const int cx = __shfl(pcx, i, 64), cy = __shfl(pcy, i, 64), cz = __shfl(pcz, i, 64), b = __shfl(pb, i, 64);
 
-            // the first nsample in-radius voxels of the window, in window order
-            int cnt = 0;
-            for (int base = 0; base < window && cnt < a.nsample; base += 64) {
-                const int w = base + lane;
-                bool hit = false;
-                int row = -1;
-                float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-                if (w < window) {
-                    const int wz = (w * mzyx) >> 20, rem = w - wz * (wy * wx), wyy = (rem * mx) >> 20;
-                    const int z = cz + wz - a.rz, y = cy + wyy - a.ry, x = cx + (rem - wyy * wx) - a.rx;
-                    if (z >= 0 && z < a.D && y >= 0 && y < a.H && x >= 0 && x < a.W) {
-                        // the sphere first: it needs no memory, and most cells of a window fail it
-                        ddx = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)x, 0.5f), sx), a.r0[0]), gx);
-                        ddy = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)y, 0.5f), sy), a.r0[1]), gy);
-                        ddz = __fsub_rn(__fadd_rn(__fmul_rn(__fadd_rn((float)z, 0.5f), sz), a.r0[2]), gz);
-                        if (!(sqdist(ddx, ddy, ddz) > r2)) {
-                            const long long key = rb_key(b, z, y, x, a.D, a.H, a.W);
-                            if (sc_test(a.bits, key)) {
-                                row = a.row_of_rank[sc_rank(a.bits, a.gprefix, key)];
-                                hit = row >= 0 && row < a.P;
-                            }
-                        }
-                    }
-                }
-                const unsigned long long mask = __ballot(hit);
-                if (mask == 0) continue;
-                const int slot = cnt + lanes_below(mask, lane);
-                if (hit && slot < a.nsample) {
-                    hrow[slot] = row;
-                    hd[slot * 3] = ddx; hd[slot * 3 + 1] = ddy; hd[slot * 3 + 2] = ddz;
-                }
-                cnt += __popcll(mask);
-            }
-            cnt = min(cnt, a.nsample);
+            const int cnt = rgp_window_hits(a, k, lane, gx, gy, gz, cx, cy, cz, b, hrow, hd);
             __builtin_amdgcn_wave_barrier();
 
             // lanes are channels: max over the group of relu(feature + position term); an empty group is relu(shift_p)

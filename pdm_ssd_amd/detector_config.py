@@ -170,8 +170,8 @@ CENTER_VOXEL_CFG = {
 # snapshot this repository was modelled on holds no YAML for this detector, so the ROI_HEAD values are BUILD-DEFINED: they
 # restate the upstream project's KITTI setting for Voxel R-CNN as far as it is remembered here (class-agnostic head, 6 x 6 x 6
 # grid, one scale of 32 -> 32 channels per level with a 9 x 9 x 9 window and 16 samples, radii 0.4 / 0.8 / 1.6 m, three FC
-# stacks of 256 -> 256, dropout 0.3, 100 test-time proposals at NMS 0.7) and were not checked against that file.  The second
-# stage runs in eval mode only: of TARGET_CONFIG it holds the box coder alone.
+# stacks of 256 -> 256, dropout 0.3, 100 test-time proposals at NMS 0.7) and were not checked against that file.  Of
+# TARGET_CONFIG it holds the box coder alone, so its second stage has no training half (VOXEL_RCNN_TRAIN_CFG below adds it).
 _VOXEL_RCNN_POOL = {'MLPS': [[32, 32]], 'QUERY_RANGES': [[4, 4, 4]], 'NSAMPLE': [16], 'POOL_METHOD': 'max_pool'}
 VOXEL_RCNN_CFG = copy.deepcopy(SECOND_CFG)
 VOXEL_RCNN_CFG['NAME'] = 'VoxelRCNN'
@@ -187,6 +187,18 @@ VOXEL_RCNN_CFG['ROI_HEAD'] = {
                                       'x_conv3': dict(copy.deepcopy(_VOXEL_RCNN_POOL), POOL_RADIUS=[0.8]),
                                       'x_conv4': dict(copy.deepcopy(_VOXEL_RCNN_POOL), POOL_RADIUS=[1.6])}},
     'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
+
+# VOXEL_RCNN_CFG plus the proposal-target sampler (TARGET_CONFIG) and the rcnn loss settings (LOSS_CONFIG): a head built from
+# this dict has the training half, and build_voxel_rcnn(VOXEL_RCNN_TRAIN_CFG) takes training steps.  BUILD-DEFINED like the
+# dict above: the values restate the upstream project's KITTI setting for Voxel R-CNN as remembered (IoU-graded class targets
+# between 0.25 and 0.75, regression on proposals above 0.55) and were not checked against that file.
+VOXEL_RCNN_TRAIN_CFG = copy.deepcopy(VOXEL_RCNN_CFG)
+VOXEL_RCNN_TRAIN_CFG['ROI_HEAD']['TARGET_CONFIG'].update(
+    ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE='roi_iou', CLS_FG_THRESH=0.75, CLS_BG_THRESH=0.25,
+    CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
+VOXEL_RCNN_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
+    'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
+    'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0, 'code_weights': [1.0] * 7}}
 
 
 def synthetic_dataset(num_point_features=4):
@@ -267,8 +279,9 @@ def build_center_voxel(model_cfg=None, num_point_features=4, dataset=None):
 
 
 def build_voxel_rcnn(model_cfg=None, num_point_features=4, dataset=None):
-    """VoxelRCNN from VOXEL_RCNN_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone ->
-    AnchorHeadSingle -> VoxelRCNNHead, on voxel_dataset() unless another dataset namespace is given.  Eval mode only."""
+    """VoxelRCNN from VOXEL_RCNN_CFG, VOXEL_RCNN_TRAIN_CFG (with the second stage's training half) or a dict like them:
+    DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle -> VoxelRCNNHead, on
+    voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and, from the training dict, takes training steps."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(VOXEL_RCNN_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

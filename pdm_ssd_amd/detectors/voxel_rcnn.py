@@ -1,7 +1,6 @@
 """VoxelRCNN: SECOND's front (dynamic mean VFE -> sparse 3-D backbone -> height compression -> 2-D backbone -> anchor head) and
 VoxelRCNNHead on the backbone's multi-scale levels: the forward and get_training_loss of the reference's
-pcdet/models/detectors/voxel_rcnn.py on this repository's template; post_processing is the template's.  Eval mode only: the
-voxel backbone and the RoI-grid pooling have no gradient yet.
+pcdet/models/detectors/voxel_rcnn.py on this repository's template; post_processing is the template's.
 """
 from .detector3d_template import Detector3DTemplate
 
@@ -12,7 +11,7 @@ class VoxelRCNN(Detector3DTemplate):
         self.module_list = self.build_networks()
 
     def forward(self, batch_dict):
-        """eval: (pred_dicts, recall_dict); training: ({'loss': loss}, tb_dict, disp_dict) once the backbone and the pooling train"""
+        """eval: (pred_dicts, recall_dict); training: ({'loss': loss}, tb_dict, disp_dict)"""
         from .. import fused_bn
         with fused_bn.counter_scope():      # the BatchNorm step counters of every stack: one multi-tensor add
             for cur_module in self.module_list:

@@ -4,10 +4,14 @@ constructor, `forward` signature and state_dict keys (groupers, mlps_in, mlps_po
 Two paths compute the same thing:
   * forward(): the reference's own formulation on the operators this package already has (VoxelQueryAndGrouping over a dense
     voxel -> row table, two grouped tensors, Conv2d + BatchNorm2d on the offsets, ReLU, pooling, the output layer).  It is the
-    on-device checker of the fused operator and the path for what that operator refuses (avg_pool, other widths, training).
+    on-device checker of the fused operators and the path for what they refuse (avg_pool, other widths).
   * forward_fused(): one contraction for mlps_in over the level's rows and ONE launch of pdm_roi_grid_pool per scale
-    (csrc/roi_grid_pool.hip), which writes straight into its columns of the caller's output rows.  Eval mode
-    only; no host read.  The folded and packed weights are cached per parameter version.
+    (csrc/roi_grid_pool.hip), which writes straight into its columns of the caller's output rows.  The eval
+    form; no host read.  The folded and packed weights are cached per parameter version.
+  * forward_fused_train(): the training form (csrc/roi_grid_train.hip).  mlps_in and mlps_out are the modules
+    themselves (batch statistics over the level's rows and over the pooled rows); per scale one query that keeps the groups
+    and the moments of the padded offsets, the position BatchNorm's batch statistics from those moments under autograd, and
+    the autograd node RoIGridPoolFunction.  No dense table, no grouped tensor, no host read.
 """
 from typing import List
 
@@ -97,9 +101,9 @@ class NeighborVoxelSAModuleMSG(nn.Module):
 
     # ------------------------------------------------------------------ the fused operator
 
-    def fused_supported(self, grid_size):
-        """whether pdm_roi_grid_pool (and the mlps_in contraction) serves every scale of this module"""
-        if self.training or self.pool_method != 'max_pool' or not 1 <= int(grid_size) <= FUSED_MAX_GRID:
+    def _within_fused_limits(self, grid_size):
+        """the configurations the fused operators serve, eval and training form alike"""
+        if self.pool_method != 'max_pool' or not 1 <= int(grid_size) <= FUSED_MAX_GRID:
             return False
         for k, g in enumerate(self.groupers):
             cin, c1, c2 = self.mlps_in[k][0].in_channels, self.mlps_in[k][0].out_channels, self.mlps_out[k][0].out_channels
@@ -110,6 +114,14 @@ class NeighborVoxelSAModuleMSG(nn.Module):
             if not 1 <= int(g.nsample) <= FUSED_MAX_NSAMPLE or not float(g.radius) >= 0:
                 return False
         return True
+
+    def fused_supported(self, grid_size):
+        """whether pdm_roi_grid_pool (and the mlps_in contraction) serves every scale of this module: eval mode only"""
+        return not self.training and self._within_fused_limits(grid_size)
+
+    def fused_train_supported(self, grid_size):
+        """whether forward_fused_train serves every scale of this module: fused_supported()'s limits, in training mode"""
+        return self.training and self._within_fused_limits(grid_size)
 
     def _folded(self, k):
         """the scale's folded and packed tensors, made once per version of its parameters and buffers (as
@@ -148,3 +160,59 @@ class NeighborVoxelSAModuleMSG(nn.Module):
                                           f['shift_out'], c2, out=out, out_offset=out_offset)
             out_offset += c2
         return out_offset
+
+    # ------------------------------------------------------------------ the fused operator, training
+
+    @staticmethod
+    def _position_norm(conv, norm, moments, num_slots):
+        """Training-mode BatchNorm2d behind Conv2d(3 -> C1) over the padded (1, 3, M, nsample) offsets, from the nine moments of
+        those offsets: the layer is linear, so mean_c = W[c] . mean and var_c = W[c]^T Cov W[c].  The moments are float64
+        constants, the weight is under autograd, so the gradient runs through the statistics as BatchNorm's own backward does.
+        Updates the running statistics as nn.BatchNorm2d would (unbiased variance, momentum None = cumulative average).
+        -> (scale_p, shift_p) fp32 with position term = dot(W[c], d) scale_p[c] + shift_p[c]."""
+        w = conv.weight.reshape(conv.out_channels, 3)
+        n = float(num_slots)
+        m = moments / n                                                     # (9) float64, no gradient
+        mean3 = m[0:3]
+        second = torch.stack([m[3], m[4], m[5], m[4], m[6], m[7], m[5], m[7], m[8]]).view(3, 3)
+        cov = second - mean3.view(3, 1) * mean3.view(1, 3)
+        wd = w.double()
+        mean = (wd @ mean3).to(w.dtype)
+        var = ((wd @ cov) * wd).sum(1).clamp_min(0).to(w.dtype)
+        if norm.track_running_stats and norm.running_mean is not None:
+            with torch.no_grad():
+                norm.num_batches_tracked += 1
+                factor = 1.0 / norm.num_batches_tracked.to(torch.float64) if norm.momentum is None else norm.momentum
+                unbiased = var.detach() * (n / max(n - 1.0, 1.0))
+                norm.running_mean += (mean.detach() - norm.running_mean) * factor
+                norm.running_var += (unbiased - norm.running_var) * factor
+        scale = torch.rsqrt(var + norm.eps)
+        if norm.weight is not None:
+            scale = scale * norm.weight
+        shift = -mean * scale
+        if norm.bias is not None:
+            shift = shift + norm.bias
+        return scale, shift
+
+    def forward_fused_train(self, rois, grid_size, features, index, stride, voxel_size, point_cloud_range):
+        """rois (B, n, 7 + ...), detached as the reference's (its targets come from no_grad); the level's features (P, C) and its
+        sparse_conv_ops.site_index -> (B n G^3, sum of C2) under autograd in the features and in every parameter of the module."""
+        assert self.fused_train_supported(grid_size), 'forward_fused_train: a configuration the fused operator refuses; use forward()'
+        if features.is_cuda and torch.cuda.is_current_stream_capturing():
+            # The three operators are captured and replayed bit for bit on their own (tests); a capture of this method with
+            # its backward (torch's training BatchNorm, the autograd thread calling pdm_roi_grid_pool_grad) has ended in a
+            # fault of the process at the end of the capture and is refused until its cause is known (DESIGN.md 7v).
+            raise RuntimeError('forward_fused_train cannot be captured in a graph: capture the operators of sparse_conv_ops '
+                               '(roi_grid_query, roi_grid_pool_train, roi_grid_pool_grad), or run the training step eagerly')
+        features = features.float()
+        out = []
+        for k, g in enumerate(self.groupers):
+            features_in = self.mlps_in[k](features.permute(1, 0).unsqueeze(0)).squeeze(0).permute(1, 0).contiguous()      # (P, C1)
+            groups = sparse_conv_ops.roi_grid_query(rois, grid_size, index, stride, voxel_size, point_cloud_range, g.max_range, g.radius, g.nsample)
+            conv, norm = self.mlps_pos[k][0], self.mlps_pos[k][1]
+            scale_p, shift_p = self._position_norm(conv, norm, groups.moments, groups.rows.shape[0] * groups.rows.shape[1])
+            pooled, _ = sparse_conv_ops.RoIGridPoolFunction.apply(features_in, conv.weight.reshape(conv.out_channels, 3), scale_p, shift_p,
+                                                                  groups.rows, groups.offsets)
+            new_features = self.mlps_out[k](pooled.permute(1, 0).unsqueeze(0))                                            # (1, C2, M)
+            out.append(new_features.squeeze(0).permute(1, 0))
+        return torch.cat(out, dim=1)

@@ -1,6 +1,5 @@
 """Voxel R-CNN's second stage: behaviour, constructor signature, config keys and state_dict keys of the reference's
-pcdet/models/roi_heads/voxelrcnn_head.py, restated.  Eval mode only: the RoI-grid pooling has no gradient yet, and the voxel
-backbone in front of this head refuses training anyway.
+pcdet/models/roi_heads/voxelrcnn_head.py, restated.
 
 Per RoI a G x G x G lattice of grid points; per grid point and per source level of the voxel backbone (ROI_GRID_POOL.
 FEATURES_SOURCE) the voxels of a window around the point's cell, within POOL_RADIUS, the first NSAMPLE of them, pooled by
@@ -12,6 +11,11 @@ row_of_rank, 1 bit a cell instead of the 4 bytes a cell of the reference's dense
 over the level's rows and one launch of pdm_roi_grid_pool writing its columns of the (B n G^3, sum C2) output: no torch.cat,
 no host read, graph-capturable.  A level whose module the fused operator refuses (avg_pool, other widths) and
 use_fused_pool = False take the reference's formulation on VoxelQueryAndGrouping, the checker of the fused operator.
+
+Training (TARGET_CONFIG with the sampler's settings): proposals under NMS_CONFIG.TRAIN, proposal targets, the sampled rois
+pooled under autograd, per level by NeighborVoxelSAModuleMSG.forward_fused_train (csrc/roi_grid_train.hip) where
+it applies and by the composed formulation otherwise, the FC stacks, forward_ret_dict for RoIHeadTemplate.get_loss.  On the
+device only: off it the RoI-grid pooling has no gradient.
 """
 import torch
 import torch.nn as nn
@@ -82,9 +86,34 @@ class VoxelRCNNHead(RoIHeadTemplate):
         key = 'multi_scale_3d_features_post' if batch_dict.get('with_voxel_feature_transform', False) else 'multi_scale_3d_features'
         return batch_dict[key][src_name], int(batch_dict['multi_scale_3d_strides'][src_name])
 
-    @torch.no_grad()
     def roi_grid_pool(self, batch_dict):
-        """batch_size, rois (B, n, 7 + C), multi_scale_3d_features / multi_scale_3d_strides -> (B n, G^3, sum of the levels' C2)"""
+        """batch_size, rois (B, n, 7 + C), multi_scale_3d_features / multi_scale_3d_strides -> (B n, G^3, sum of the levels' C2);
+        in training mode under autograd in the levels' features and the pool layers' parameters (the rois detached)"""
+        if self.training:
+            return self._roi_grid_pool_train(batch_dict)
+        with torch.no_grad():
+            return self._roi_grid_pool_eval(batch_dict)
+
+    def _roi_grid_pool_train(self, batch_dict):
+        rois = batch_dict['rois'].detach().float().contiguous()
+        B, n = rois.shape[0], rois.shape[1]
+        G = int(_get(self.pool_cfg, 'GRID_SIZE'))
+        composed_inputs = None
+        pooled = []
+        for k, src_name in enumerate(_get(self.pool_cfg, 'FEATURES_SOURCE')):
+            layer = self.roi_grid_pool_layers[k]
+            sp, stride = self._level(batch_dict, src_name)
+            if self.use_fused_pool and rois.is_cuda and layer.fused_train_supported(G):
+                index = sparse_conv_ops.site_index(sp.indices, B, sp.spatial_shape)
+                pooled.append(layer.forward_fused_train(rois, G, sp.features, index, stride, self.voxel_size, self.point_cloud_range))
+                continue
+            if composed_inputs is None:
+                with torch.no_grad():
+                    composed_inputs = self._grid_points_and_cells(rois, G)
+            pooled.append(self._pool_level_composed(layer, sp, stride, B, *composed_inputs))
+        return torch.cat(pooled, dim=1).view(B * n, G ** 3, self.num_pooled_channels)
+
+    def _roi_grid_pool_eval(self, batch_dict):
         rois = batch_dict['rois'].float().contiguous()
         B, n = rois.shape[0], rois.shape[1]
         G = int(_get(self.pool_cfg, 'GRID_SIZE'))
@@ -150,16 +179,30 @@ class VoxelRCNNHead(RoIHeadTemplate):
     # ------------------------------------------------------------------ forward
 
     def forward(self, batch_dict):
-        """Eval mode (ref :217-262): proposals (unless rois are given) -> pooled grid features -> rcnn_cls (R, num_class),
-        rcnn_reg (R, code_size) -> batch_cls_preds / batch_box_preds with cls_preds_normalized = False."""
+        """(ref :217-262) proposals (unless rois are given) -> pooled grid features -> rcnn_cls (R, num_class), rcnn_reg
+        (R, code_size).  Eval: batch_cls_preds / batch_box_preds with cls_preds_normalized = False.  Training: the proposals go
+        through assign_targets first, the sampled rois are pooled, and forward_ret_dict holds the targets with rcnn_cls and
+        rcnn_reg for get_loss."""
         if self.training:
-            raise NotImplementedError('VoxelRCNNHead training: the RoI-grid pooling has no gradient yet (and the voxel backbone in '
-                                      'front of this head runs in eval mode only)')
-        self.proposal_layer(batch_dict, nms_config=_get(self.model_cfg, 'NMS_CONFIG')['TEST'])
+            levels = batch_dict.get('multi_scale_3d_features', None) or {}
+            tensors = list(batch_dict.values()) + [getattr(sp, 'features', None) for sp in levels.values()]
+            if not any(torch.is_tensor(v) and v.is_cuda for v in tensors):
+                raise NotImplementedError('VoxelRCNNHead training on CPU tensors: off the device the RoI-grid pooling has no gradient yet')
+            self._require_training_half(type(self).__name__)
+        self.proposal_layer(batch_dict, nms_config=_get(self.model_cfg, 'NMS_CONFIG')['TRAIN' if self.training else 'TEST'])
+        if self.training:
+            targets_dict = self.assign_targets(batch_dict)
+            batch_dict['rois'] = targets_dict['rois']
+            batch_dict['roi_labels'] = targets_dict['roi_labels']
         pooled = self.roi_grid_pool(batch_dict)
         shared = self.shared_fc_layer(pooled.view(pooled.size(0), -1))
         rcnn_cls = self.cls_pred_layer(self.cls_fc_layers(shared))
         rcnn_reg = self.reg_pred_layer(self.reg_fc_layers(shared))
+        if self.training:
+            targets_dict['rcnn_cls'] = rcnn_cls
+            targets_dict['rcnn_reg'] = rcnn_reg
+            self.forward_ret_dict = targets_dict
+            return batch_dict
         cls, boxes = self.generate_predicted_boxes(batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls,
                                                    box_preds=rcnn_reg)
         batch_dict.update(rcnn_cls=rcnn_cls, rcnn_reg=rcnn_reg, batch_cls_preds=cls, batch_box_preds=boxes, cls_preds_normalized=False)

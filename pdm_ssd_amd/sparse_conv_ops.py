@@ -3,13 +3,14 @@ means (voxel_assign), the rulebook of a sparse 3-D convolution (rulebook), the c
 (sparse_conv) with its gradients (rulebook_transpose, pack_weight_transposed, sparse_conv_dgrad, sparse_conv_wgrad of
 csrc/sparse_conv_wgrad.hip, and the autograd node SparseConvFunction over them), the dense canvas of a sparse tensor (to_dense,
 differentiable in the features), the site index of a level as an object of its own (site_index) and Voxel R-CNN's RoI-grid
-pooling over it (roi_grid_pool, csrc/roi_grid_pool.hip).  An occupancy bitmap with scanned popcounts numbers
+pooling over it (roi_grid_pool, csrc/roi_grid_pool.hip) with its training form (roi_grid_query, RoIGridPoolFunction over
+roi_grid_pool_train and roi_grid_pool_grad, csrc/roi_grid_train.hip).  An occupancy bitmap with scanned popcounts numbers
 voxels and output sites in ascending key order: no host loop, no sort, no hash, no float atomics, so every result is a
-function of the input alone and two runs give the same bits, the gradients' included.  voxel_assign, the site index and the
-RoI-grid pooling have no gradient.
+function of the input alone and two runs give the same bits, the gradients' included.  voxel_assign and the site index
+have no gradient.
 
 Host reads: voxel_assign() copies the two ints {N', P} to the host, and a STRIDED rulebook() copies the one int P_out;
-a submanifold rulebook, sparse_conv(), to_dense(), site_index(), roi_grid_pool() and the gradients read nothing.  HOST_READS counts the copies.
+a submanifold rulebook, sparse_conv(), to_dense(), site_index(), roi_grid_pool(), roi_grid_query() and the gradients read nothing.  HOST_READS counts the copies.
 
 The torch formulations these stand for (torch.unique + scatter_mean, and per offset index_select -> mm -> index_add_) are
 what the tests and tools/sparse_conv_rate.py compare with.
@@ -155,6 +156,97 @@ def roi_grid_pool(rois, grid_size, index, stride, voxel_size, point_cloud_range,
                  int(nsample), int(c_out), wout_pack.data_ptr(), small[3].data_ptr(), small[4].data_ptr(), out.data_ptr(),
                  out.stride(0) if M else max(out_offset + c_out, 1), int(out_offset))
     return out
+
+
+RoIGroups = namedtuple('RoIGroups', ['rows', 'offsets', 'moments', 'num_rows'])
+
+
+@torch.no_grad()
+def roi_grid_query(rois, grid_size, index, stride, voxel_size, point_cloud_range, query_range, radius, nsample):
+    """The query of the RoI-grid pooling's training form (pdm_roi_grid_query): rois (B, n, 7 + ...) fp32, index =
+    site_index() of the level's rows -> RoIGroups: rows (M, nsample) int32, the group of every grid point in window order with -1
+    in unused slots; offsets (M, nsample, 3) fp32, voxel centre - grid point, the bits roi_grid_pool forms; moments (9) float64,
+    the sums [x, y, z, xx, xy, xz, yy, yz, zz] of the offsets over the M nsample slots of the reference's padded tensor (slot 0
+    repeated into the unused slots, zeros for an empty group).  M = B n G^3 <= 2^22.  No host read; two runs give the same bits."""
+    assert rois.is_cuda and rois.dtype == torch.float32 and rois.dim() == 3 and rois.shape[2] >= 7, 'rois: fp32 (B, n, 7 + C) on the GPU'
+    rois = rois.detach()
+    rois = rois if rois.is_contiguous() else rois.contiguous()
+    B, n, G, S, dev = rois.shape[0], rois.shape[1], int(grid_size), int(nsample), rois.device
+    assert B == index.batch_size, (B, index.batch_size)
+    M = B * n * G ** 3
+    rz, ry, rx = (int(v) for v in query_range)
+    D, H, W = index.spatial_shape
+    nbytes = _native.lib().pdm_roi_grid_query_workspace_bytes(M)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    grp_row = torch.empty((M, S), dtype=torch.int32, device=dev)
+    grp_off = torch.empty((M, S, 3), dtype=torch.float32, device=dev)
+    moments = torch.empty(9, dtype=torch.float64, device=dev)
+    _native.call("pdm_roi_grid_query", _native.stream(dev), B, n, rois.shape[2], rois.data_ptr(), G, D, H, W, int(stride),
+                 *(float(v) for v in voxel_size[:3]), *(float(v) for v in point_cloud_range[:3]), index.num_rows, index.workspace.data_ptr(),
+                 index.nbytes, rz, ry, rx, float(radius), S, grp_row.data_ptr(), grp_off.data_ptr(), moments.data_ptr(), ws.data_ptr(), nbytes)
+    return RoIGroups(grp_row, grp_off, moments, index.num_rows)
+
+
+def roi_grid_grad_chunk_points(num_grid_points, c1):
+    """grid points of one partial of roi_grid_pool_grad's parameter sums: a function of these two numbers alone"""
+    return _native.lib().pdm_roi_grid_pool_grad_chunk_points(int(num_grid_points), int(c1))
+
+
+@torch.no_grad()
+def roi_grid_pool_train(features_in, wp, scale_p, shift_p, grp_row, grp_off):
+    """-> pooled (M, C1) fp32 and arg (M, C1) uint8, the winning slot or 0xFF (pdm_roi_grid_pool_train)"""
+    assert features_in.is_cuda and features_in.dtype == torch.float32 and features_in.dim() == 2 and features_in.is_contiguous()
+    assert grp_row.dtype == torch.int32 and grp_row.dim() == 2 and grp_row.is_contiguous() and grp_off.is_contiguous()
+    assert grp_off.dtype == torch.float32 and tuple(grp_off.shape) == (*grp_row.shape, 3), tuple(grp_off.shape)
+    (P, C1), (M, S), dev = features_in.shape, grp_row.shape, features_in.device
+    small = [t.detach().float().contiguous() for t in (wp, scale_p, shift_p)]
+    assert tuple(small[0].shape) == (C1, 3) and small[1].numel() == C1 and small[2].numel() == C1
+    pooled = torch.empty((M, C1), dtype=torch.float32, device=dev)
+    arg = torch.empty((M, C1), dtype=torch.uint8, device=dev)
+    _native.call("pdm_roi_grid_pool_train", _native.stream(dev), M, S, P, C1, grp_row.data_ptr(), grp_off.data_ptr(), features_in.data_ptr(),
+                 small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr(), pooled.data_ptr(), arg.data_ptr())
+    return pooled, arg
+
+
+@torch.no_grad()
+def roi_grid_pool_grad(gpool, arg, grp_row, grp_off, wp, scale_p, num_rows):
+    """-> dfeatures_in (P, C1), dwp (C1, 3), dscale_p (C1), dshift_p (C1) (pdm_roi_grid_pool_grad): the features' gradient in
+    64-bit fixed point under integer atomics, the parameter sums through partials in a fixed order.  No host read."""
+    assert gpool.is_cuda and gpool.dtype == torch.float32 and gpool.dim() == 2 and tuple(arg.shape) == tuple(gpool.shape) and arg.dtype == torch.uint8
+    gpool, arg = gpool.contiguous(), arg.contiguous()
+    (M, C1), S, P, dev = gpool.shape, grp_row.shape[1], int(num_rows), gpool.device
+    assert tuple(grp_row.shape) == (M, S) and grp_row.is_contiguous() and grp_off.is_contiguous()
+    small = [t.detach().float().contiguous() for t in (wp, scale_p)]
+    nbytes = _native.lib().pdm_roi_grid_pool_grad_workspace_bytes(M, P, C1)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    dfeat, dwp, dscale, dshift = torch.empty((P, C1), **f32), torch.empty((C1, 3), **f32), torch.empty(C1, **f32), torch.empty(C1, **f32)
+    _native.call("pdm_roi_grid_pool_grad", _native.stream(dev), M, S, P, C1, gpool.data_ptr(), arg.data_ptr(), grp_row.data_ptr(), grp_off.data_ptr(),
+                 small[0].data_ptr(), small[1].data_ptr(), dfeat.data_ptr(), dwp.data_ptr(), dscale.data_ptr(), dshift.data_ptr(), ws.data_ptr(),
+                 nbytes)
+    return dfeat, dwp, dscale, dshift
+
+
+class RoIGridPoolFunction(torch.autograd.Function):
+    """pooled (M, C1) = the RoI-grid pooling over kept groups (roi_grid_query), with its gradients in features_in (P, C1), wp
+    (C1, 3), scale_p and shift_p (C1): forward pdm_roi_grid_pool_train, backward pdm_roi_grid_pool_grad.  Returns (pooled,
+    arg); arg and the groups take no gradient."""
+
+    @staticmethod
+    def forward(ctx, features_in, wp, scale_p, shift_p, grp_row, grp_off):
+        features_in = features_in.detach().float().contiguous()
+        wp, scale_p, shift_p = (t.detach().float().contiguous() for t in (wp, scale_p, shift_p))
+        pooled, arg = roi_grid_pool_train(features_in, wp.reshape(-1, 3), scale_p, shift_p, grp_row, grp_off)
+        ctx.save_for_backward(arg, grp_row, grp_off, wp, scale_p)
+        ctx.num_rows = features_in.shape[0]
+        ctx.mark_non_differentiable(arg)
+        return pooled, arg
+
+    @staticmethod
+    def backward(ctx, gpool, _garg=None):
+        arg, grp_row, grp_off, wp, scale_p = ctx.saved_tensors
+        dfeat, dwp, dscale, dshift = roi_grid_pool_grad(gpool.float(), arg, grp_row, grp_off, wp.reshape(-1, 3), scale_p, ctx.num_rows)
+        return dfeat, dwp.reshape(wp.shape), dscale, dshift, None, None
 
 
 def pack_weight(weight):

@@ -1206,6 +1206,30 @@ int pdm_roi_grid_pool_grad(void *stream, long long M, int nsample, int P, int C1
                            const int *grp_row, const float *grp_off, const float *wp, const float *scale_p, float *dfeatures_in,
                            float *dwp, float *dscale_p, float *dshift_p, void *workspace, size_t workspace_bytes);
 
+/* PV-RCNN's two operators (csrc/pv_rcnn.hip).  Both check every argument before any launch, use no atomics (two
+ * runs give the same bits), read nothing on the host and can be captured in a graph.
+ * pdm_bev_interpolate: keypoints (K, 4) fp32 rows (b, x, y, z) of all samples; spatial_features (B, C, H, W) fp32 contiguous, the
+ *   map as HeightCompression leaves it.  x = ((kx - x0) / vx) / bev_stride and y likewise (IEEE divisions), corners
+ *   clamp(floor, 0, n - 1) and clamp(floor + 1, 0, n - 1), weights from the CLAMPED corners,
+ *   out[k][col0 + c] = Ia wa + Ib wb + Ic wc + Id wd summed left to right in fp32 without contraction (Ia = im[y0][x0],
+ *   Ib = im[y1][x0], Ic = im[y0][x1], Id = im[y1][x1]): the bits of the reference's bilinear_interpolate_torch.  Rows of ld floats,
+ *   columns [col0, col0 + C); a row whose b is outside [0, B) gets zeros.  One launch.
+ * pdm_roi_keypoint_query: rois (B, n, roi_stride >= 7); grid point g of RoI r as pdm_roi_grid_pool forms it (the same code).
+ *   xyz (K, 3): the keypoints of all samples stacked, xyz_batch_cnt (B) int32 on the device; max_per_sample: the caller's bound
+ *   on those counts (it sizes the LDS the workgroup stages a sample in; a sample above it is cut to its first max_per_sample
+ *   keypoints), at most pdm_roi_keypoint_query_cap() = 4096 (PDM_E_TOOLARGE beyond).  Per scale s < nscales (1 or 2), with
+ *   pdm_stack_ball_query's rules (pinned squared distance, strict <, first nsample_s by index, padding with the first hit):
+ *   idx_s (B n G^3, nsample_s) int32 GLOBAL rows of xyz, empty_s (B n G^3) bytes, 1 for a ball without a hit, whose slots all
+ *   hold row 0 of the sample.  grid_points (B n G^3, 3).  G <= 8, nsample <= 64, B <= 1024, K >= 1 (PDM_E_BADARG
+ *   otherwise: an empty ball needs a row to point at).  One launch for all scales. */
+/* align: any (4-byte accesses). */
+int pdm_bev_interpolate(void *stream, int K, const float *keypoints, int B, int C, int H, int W, const float *spatial_features,
+                        float x0, float y0, float vx, float vy, int bev_stride, float *out, int ld, int col0);
+int pdm_roi_keypoint_query_cap(void);
+int pdm_roi_keypoint_query(void *stream, int B, int n, int roi_stride, const float *rois, int G, int K, const float *xyz,
+                           const int *xyz_batch_cnt, int max_per_sample, int nscales, float radius0, int nsample0, float radius1,
+                           int nsample1, float *grid_points, int *idx0, unsigned char *empty0, int *idx1, unsigned char *empty1);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -1,4 +1,5 @@
 """3-D backbones of the voxel family, registered by NAME as the reference's pcdet/models/backbones_3d/__init__.py does."""
+from . import pfe  # noqa: F401
 from .spconv_backbone import SparseBasicBlock, VoxelBackBone8x, VoxelResBackBone8x, post_act_block
 
 __all__ = {

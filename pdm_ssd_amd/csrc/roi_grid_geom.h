@@ -41,22 +41,29 @@ __device__ __forceinline__ RgpWalk rgp_walk_of(const A &a) {
     return k;
 }
 
-// the tile's 16 grid points, one per lane (lanes 16 and up repeat them): the trigonometry runs once a point, not once a lane
-template <class A>
-__device__ __forceinline__ void rgp_tile_points(const A &a, const RgpWalk &k, long long tile, int lane, float &pgx, float &pgy, float &pgz,
-                                                int &pcx, int &pcy, int &pcz, int &pb) {
-    const int G = k.G, G3 = k.G3;
-    const int m = (int)min(tile * RGP_TILE + (lane & 15), a.M - 1);
-    const int r = m / G3, gi = m - r * G3, ix = gi / (G * G), iy = (gi / G) % G, iz = gi % G;      // nonzero()'s order
-    const float *roi = a.rois + (size_t)r * a.roi_stride;
+// grid point gi (0 <= gi < G^3, the lattice in nonzero()'s order: x index slowest, z fastest) of the RoI row `roi`
+// (x, y, z, dx, dy, dz, heading, ...): (i + 0.5) / G size - size / 2 per axis, turned by the heading, plus the centre.  The one
+// definition of the fp32 operation order, for the voxel pooling (below) and PV-RCNN's keypoint query (pv_rcnn.hip) alike.
+__device__ __forceinline__ void rgp_grid_point(const float *roi, int G, int gi, float &gx, float &gy, float &gz) {
+    const int ix = gi / (G * G), iy = (gi / G) % G, iz = gi % G;
     const float dxs = roi[3], dys = roi[4], dzs = roi[5], head = roi[6];
     const float lx = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)ix, 0.5f), (float)G), dxs), __fdiv_rn(dxs, 2.0f));
     const float ly = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iy, 0.5f), (float)G), dys), __fdiv_rn(dys, 2.0f));
     const float lz = __fsub_rn(__fmul_rn(__fdiv_rn(__fadd_rn((float)iz, 0.5f), (float)G), dzs), __fdiv_rn(dzs, 2.0f));
     const float cs = cosf(head), sn = sinf(head);
-    pgx = __fadd_rn(__fsub_rn(__fmul_rn(lx, cs), __fmul_rn(ly, sn)), roi[0]);
-    pgy = __fadd_rn(__fadd_rn(__fmul_rn(lx, sn), __fmul_rn(ly, cs)), roi[1]);
-    pgz = __fadd_rn(lz, roi[2]);
+    gx = __fadd_rn(__fsub_rn(__fmul_rn(lx, cs), __fmul_rn(ly, sn)), roi[0]);
+    gy = __fadd_rn(__fadd_rn(__fmul_rn(lx, sn), __fmul_rn(ly, cs)), roi[1]);
+    gz = __fadd_rn(lz, roi[2]);
+}
+
+// the tile's 16 grid points, one per lane (lanes 16 and up repeat them): the trigonometry runs once a point, not once a lane
+template <class A>
+__device__ __forceinline__ void rgp_tile_points(const A &a, const RgpWalk &k, long long tile, int lane, float &pgx, float &pgy, float &pgz,
+                                                int &pcx, int &pcy, int &pcz, int &pb) {
+    const int G3 = k.G3;
+    const int m = (int)min(tile * RGP_TILE + (lane & 15), a.M - 1);
+    const int r = m / G3, gi = m - r * G3;
+    rgp_grid_point(a.rois + (size_t)r * a.roi_stride, k.G, gi, pgx, pgy, pgz);
     pb = r / a.n;
     pcx = floor_div(rgp_cell0(pgx, a.r0[0], a.vox[0]), a.stride);
     pcy = floor_div(rgp_cell0(pgy, a.r0[1], a.vox[1]), a.stride);

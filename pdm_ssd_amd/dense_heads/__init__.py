@@ -4,11 +4,13 @@ from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
 from .pdm_heatmap_head import PDMHeatmapHead
 from .point_head_box import PointHeadBox
+from .point_head_simple import PointHeadSimple
 from .point_head_template import PointHeadTemplate
 
 __all__ = {
     'PointHeadTemplate': PointHeadTemplate,
     'PointHeadBox': PointHeadBox,
+    'PointHeadSimple': PointHeadSimple,
     'PDMHeatmapHead': PDMHeatmapHead,
     'CenterHead': CenterHead,
     'AnchorHeadTemplate': AnchorHeadTemplate,

@@ -200,6 +200,35 @@ VOXEL_RCNN_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
     'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
     'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0, 'code_weights': [1.0] * 7}}
 
+# PV-RCNN: SECOND_CFG's front as it is, plus the voxel set abstraction (PFE), the keypoint segmentation head and PVRCNNHead.  The
+# snapshot this repository was modelled on holds no YAML for this detector, so the PFE, POINT_HEAD and ROI_HEAD values are
+# BUILD-DEFINED: they restate the upstream project's published KITTI setting for PV-RCNN as far as it is remembered here (2048
+# keypoints by FPS of the raw points, 128 fused features; two-scale set abstraction over the raw points and the four levels of
+# the backbone; a 6 x 6 x 6 RoI grid over the keypoints at radii 0.8 / 1.6 m; FC stacks of 256, dropout 0.3, 100 test-time
+# proposals at NMS 0.7) and were not checked against that file.  Eval only: TARGET_CONFIG holds the box coder alone.
+PV_RCNN_CFG = copy.deepcopy(SECOND_CFG)
+PV_RCNN_CFG['NAME'] = 'PVRCNN'
+PV_RCNN_CFG['PFE'] = {
+    'NAME': 'VoxelSetAbstraction', 'POINT_SOURCE': 'raw_points', 'NUM_KEYPOINTS': 2048, 'NUM_OUTPUT_FEATURES': 128, 'SAMPLE_METHOD': 'FPS',
+    'FEATURES_SOURCE': ['bev', 'x_conv1', 'x_conv2', 'x_conv3', 'x_conv4', 'raw_points'],
+    'SA_LAYER': {'raw_points': {'MLPS': [[16, 16], [16, 16]], 'POOL_RADIUS': [0.4, 0.8], 'NSAMPLE': [16, 16]},
+                 'x_conv1': {'DOWNSAMPLE_FACTOR': 1, 'MLPS': [[16, 16], [16, 16]], 'POOL_RADIUS': [0.4, 0.8], 'NSAMPLE': [16, 16]},
+                 'x_conv2': {'DOWNSAMPLE_FACTOR': 2, 'MLPS': [[32, 32], [32, 32]], 'POOL_RADIUS': [0.8, 1.2], 'NSAMPLE': [16, 32]},
+                 'x_conv3': {'DOWNSAMPLE_FACTOR': 4, 'MLPS': [[64, 64], [64, 64]], 'POOL_RADIUS': [1.2, 2.4], 'NSAMPLE': [16, 32]},
+                 'x_conv4': {'DOWNSAMPLE_FACTOR': 8, 'MLPS': [[64, 64], [64, 64]], 'POOL_RADIUS': [2.4, 4.8], 'NSAMPLE': [16, 32]}}}
+PV_RCNN_CFG['POINT_HEAD'] = {'NAME': 'PointHeadSimple', 'CLS_FC': [256, 256], 'CLASS_AGNOSTIC': True,
+                             'USE_POINT_FEATURES_BEFORE_FUSION': True}
+PV_RCNN_CFG['ROI_HEAD'] = {
+    'NAME': 'PVRCNNHead', 'CLASS_AGNOSTIC': True,
+    'SHARED_FC': [256, 256], 'CLS_FC': [256, 256], 'REG_FC': [256, 256], 'DP_RATIO': 0.3,
+    'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                             'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                   'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 1024,
+                            'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+    'ROI_GRID_POOL': {'GRID_SIZE': 6, 'MLPS': [[64, 64], [64, 64]], 'POOL_RADIUS': [0.8, 1.6], 'NSAMPLE': [16, 16],
+                      'POOL_METHOD': 'max_pool'},
+    'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -284,4 +313,13 @@ def build_voxel_rcnn(model_cfg=None, num_point_features=4, dataset=None):
     voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and, from the training dict, takes training steps."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(VOXEL_RCNN_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_pv_rcnn(model_cfg=None, num_point_features=4, dataset=None):
+    """PVRCNN from PV_RCNN_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> VoxelSetAbstraction ->
+    BaseBEVBackbone -> AnchorHeadSingle -> PointHeadSimple -> PVRCNNHead (the reference's module order), on voxel_dataset() unless
+    another dataset namespace is given.  Runs in eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(PV_RCNN_CFG if model_cfg is None else model_cfg))   # (the SA constructors edit MLPS)
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

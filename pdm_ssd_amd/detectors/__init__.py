@@ -7,6 +7,7 @@ from .centerpoint import CenterPoint
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
+from .pv_rcnn import PVRCNN
 from .second_net import SECONDNet
 from .voxel_rcnn import VoxelRCNN
 
@@ -18,6 +19,7 @@ __all__ = {
     'PointPillar': PointPillar,
     'SECONDNet': SECONDNet,
     'VoxelRCNN': VoxelRCNN,
+    'PVRCNN': PVRCNN,
 }
 
 

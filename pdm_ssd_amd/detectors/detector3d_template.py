@@ -7,14 +7,15 @@ checkpoint loading).  The reference's template cannot be imported on this platfo
 pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
 (DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and the voxel family (DynamicMeanVFE ->
 VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
-outside the registries (MeanVFE, PillarVFE, ...) and the pfe slot are refused.  The roi_head slot builds the RoI heads of
-roi_heads/ (PointRCNN's second stage; Voxel R-CNN's, in eval mode).
+outside the registries (MeanVFE, PillarVFE, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction, the roi_head slot
+the RoI heads of roi_heads/ (PointRCNN's second stage, Voxel R-CNN's, PV-RCNN's in eval mode).
 """
 import torch
 import torch.nn as nn
 
 from .. import backbones_2d, backbones_3d, dense_heads, roi_heads, vfe
 from ..backbones_2d import map_to_bev
+from ..backbones_3d import pfe
 from ..iou3d_nms import iou3d_nms_utils
 from ..pdm_neck import PDMNeck
 from ..pointnet2_backbone import PointNet2MSG
@@ -64,10 +65,6 @@ class Detector3DTemplate(nn.Module):
             self.add_module(module_name, module)
         return model_info_dict['module_list']
 
-    def _unsupported(self, key, model_info_dict):
-        assert _get(self.model_cfg, key, None) is None, f'{key} needs spconv / voxel modules: not part of the point path'
-        return None, model_info_dict
-
     def _registered(self, key, registry):
         """the slot's config, or None; a NAME outside the registry is one of the reference's spconv / voxel modules"""
         cfg = _get(self.model_cfg, key, None)
@@ -89,7 +86,18 @@ class Detector3DTemplate(nn.Module):
         return module, model_info_dict
 
     def build_pfe(self, model_info_dict):
-        return self._unsupported('PFE', model_info_dict)
+        """ref :109-125: the point feature encoder (PV-RCNN's VoxelSetAbstraction); its widths become num_point_features and
+        num_point_features_before_fusion"""
+        cfg = self._registered('PFE', pfe.__all__)
+        if cfg is None:
+            return None, model_info_dict
+        module = pfe.__all__[_get(cfg, 'NAME')](
+            model_cfg=cfg, voxel_size=model_info_dict['voxel_size'], point_cloud_range=model_info_dict['point_cloud_range'],
+            num_bev_features=model_info_dict['num_bev_features'], num_rawpoint_features=model_info_dict['num_rawpoint_features'])
+        model_info_dict['module_list'].append(module)
+        model_info_dict['num_point_features'] = module.num_point_features
+        model_info_dict['num_point_features_before_fusion'] = module.num_point_features_before_fusion
+        return module, model_info_dict
 
     def build_backbone_2d(self, model_info_dict):
         """ref :106-117: reads num_bev_features of the map_to_bev module and replaces it with its own"""
@@ -156,8 +164,9 @@ class Detector3DTemplate(nn.Module):
         cfg = _get(self.model_cfg, 'POINT_HEAD', None)
         if cfg is None:
             return None, model_info_dict
+        before_fusion = _get(cfg, 'USE_POINT_FEATURES_BEFORE_FUSION', False) and 'num_point_features_before_fusion' in model_info_dict
         module = dense_heads.__all__[_get(cfg, 'NAME')](
-            model_cfg=cfg, input_channels=model_info_dict['num_point_features'],
+            model_cfg=cfg, input_channels=model_info_dict['num_point_features_before_fusion' if before_fusion else 'num_point_features'],
             num_class=self.num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1,
             predict_boxes_when_training=_get(self.model_cfg, 'ROI_HEAD', False))
         model_info_dict['module_list'].append(module)

@@ -46,10 +46,11 @@ def _conv_bn_relu(spec):
     return TrainSequential(*layers)
 
 
-def _row_starts(cnt_src, cnt_rows):
-    """start offset (in the stacked source) of the sample each stacked row belongs to, int32 (rows,)."""
+def _row_starts(cnt_src, cnt_rows, total=None):
+    """start offset (in the stacked source) of the sample each stacked row belongs to, int32 (rows,); `total`, the number of
+    rows when the caller knows it, spares repeat_interleave its read of the counts on the host."""
     starts = torch.cumsum(cnt_src.long(), 0) - cnt_src.long()
-    return torch.repeat_interleave(starts, cnt_rows.long()).int()
+    return torch.repeat_interleave(starts, cnt_rows.long(), output_size=total).int()
 
 
 class StackSAModuleMSG(nn.Module):
@@ -88,7 +89,11 @@ class StackSAModuleMSG(nn.Module):
                 and all(g.nsample % 16 == 0 for g in self.groupers))
 
     @torch.no_grad()
-    def _forward_fused(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features):
+    def _forward_fused(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features, queries=None, dest=None):
+        """queries: per scale a precomputed (GLOBAL neighbour rows (M, nsample) int32, empty-ball mask (M,)) instead of the ball
+        query here (PV-RCNN's RoI-grid pooling makes all of them in one launch); dest: (rows (M, ld) fp32, column offset), the
+        scales' columns are written there instead of into a fresh (M, sum of widths) tensor.  Returns None, before anything is
+        written, when the fused kernels do not serve this module."""
         cin = 0 if features is None else features.shape[1]
         perm = list(range(3, 3 + cin)) + [0, 1, 2]      # reference order [xyz, features] -> kernel order [features, xyz]
         packs = [fused.cached_pack(self, i, mlp, xyz.device, perm) for i, mlp in enumerate(self.mlps)]
@@ -97,8 +102,15 @@ class StackSAModuleMSG(nn.Module):
         xyz1, new1 = xyz.contiguous()[None], new_xyz.contiguous()[None]
         feat1 = None if features is None else features.contiguous()[None]        # (1, N, C): already point-major
         M = new_xyz.shape[0]
-        out = torch.empty((1, M, sum(pk.cout for pk in packs)), dtype=torch.float32, device=xyz.device)
-        starts = _row_starts(xyz_batch_cnt, new_xyz_batch_cnt)
+        if dest is None:
+            out, coff = torch.empty((1, M, sum(pk.cout for pk in packs)), dtype=torch.float32, device=xyz.device), 0
+        else:
+            rows, coff = dest
+            assert rows.dim() == 2 and rows.shape[0] == M and rows.is_contiguous() and rows.dtype == torch.float32 \
+                and coff + sum(pk.cout for pk in packs) <= rows.shape[1], "dest: contiguous fp32 (M, ld) rows with room for the columns"
+            out = rows[None]
+        # (a caller that hands over `dest` vouches that new_xyz_batch_cnt sums to M: repeat_interleave need not read the counts)
+        starts = _row_starts(xyz_batch_cnt, new_xyz_batch_cnt, M if dest is not None else None) if queries is None else None
         pre = None
         if cin >= PRE_MIN_CIN and getattr(self, 'use_pre', True):
             pre = fused.cached_pre_packs(self, 'pre', list(self.mlps), xyz.device, range(3, 3 + cin), range(3))
@@ -106,11 +118,14 @@ class StackSAModuleMSG(nn.Module):
             prepack, packs = pre
             z = torch.empty((1, xyz.shape[0], prepack.width), dtype=torch.float32, device=xyz.device)
             fused.rows_forward(prepack, feat1, z, relu_last=False)
-        coff = 0
         for i, (grouper, pk, mlp) in enumerate(zip(self.groupers, packs, self.mlps)):
-            idx, empty = pointnet2_utils.ball_query(grouper.radius, grouper.nsample, xyz, xyz_batch_cnt, new_xyz,
-                                                    new_xyz_batch_cnt)
-            gidx = (idx + starts[:, None])[None].contiguous()                     # global neighbour indices
+            if queries is None:
+                idx, empty = pointnet2_utils.ball_query(grouper.radius, grouper.nsample, xyz, xyz_batch_cnt, new_xyz,
+                                                        new_xyz_batch_cnt)
+                gidx = (idx + starts[:, None])[None].contiguous()                 # global neighbour indices
+            else:
+                gidx, empty = queries[i][0][None], queries[i][1]
+                assert gidx.shape == (1, M, grouper.nsample) and gidx.dtype == torch.int32 and gidx.is_contiguous()
             if pre is not None:
                 fused.sa_scale_forward_pre(pk, xyz1, new1, z, prepack.offsets[i], gidx, out, coff)
             else:
@@ -121,7 +136,7 @@ class StackSAModuleMSG(nn.Module):
             out[0, :, coff:coff + pk.cout] = torch.where(empty[:, None], mlp(zero_in).view(1, -1),
                                                          out[0, :, coff:coff + pk.cout])
             coff += pk.cout
-        return out[0]
+        return out[0] if dest is None else dest[0]
 
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None, empty_voxel_set_zeros=True):
         """xyz (N1+N2+...,3), new_xyz (M1+M2+...,3), features (N1+N2+...,C) -> (new_xyz, (M1+M2+..., sum_k mlps[k][-1]))."""

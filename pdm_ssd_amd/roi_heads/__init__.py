@@ -1,5 +1,6 @@
 """RoI (second-stage) heads, registered by NAME as /root/reference/pcdet/models/roi_heads/__init__.py does."""
 from .pointrcnn_head import PointRCNNHead
+from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
 from .voxelrcnn_head import VoxelRCNNHead
 
@@ -7,4 +8,5 @@ __all__ = {
     'RoIHeadTemplate': RoIHeadTemplate,
     'PointRCNNHead': PointRCNNHead,
     'VoxelRCNNHead': VoxelRCNNHead,
+    'PVRCNNHead': PVRCNNHead,
 }

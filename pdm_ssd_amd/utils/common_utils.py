@@ -21,10 +21,12 @@ def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_ra
     (float(c) + 0.5) * (float(voxel_size) * downsample_times) + range minimum, three fp32 roundings (the reference's function
     of this name; the RoI-grid pooling kernel forms the same bits from the cell it visits)."""
     assert voxel_coords.shape[1] == 3
-    voxel_centers = voxel_coords[:, [2, 1, 0]].float()
-    voxel_size = torch.tensor(voxel_size, device=voxel_centers.device).float() * downsample_times
-    pc_range = torch.tensor(point_cloud_range[0:3], device=voxel_centers.device).float()
-    return (voxel_centers + 0.5) * voxel_size + pc_range
+    # the constants stay python numbers holding fp32 values (the product rounded in fp32 as the tensor form rounds it): no index
+    # or constant tensor is uploaded, so nothing here makes the host wait for the stream
+    size = [float(np.float32(v) * np.float32(downsample_times)) for v in voxel_size]
+    low = [float(np.float32(v)) for v in point_cloud_range[0:3]]
+    cols = [(voxel_coords[:, 2 - k].float() + 0.5) * size[k] + low[k] for k in range(3)]
+    return torch.stack(cols, dim=1)
 
 
 def generate_voxel2pinds(sparse_tensor):

@@ -641,6 +641,39 @@ int pdm_roiaware_pool3d_forward(void *stream, int K, int P, int C, int max_pts, 
 int pdm_roiaware_pool3d_backward(void *stream, int K, int P, int C, int max_pts, int out_x, int out_y, int out_z, const float *rois,
                                  const float *pts, const int *pts_idx_of_voxels, const int *argmax, const float *grad_out,
                                  int pool_method, float *grad_in);
+/* Part-A2's RoI-aware pooling for the whole batch, straight to sparse rows (csrc/roiaware_sparse.hip): what
+ * pdm_roiaware_pool3d_forward 'avg' on part and 'max' on rpn per sample, `cat`, `sum(-1) != 0`, `nonzero` and a gather compute,
+ * bit for bit, without the dense (B N, S^3, 4 + C) tensor.  rois (B, N, 7); pts (P, 3) batch-major with counts (B) int32 rows per
+ * sample; part (P, 4); rpn (P, C).  Two calls around the caller's ONE host read:
+ *   _index  count -> scan -> fill into the workspace; record (2) int32 = {Q, overflow}.  Q = active cells: those whose fp32 sum,
+ *           in ascending channel order, of the four averaged part channels is non-zero.  overflow = 1: a box's point lists did
+ *           not fit list_capacity ints (its rows are missing: refuse the result).  The lists hold a cell's first max_pts - 1
+ *           points in ascending index, as the composed kernel's do.
+ *   _emit   with that Q and the same workspace: coords (Q, 4) int32 rows (roi, x, y, z) ascending in ((roi ox + x) oy + y) oz + z,
+ *           out_part (Q, 4) the average, out_rpn (Q, C) the maximum (0 where nothing wins).  Q == 0 launches nothing.
+ * At most 4096 cells a box, B <= 1024, B N min(P, cells (max_pts - 1)) < 2^31.  No float atomics: two runs give the same bits. */
+size_t pdm_roiaware_pool_sparse_workspace_bytes(int B, int N, int out_x, int out_y, int out_z, long long list_capacity);
+int pdm_roiaware_pool_sparse_index(void *stream, int B, int N, int P, int max_pts, int out_x, int out_y, int out_z, const float *rois,
+                                   const float *pts, const int *counts, const float *part, long long list_capacity, int *record,
+                                   void *workspace, size_t workspace_bytes);
+int pdm_roiaware_pool_sparse_emit(void *stream, int B, int N, int P, int C, int out_x, int out_y, int out_z, const float *part,
+                                  const float *rpn, long long list_capacity, int Q, const void *workspace, size_t workspace_bytes,
+                                  int *coords, float *out_part, float *out_rpn);
+/* dense() of the RoI grids + the first shared FC of Part-A2's head without the dense tensor (csrc/sparse_fc.hip):
+ * coords (Q, 4) int32 rows (box, x, y, z) ascending in ((box sx + x) sy + y) sz + z, one row per (box, cell) at most; xa (Q, C_a)
+ * and xb (Q, C_b) or null with C_b = 0, read where they lie (channel c < C_a from xa, else from xb), C = C_a + C_b; wpack
+ * (pdm_sparse_fc_packed_floats) [cell][kb][nb][lane][j] = W[16 nb + (lane & 15)][(16 kb + 4 (lane >> 4) + j) cells + cell] of the
+ * Conv1d weight (Cout, C cells); scale / shift (Cout) both or neither; relu.
+ * -> out (R, Cout) = epilogue(sum over the rows q of box r of W[:, :, cell(q)] x[q]), epilogue(v) = relu(v scale + shift) as one
+ * multiply and one add; boxes without rows get epilogue(0).  The sum runs over pdm_sparse_fc_chunks(R, cells, Cout) partials of
+ * ascending cells added in ascending order, the boundaries a function of those three sizes alone: no atomics, two runs give the
+ * same bits.  C_a, C_b multiples of 4, C of 16 up to 512, Cout of 16 up to 1024; xa, xb, wpack 16-byte aligned.  No host read. */
+size_t pdm_sparse_fc_packed_floats(int cells, int C, int Cout);
+int pdm_sparse_fc_chunks(int R, int cells, int Cout);
+size_t pdm_sparse_fc_workspace_bytes(long long Q, int R, int cells, int Cout);
+int pdm_sparse_fc(void *stream, long long Q, int R, int sx, int sy, int sz, int Ca, int Cb, int Cout, const int *coords, const float *xa,
+                  const float *xb, const float *wpack, const float *scale, const float *shift, int relu, float *out, void *workspace,
+                  size_t workspace_bytes);
 
 /* ---- input path -------------------------------------------------------
  * sample_points (pcdet/datasets/processor/data_processor.py:182-212) + the batch-index column of collate_batch

@@ -1,8 +1,10 @@
 """3-D backbones of the voxel family, registered by NAME as the reference's pcdet/models/backbones_3d/__init__.py does."""
 from . import pfe  # noqa: F401
 from .spconv_backbone import SparseBasicBlock, VoxelBackBone8x, VoxelResBackBone8x, post_act_block
+from .spconv_unet import UNetV2
 
 __all__ = {
     'VoxelBackBone8x': VoxelBackBone8x,
     'VoxelResBackBone8x': VoxelResBackBone8x,
+    'UNetV2': UNetV2,
 }

@@ -89,6 +89,20 @@ __device__ __forceinline__ int scan_totals(int n, int *__restrict__ v, int *s_wa
     return carry;
 }
 
+// scan_totals as a launch of its own, ONE workgroup of NT threads: v[0 .. n) -> its exclusive prefix in place, v[n] = the total
+// (v holds n + 1 ints).  record, when not null: record[slot] = the total, and record[clear] = 0 when clear >= 0 (the words of
+// a caller's host read).  roiaware_sparse.hip, sparse_fc.hip.
+template <int NT>
+__global__ __launch_bounds__(NT) void scan_totals_kernel(int n, int *v, int *record, int slot, int clear) {
+    __shared__ int s_wave[NT / 64];
+    const int total = scan_totals<NT>(n, v, s_wave);
+    if (threadIdx.x == 0) {
+        v[n] = total;
+        if (record) record[slot] = total;
+        if (record && clear >= 0) record[clear] = 0;
+    }
+}
+
 // Exclusive scan of an LDS histogram in place: counts become running cursors (the fill positions of a counting sort).
 // Every thread of the workgroup (NT threads) calls it after the barrier that completes hist[0..ncells); a thread owns a
 // contiguous chunk of cells (a compile-time ncells gives constant-trip loops, which unroll).  start_out, when not null,

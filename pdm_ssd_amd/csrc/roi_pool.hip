@@ -9,6 +9,7 @@
 // The in-box test and the voxel of a point are box_geometry.h's point_in_box3d_cs / roiaware_voxel, the test the same
 // function points_in_boxes (iou3d_nms.hip) evaluates.  Built with -ffp-contract=off: one rounding per operation.
 #include "box_geometry.h"
+#include "roiaware.h"
 
 namespace pdm {
 
@@ -133,7 +134,6 @@ __global__ __launch_bounds__(RP_NT) void roipoint_pool_kernel(int N, int M, int 
 }
 
 // ---- RoI-aware pooling --------------------------------------------------------------------------------------------------
-constexpr int RA_NT = 256;
 constexpr int RA_LDS_VOX = 8192;   // voxel counters of a box held in LDS (32 KB); larger grids count in the caller's workspace
 
 // roiaware_pool3d_launcher (roiaware_pool3d_kernel.cu:39-233), a workgroup per box: the points are tested 256 at a time in
@@ -162,38 +162,13 @@ __global__ __launch_bounds__(RA_NT) void roiaware_forward_kernel(int P, int C, i
 
     for (int p0 = 0; p0 < P; p0 += RA_NT) {
         const int p = p0 + tid;
-        int v = -1;
-        if (p < P) {
-            const float x = pts[(size_t)p * 3], y = pts[(size_t)p * 3 + 1], z = pts[(size_t)p * 3 + 2];
-            const float sx = x - bx[0], sy = y - bx[1];
-            float lx, ly;
-            if (!(sx * sx + sy * sy > reach2) && point_in_box3d_cs(x, y, z, bx, c, s, &lx, &ly))
-                v = roiaware_voxel(lx, ly, z, bx, ox, oy, oz);
-        }
+        const int v = p < P ? roiaware_cell_of(pts, (size_t)p, bx, c, s, reach2, ox, oy, oz) : -1;
         s_vox[tid] = v;
         if (!__syncthreads_or(v >= 0)) continue;   // no hit in this block of points (nobody reads s_vox)
-        if (wave == 0) {
-            for (int j = 0; j < RA_NT / 64; ++j) {
-                const int vv = s_vox[j * 64 + lane];
-                unsigned long long todo = __ballot(vv >= 0);
-                while (todo) {
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int lv = __shfl(vv, leader, 64);
-                    const unsigned long long same = __ballot(vv == lv);
-                    int base = 0;
-                    if (lane == 0) {   // lane 0 alone reads and advances every counter, whichever lane leads the voxel: all
-                        base = cnt[lv];   // accesses to a counter (LDS or workspace) are one thread's, in program order
-                        cnt[lv] = base + __popcll(same);
-                    }
-                    base = __shfl(base, 0, 64);
-                    if (vv == lv) {
-                        const int slot = base + lanes_below(same, lane);
-                        if (slot < cap) list[(size_t)lv * max_pts + 1 + slot] = p0 + j * 64 + lane;
-                    }
-                    todo &= ~same;
-                }
-            }
-        }
+        if (wave == 0)
+            roiaware_append_block(s_vox, p0, cnt, [&](int lv, int slot, int pt) {
+                if (slot < cap) list[(size_t)lv * max_pts + 1 + slot] = pt;
+            });
         __syncthreads();
     }
     __syncthreads();
@@ -211,20 +186,13 @@ __global__ __launch_bounds__(RA_NT) void roiaware_forward_kernel(int P, int C, i
         const int n = min(cnt[v], cap);
         const int *l = list + (size_t)v * max_pts + 1;
         const size_t o = (size_t)k * VC + e;
-        if (pool_method == 0) {   // strict > from -inf (the reference's float -1e50): first index wins, NaN and -inf never do
-            float best = -INFINITY;
-            int arg = -1;
-            for (int q = 0; q < n; ++q) {
-                const int idx = l[q];
-                const float f = feats[(size_t)idx * C + ch];
-                if (f > best) { best = f; arg = idx; }
-            }
+        if (pool_method == 0) {
+            int arg;
+            const float best = roiaware_list_max(l, n, feats, C, ch, &arg);
             if (arg != -1) pooled[o] = best;
             argmax[o] = arg;
-        } else {
-            float sum = 0.f;
-            for (int q = 0; q < n; ++q) sum += feats[(size_t)l[q] * C + ch];
-            if (n > 0) pooled[o] = sum / (float)n;
+        } else if (n > 0) {
+            pooled[o] = roiaware_list_avg(l, n, feats, C, ch);
         }
     }
 }

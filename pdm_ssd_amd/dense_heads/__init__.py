@@ -5,12 +5,14 @@ from .center_head import CenterHead
 from .pdm_heatmap_head import PDMHeatmapHead
 from .point_head_box import PointHeadBox
 from .point_head_simple import PointHeadSimple
+from .point_intra_part_head import PointIntraPartOffsetHead
 from .point_head_template import PointHeadTemplate
 
 __all__ = {
     'PointHeadTemplate': PointHeadTemplate,
     'PointHeadBox': PointHeadBox,
     'PointHeadSimple': PointHeadSimple,
+    'PointIntraPartOffsetHead': PointIntraPartOffsetHead,
     'PDMHeatmapHead': PDMHeatmapHead,
     'CenterHead': CenterHead,
     'AnchorHeadTemplate': AnchorHeadTemplate,

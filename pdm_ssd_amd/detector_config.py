@@ -229,6 +229,30 @@ PV_RCNN_CFG['ROI_HEAD'] = {
                       'POOL_METHOD': 'max_pool'},
     'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
 
+# Part-A2 (the anchor-based variant): SECOND_CFG's 2-D half on the sparse UNet, plus the intra-object part head on the UNet's
+# per-voxel features and PartA2FCHead.  The snapshot this repository was modelled on holds no YAML for this detector, so the
+# POINT_HEAD and ROI_HEAD values are BUILD-DEFINED: they restate the upstream project's published KITTI setting for Part-A2 as
+# far as it is remembered here (a 12 x 12 x 12 RoI-aware grid of 128 features with at most 128 points a cell, three shared FC
+# layers of 256, class and box stacks of 256 -> 256, dropout 0.3, points scoring under 0.3 masked out of the part features,
+# point stacks of 256 -> 256, ground truth enlarged by 0.2 m for the point targets, 100 test-time proposals at NMS 0.7) and were
+# not checked against that file.  Eval only: TARGET_CONFIG holds the box coder alone.  ROI_AWARE_POOL.FUSED selects the batched
+# sparse pooling + sparse FC over the reference's composed formulation.
+PART_A2_CFG = copy.deepcopy(SECOND_CFG)
+PART_A2_CFG['NAME'] = 'PartA2Net'
+PART_A2_CFG['BACKBONE_3D'] = {'NAME': 'UNetV2', 'RETURN_ENCODED_TENSOR': True}
+PART_A2_CFG['POINT_HEAD'] = {'NAME': 'PointIntraPartOffsetHead', 'CLS_FC': [256, 256], 'PART_FC': [256, 256], 'CLASS_AGNOSTIC': True,
+                             'TARGET_CONFIG': {'GT_EXTRA_WIDTH': [0.2, 0.2, 0.2]}}
+PART_A2_CFG['ROI_HEAD'] = {
+    'NAME': 'PartA2FCHead', 'CLASS_AGNOSTIC': True,
+    'SHARED_FC': [256, 256, 256], 'CLS_FC': [256, 256], 'REG_FC': [256, 256], 'DP_RATIO': 0.3,
+    'DISABLE_PART': False, 'SEG_MASK_SCORE_THRESH': 0.3,
+    'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                             'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                   'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 1024,
+                            'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+    'ROI_AWARE_POOL': {'POOL_SIZE': 12, 'NUM_FEATURES': 128, 'MAX_POINTS_PER_VOXEL': 128, 'FUSED': True},
+    'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -322,4 +346,13 @@ def build_pv_rcnn(model_cfg=None, num_point_features=4, dataset=None):
     another dataset namespace is given.  Runs in eval mode only."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(PV_RCNN_CFG if model_cfg is None else model_cfg))   # (the SA constructors edit MLPS)
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_part_a2(model_cfg=None, num_point_features=4, dataset=None):
+    """PartA2Net from PART_A2_CFG (or a dict like it): DynamicMeanVFE -> UNetV2 -> HeightCompression -> BaseBEVBackbone ->
+    AnchorHeadSingle -> PointIntraPartOffsetHead -> PartA2FCHead, on voxel_dataset() unless another dataset namespace is given.
+    Runs in eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(PART_A2_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

@@ -4,6 +4,7 @@ from collections import namedtuple
 
 from .detector3d_template import BACKBONES_2D, BACKBONES_3D, MAP_TO_BEV, VFE, Detector3DTemplate
 from .centerpoint import CenterPoint
+from .partA2_net import PartA2Net
 from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
@@ -20,6 +21,7 @@ __all__ = {
     'SECONDNet': SECONDNet,
     'VoxelRCNN': VoxelRCNN,
     'PVRCNN': PVRCNN,
+    'PartA2Net': PartA2Net,
 }
 
 

@@ -29,6 +29,62 @@ class RoIAwarePool3d(nn.Module):
         return RoIAwarePool3dFunction.apply(rois, pts, pts_feature, self.out_size, self.max_pts_each_voxel, pool_method)
 
 
+class PointListOverflow(RuntimeError):
+    """roiaware_pool_sparse: the boxes list more (box, point) pairs than its workspace was sized for"""
+
+
+def sparse_list_capacity(num_rois, num_points, cells, max_pts_each_voxel):
+    """ints of roiaware_pool_sparse's point-list workspace: every listed (box, point) pair takes one.  No more than the
+    composed form's (boxes, cells, max_pts - 1) lists, and no more than 4 pairs a point plus 256 a box, which only boxes piled on
+    one another exceed (the operator then raises and the caller takes the composed form)."""
+    return max(min(num_rois * cells * (int(max_pts_each_voxel) - 1), 4 * num_points + 256 * num_rois), 1)
+
+
+@torch.no_grad()
+def roiaware_pool_sparse(rois, points, point_counts, part_features, rpn_features, out_size, max_pts_each_voxel=128, list_capacity=None):
+    """The head's two RoI-aware poolings for the whole batch, straight to sparse rows (pdm_roiaware_pool_sparse_index / _emit,
+    csrc/roiaware_sparse.hip): rois (B, N, 7), points (P, 3) batch-major, point_counts (B) int32 rows per sample (a
+    device tensor: it is not read here), part_features (P, 4), rpn_features (P, C) ->
+      coords (Q, 4) int32 (roi, x, y, z), ascending in ((roi Sx + x) Sy + y) Sz + z: the order pooled.sum(-1).nonzero() gives
+      part (Q, 4) the 'avg' pooling, rpn (Q, C) the 'max' pooling
+    of the ACTIVE cells: those whose averaged part channels, added in fp32 in ascending channel order, are non-zero.  Bit-equal
+    to RoIAwarePool3d 'avg' / 'max' per sample, cat, sum(-1) != 0, nonzero and a gather.  ONE host read ({Q, overflow}, counted in
+    sparse_conv_ops.HOST_READS); none and no launch without boxes or points.  Raises PointListOverflow (a RuntimeError) when the point lists do not
+    fit list_capacity (default sparse_list_capacity)."""
+    from .. import sparse_conv_ops
+    assert rois.is_cuda and rois.dim() == 3 and rois.shape[2] == 7, 'rois: (B, N, 7) on the GPU'
+    assert points.dim() == 2 and points.shape[1] == 3 and part_features.shape == (points.shape[0], 4), (tuple(points.shape), tuple(part_features.shape))
+    assert rpn_features.dim() == 2 and rpn_features.shape[0] == points.shape[0] and rpn_features.shape[1] >= 1, tuple(rpn_features.shape)
+    assert point_counts.is_cuda and point_counts.dtype == torch.int32 and point_counts.shape == (rois.shape[0],), 'point_counts: int32 (B) on the GPU'
+    ox, oy, oz = _out_size(out_size)
+    rois, points, part, rpn = (t.float().contiguous() for t in (rois, points, part_features, rpn_features))
+    point_counts = point_counts.contiguous()
+    (B, N), P, C, dev = rois.shape[:2], points.shape[0], rpn.shape[1], rois.device
+    empty = (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty((0, 4), dtype=torch.float32, device=dev),
+             torch.empty((0, C), dtype=torch.float32, device=dev))
+    if B * N == 0 or P == 0:
+        return empty
+    L = sparse_list_capacity(B * N, P, ox * oy * oz, max_pts_each_voxel) if list_capacity is None else int(list_capacity)
+    nbytes = _native.lib().pdm_roiaware_pool_sparse_workspace_bytes(B, N, ox, oy, oz, L)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    record = torch.empty(2, dtype=torch.int32, device=dev)
+    _native.call("pdm_roiaware_pool_sparse_index", _native.stream(dev), B, N, P, int(max_pts_each_voxel), ox, oy, oz, rois.data_ptr(),
+                 points.data_ptr(), point_counts.data_ptr(), part.data_ptr(), L, record.data_ptr(), ws.data_ptr(), nbytes)
+    sparse_conv_ops.HOST_READS += 1
+    Q, overflow = (int(v) for v in record.cpu().tolist())
+    if overflow:
+        raise PointListOverflow(f'roiaware_pool_sparse: the boxes list more than list_capacity = {L} (box, point) pairs; use the composed '
+                           f'RoIAwarePool3d formulation or pass a larger list_capacity')
+    if Q == 0:
+        return empty
+    coords = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+    out_part = torch.empty((Q, 4), dtype=torch.float32, device=dev)
+    out_rpn = torch.empty((Q, C), dtype=torch.float32, device=dev)
+    _native.call("pdm_roiaware_pool_sparse_emit", _native.stream(dev), B, N, P, C, ox, oy, oz, part.data_ptr(), rpn.data_ptr(), L, Q,
+                 ws.data_ptr(), nbytes, coords.data_ptr(), out_part.data_ptr(), out_rpn.data_ptr())
+    return coords, out_part, out_rpn
+
+
 class RoIAwarePool3dFunction(Function):
     @staticmethod
     def forward(ctx, rois, pts, pts_feature, out_size, max_pts_each_voxel, pool_method):

@@ -12,6 +12,10 @@ have no gradient.
 Host reads: voxel_assign() copies the two ints {N', P} to the host, and a STRIDED rulebook() copies the one int P_out;
 a submanifold rulebook, sparse_conv(), to_dense(), site_index(), roi_grid_pool(), roi_grid_query() and the gradients read nothing.  HOST_READS counts the copies.
 
+Part-A2's head: pack_fc_weight / sparse_fc (csrc/sparse_fc.hip) apply the Conv1d behind SparseConvTensor.dense() to
+the sparse rows of the RoI grids without the dense tensor, no host read; roiaware_pool3d_utils.roiaware_pool_sparse, which
+produces those rows, counts its one host read in HOST_READS as well.
+
 The torch formulations these stand for (torch.unique + scatter_mean, and per offset index_select -> mm -> index_add_) are
 what the tests and tools/sparse_conv_rate.py compare with.
 """
@@ -26,7 +30,9 @@ CIN_SUPPORTED = (3, 4, 5, 6, 7, 8, 16, 32, 64, 128)
 COUT_SUPPORTED = (16, 32, 64, 128)
 
 Voxels = namedtuple('Voxels', ['kept_idx', 'unq_inv', 'voxel_coords', 'voxel_count', 'voxel_mean', 'num_kept', 'num_voxels'])
-Rulebook = namedtuple('Rulebook', ['out_indices', 'nbr', 'out_shape', 'kernel_size', 'subm'])
+# in_indices / in_shape: the input rows and grid the table was built over, where an inverse convolution finds them
+Rulebook = namedtuple('Rulebook', ['out_indices', 'nbr', 'out_shape', 'kernel_size', 'subm', 'in_indices', 'in_shape'],
+                      defaults=(None, None))
 SiteIndex = namedtuple('SiteIndex', ['workspace', 'nbytes', 'num_rows', 'batch_size', 'spatial_shape'])
 
 
@@ -109,7 +115,7 @@ def rulebook(indices, batch_size, spatial_shape, kernel_size, stride=1, padding=
     nbr = torch.empty((P_out, kvol), dtype=torch.int32, device=dev)
     _native.call("pdm_sparse_rulebook", _native.stream(dev), P, indices.data_ptr(), P_out, *geom,
                  None if subm else out_indices.data_ptr(), nbr.data_ptr(), ws.data_ptr(), nbytes)
-    return Rulebook(out_indices, nbr, conv_out_shape((D, H, W), k, s, p, subm), k, bool(subm))
+    return Rulebook(out_indices, nbr, conv_out_shape((D, H, W), k, s, p, subm), k, bool(subm), indices, (D, H, W))
 
 
 @torch.no_grad()
@@ -435,4 +441,54 @@ def _to_dense(features, indices, batch_size, spatial_shape, out=None):
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
     _native.call("pdm_sparse_to_dense", _native.stream(dev), P, C, features.data_ptr(), indices.data_ptr(), B, D, H, W, out.data_ptr(),
                  ws.data_ptr(), nbytes)
+    return out
+
+
+def pack_fc_weight(weight, cells):
+    """weight (Cout, C cells[, 1]), the Conv1d behind SparseConvTensor.dense() (column c cells + cell: dense() is channels-first) ->
+    the flat fp32 tensor pdm_sparse_fc reads, cell-major: [cell][kb][nb][lane][j] = W[16 nb + (lane & 15)][(16 kb + 4 (lane >> 4) + j)
+    cells + cell], the A fragments of mfma_f32_16x16x4f32.  Device arithmetic only."""
+    w = weight.detach().float().reshape(weight.shape[0], -1)
+    cout, cells = w.shape[0], int(cells)
+    C = w.shape[1] // cells
+    if w.shape[1] != C * cells or C % 16 or cout % 16:
+        raise ValueError(f'sparse_fc: weight {tuple(weight.shape)} over {cells} cells; C and Cout must be multiples of 16')
+    w = w.reshape(cout // 16, 16, C // 16, 4, 4, cells).permute(5, 2, 0, 3, 1, 4)          # (cell, kb, nb, g, i, j)
+    out = w.contiguous().reshape(-1)
+    assert out.numel() == _native.lib().pdm_sparse_fc_packed_floats(cells, C, cout)
+    return out
+
+
+def sparse_fc_chunks(num_rois, cells, cout):
+    """partials pdm_sparse_fc adds per output, each over a run of ascending cells: a function of these three numbers alone"""
+    return _native.lib().pdm_sparse_fc_chunks(int(num_rois), int(cells), int(cout))
+
+
+@torch.no_grad()
+def sparse_fc(coords, feats_a, feats_b, num_rois, spatial_shape, wpack, cout, scale=None, shift=None, relu=False, out=None):
+    """out (R, cout)[r] = epilogue(sum over the rows q of box r of W[:, :, cell(q)] x[q]) (pdm_sparse_fc, csrc/sparse_fc.hip):
+    SparseConvTensor(cat(feats_a, feats_b), coords, spatial_shape, R).dense().view(R, -1) @ W.T without the dense tensor or the
+    cat.  coords (Q, 4) int32 rows (box, x, y, z) ascending in ((box Sx + x) Sy + y) Sz + z, distinct; feats_a (Q, C_a), feats_b
+    (Q, C_b) or None; wpack = pack_fc_weight(weight, Sx Sy Sz); epilogue = * scale + shift (both or neither), ReLU; boxes without
+    rows get epilogue(0).  Fixed-order partials, no atomics: two runs give the same bits.  No host read."""
+    assert coords.is_cuda and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4, 'coords: int32 (Q, 4) on the GPU'
+    sx, sy, sz = (int(v) for v in spatial_shape)
+    Q, R, dev = coords.shape[0], int(num_rois), coords.device
+    coords, feats_a = coords.contiguous(), feats_a.contiguous()
+    assert feats_a.dtype == torch.float32 and feats_a.dim() == 2 and feats_a.shape[0] == Q, tuple(feats_a.shape)
+    ca, cb = feats_a.shape[1], 0
+    if feats_b is not None:
+        feats_b = feats_b.contiguous()
+        assert feats_b.dtype == torch.float32 and feats_b.dim() == 2 and feats_b.shape[0] == Q, tuple(feats_b.shape)
+        cb = feats_b.shape[1]
+    assert wpack.numel() == sx * sy * sz * (ca + cb) * cout, (wpack.numel(), sx * sy * sz, ca + cb, cout)
+    if out is None:
+        out = torch.empty((R, cout), dtype=torch.float32, device=dev)
+    assert out.shape == (R, cout) and out.is_contiguous() and out.dtype == torch.float32
+    opt = [None if t is None else t.detach().float().contiguous() for t in (scale, shift)]
+    nbytes = _native.lib().pdm_sparse_fc_workspace_bytes(Q, R, sx * sy * sz, cout)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    _native.call("pdm_sparse_fc", _native.stream(dev), Q, R, sx, sy, sz, ca, cb, cout, coords.data_ptr(), feats_a.data_ptr(),
+                 None if feats_b is None else feats_b.data_ptr(), wpack.data_ptr(), *(None if t is None else t.data_ptr() for t in opt),
+                 1 if relu else 0, out.data_ptr(), ws.data_ptr(), nbytes)
     return out

@@ -8,7 +8,12 @@ requires grad, takes the autograd path on CUDA tensors: sparse_conv_ops.SparseCo
 pdm_sparse_conv_split, the forward kernel with one accumulator per offset, the latter over the transposed rulebook; weight
 gradient by pdm_sparse_conv_wgrad), then the BatchNorm1d module itself on the
 (P, C) features (batch statistics over the active rows), + residual, ReLU, all in torch.  CPU tensors there raise
-NotImplementedError.  SparseInverseConv3d is not built.
+NotImplementedError.
+
+SparseInverseConv3d(indice_key) is the forward kernel over the TRANSPOSED table of the strided convolution that built the
+rulebook under that key, with the layer's own weights (not transposed, offsets not flipped): out[i] = sum over the pairs
+nbr[j, k] = i of W[:, k, :] x[j].  Its rows are that convolution's input rows, in their order, on its input grid.  The table is
+the one the data gradient walks (one (indice_key, 'nbr_t') slot for both).  Eval mode only: its gradients are not built.
 
 A rulebook is built once per indice_key per forward and shared by the layers that name the key (the tensors of one forward
 share one indice_dict), as spconv shares them.  Row orders: a submanifold convolution keeps its input's rows; a strided one
@@ -105,13 +110,14 @@ class SparseConvolution(SparseModule):
             x.indice_dict[self.indice_key] = rb
         return rb
 
-    def get_transpose(self, x, rb):
+    def get_transpose(self, x, rb, num_in_rows=None):
         """the transposed table of a strided rulebook, built once per forward beside the rulebook it belongs to (under the
-        key (indice_key, 'nbr_t') of the tensors' shared indice_dict)"""
+        key (indice_key, 'nbr_t') of the tensors' shared indice_dict).  num_in_rows: the rows of the rulebook's input when x
+        is not that input (the inverse convolution's x is its output)"""
         key = (self.indice_key, 'nbr_t')
         nbr_t = x.indice_dict.get(key) if self.indice_key is not None else None
         if nbr_t is None:
-            nbr_t = sparse_conv_ops.rulebook_transpose(rb.nbr, x.features.shape[0])
+            nbr_t = sparse_conv_ops.rulebook_transpose(rb.nbr, x.features.shape[0] if num_in_rows is None else num_in_rows)
             if self.indice_key is not None:
                 x.indice_dict[key] = nbr_t
         return nbr_t
@@ -159,6 +165,37 @@ class SparseConv3d(SparseConvolution):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, subm=False)
 
 
+class SparseInverseConv3d(SparseConvolution):
+    """spconv 2.x's SparseInverseConv3d(in_channels, out_channels, kernel_size, indice_key, bias=True): undoes the site set of
+    the SparseConv3d that shares its indice_key (not its values)"""
+
+    def __init__(self, in_channels, out_channels, kernel_size, indice_key=None, bias=True, **kwargs):
+        assert indice_key is not None, 'SparseInverseConv3d needs the indice_key of the convolution it inverts'
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, indice_key, subm=False)
+
+    def forward(self, x, norm=None, relu=False, residual=None):
+        """x: a tensor whose rows are the paired convolution's output rows -> SparseConvTensor on that convolution's input
+        rows and grid.  One pdm_sparse_conv launch over the transposed table, norm and ReLU folded as SparseConvolution does."""
+        if self.training or (norm is not None and norm.training) or x.features.requires_grad:
+            raise NotImplementedError('SparseInverseConv3d runs in eval mode without grad: its data and weight gradients are not built')
+        assert x.features.shape[1] == self.in_channels, (tuple(x.features.shape), self.in_channels)
+        rb = x.indice_dict.get(self.indice_key)
+        if rb is None:
+            raise KeyError(f'SparseInverseConv3d: no convolution has stored a rulebook under indice_key {self.indice_key!r} in this '
+                           f'tensor\'s indice_dict (keys: {[k for k in x.indice_dict if not isinstance(k, tuple)]})')
+        assert not rb.subm and rb.in_indices is not None, \
+            f'indice_key {self.indice_key}: a submanifold rulebook; an inverse convolution pairs with a strided SparseConv3d'
+        assert rb.kernel_size == self.kernel_size, f'indice_key {self.indice_key}: kernel {rb.kernel_size}, this layer {self.kernel_size}'
+        assert rb.nbr.shape[0] == x.features.shape[0], \
+            f'indice_key {self.indice_key}: {x.features.shape[0]} rows, the paired convolution wrote {rb.nbr.shape[0]}'
+        nbr_t = self.get_transpose(x, rb, rb.in_indices.shape[0])
+        wpack = self._cached('pack', [self.weight], lambda: sparse_conv_ops.pack_weight(self.weight))
+        sources = [self.bias] + ([norm.weight, norm.bias, norm.running_mean, norm.running_var] if norm is not None else [])
+        scale, shift = self._cached('fold', sources, lambda: fold_norm(norm, self.bias, self.out_channels, self.weight))
+        out = sparse_conv_ops.sparse_conv(x.features, nbr_t, wpack, self.in_channels, self.out_channels, scale, shift, residual, relu)
+        return SparseConvTensor(out, rb.in_indices, rb.in_shape, x.batch_size, x.indice_dict)
+
+
 class SparseSequential(SparseModule, nn.Sequential):
     """nn.Sequential over SparseConvTensors: sparse modules take the tensor, plain nn modules its features.  A convolution
     takes the BatchNorm1d and the ReLU behind it: into its own launch in eval mode without grad, behind its autograd node
@@ -188,4 +225,4 @@ class SparseSequential(SparseModule, nn.Sequential):
         return x
 
 
-__all__ = ['SparseConvTensor', 'SparseModule', 'SparseSequential', 'SubMConv3d', 'SparseConv3d', 'replace_feature']
+__all__ = ['SparseConvTensor', 'SparseModule', 'SparseSequential', 'SubMConv3d', 'SparseConv3d', 'SparseInverseConv3d', 'replace_feature']

@@ -1263,6 +1263,32 @@ int pdm_roi_keypoint_query(void *stream, int B, int n, int roi_stride, const flo
                            const int *xyz_batch_cnt, int max_per_sample, int nscales, float radius0, int nsample0, float radius1,
                            int nsample1, float *grid_points, int *idx0, unsigned char *empty0, int *idx1, unsigned char *empty1);
 
+/* PV-RCNN++'s proposal-centric partition (csrc/spc.hip): sample_points_with_roi and the front half of sector_fps of
+ * the reference's voxel_set_abstraction.py, for the whole batch.  Every argument is checked before any launch; nothing is read on
+ * the host; no atomic cursor (two runs and a graph replay give the same bits); five launches.
+ *   xyz (N, 3) fp32, sample-major stacked rows; xyz_batch_cnt (B <= 1024) int32 on the device (rows past the counts' sum belong
+ *   to no sample and are ignored); rois (B, n, roi_stride >= 7) fp32, 1 <= n <= pdm_spc_partition_max_rois() = 1024
+ *   (PDM_E_TOOLARGE beyond); num_sectors S in [0, pdm_spc_partition_max_sectors() = 64]; num_keypoints K >= 1 when S > 0.
+ * KEEP: a row is kept when d_min < fl(||dims / 2|| + radius), d = sqrt_rn(sqdist(p - centre)) (common.h's pinned squared
+ *   distance), the rois of its sample walked in ascending index with a strict < (ties to the lower index), ||dims / 2|| =
+ *   sqrt_rn(sqdist) of the halved dimensions of the roi that gave d_min.  All-zero roi rows are rois at the origin of size zero.
+ *   mask (N) bytes, when not null: that verdict, 0 / 1, for every row of a sample.
+ * FALLBACK (fallback != 0): a sample with points of which none is kept yields its first row alone (points[:1]); mask stays 0.
+ *   A sample without points yields nothing: every count of it is 0.
+ * SECTOR (S > 0): s = floor(fl(fl(atan2f(y, x) + PI_F) / SIZE_F)) clamped to [0, S], SIZE_F = (float)(2 pi / S), IEEE fp32
+ *   division.  s = S is no sector: the row is dropped from the output but counted in kept_cnt.  S = 0: one segment a sample.
+ * OUT: seg_xyz (N, 3) and seg_row (N) int32 source rows, written up to the sum of seg_cnt: sample-major, sector ascending, source
+ *   order inside a sector.  seg_cnt (B max(S, 1)); kept_cnt (B) = the sample's kept rows N', dropped ones included;
+ *   seg_take (B S; not written and may be null when S = 0) = min(c, ceil(c / N' * K)) evaluated in double in that order.
+ * workspace: pdm_spc_partition_ws_bytes(N, B, num_sectors) bytes (0 for sizes the call refuses), contents irrelevant. */
+/* align: xyz, rois, outputs any (4-byte and 1-byte accesses); workspace 8 B (checked). */
+int pdm_spc_partition_max_rois(void);
+int pdm_spc_partition_max_sectors(void);
+size_t pdm_spc_partition_ws_bytes(int N, int B, int num_sectors);
+int pdm_spc_partition(void *stream, int N, const float *xyz, int B, const int *xyz_batch_cnt, int n, int roi_stride, const float *rois,
+                      float radius, int num_sectors, int num_keypoints, int fallback, float *seg_xyz, int *seg_row, int *seg_cnt,
+                      int *seg_take, int *kept_cnt, unsigned char *mask, void *workspace, size_t workspace_bytes);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -21,7 +21,8 @@ of another sample (the row the clamped index lands on) under the empty sample's 
 so its set-abstraction columns are the layers' response to an empty ball.
 
 Refused with NotImplementedError: SAMPLE_METHOD 'SPC', POINT_SOURCE 'voxel_centers', FILTER_NEIGHBOR_WITH_ROI and the
-VectorPoolAggregationModuleMSG layers (PV-RCNN++), and training mode.
+VectorPoolAggregationModuleMSG layers (PV-RCNN++: VoxelSetAbstractionSPC in voxel_set_abstraction_spc.py serves them, under its own
+registry NAME), and training mode.
 """
 import torch
 import torch.nn as nn
@@ -78,23 +79,9 @@ class VoxelSetAbstraction(nn.Module):
         self.voxel_size = [float(v) for v in voxel_size]
         self.point_cloud_range = [float(v) for v in point_cloud_range]
         self.use_fused_bev = True
-        if _get(model_cfg, 'POINT_SOURCE') != 'raw_points':
-            raise NotImplementedError(f"VoxelSetAbstraction: POINT_SOURCE = {_get(model_cfg, 'POINT_SOURCE')!r} (only 'raw_points'; "
-                                      "'voxel_centers' is PV-RCNN++)")
-        if _get(model_cfg, 'SAMPLE_METHOD') != 'FPS':
-            raise NotImplementedError(f"VoxelSetAbstraction: SAMPLE_METHOD = {_get(model_cfg, 'SAMPLE_METHOD')!r} (only 'FPS'; 'SPC', the "
-                                      "sectorized proposal-centric sampling, is PV-RCNN++)")
+        self._check_config(model_cfg)
         SA_cfg = _get(model_cfg, 'SA_LAYER')
         sources = list(_get(model_cfg, 'FEATURES_SOURCE'))
-        for src_name in sources:
-            if src_name == 'bev':
-                continue
-            cfg = _get(SA_cfg, src_name)
-            if _get(cfg, 'FILTER_NEIGHBOR_WITH_ROI', False):
-                raise NotImplementedError(f'VoxelSetAbstraction: SA_LAYER.{src_name}.FILTER_NEIGHBOR_WITH_ROI is PV-RCNN++')
-            if _get(cfg, 'NAME', 'StackSAModuleMSG') != 'StackSAModuleMSG':
-                raise NotImplementedError(f"VoxelSetAbstraction: SA_LAYER.{src_name}.NAME = {_get(cfg, 'NAME')!r} (the "
-                                          "VectorPoolAggregationModuleMSG layers are PV-RCNN++)")
 
         self.SA_layers = nn.ModuleList()
         self.SA_layer_names = []
@@ -125,6 +112,26 @@ class VoxelSetAbstraction(nn.Module):
         self.vsa_point_feature_fusion = nn.Sequential(nn.Linear(c_in, width, bias=False), nn.BatchNorm1d(width), nn.ReLU())
         self.num_point_features = width
         self.num_point_features_before_fusion = c_in
+
+    def _check_config(self, model_cfg):
+        """what this class refuses (a subclass that serves more overrides it: VoxelSetAbstractionSPC)"""
+        see = '; see VoxelSetAbstractionSPC (voxel_set_abstraction_spc.py)'
+        if _get(model_cfg, 'POINT_SOURCE') != 'raw_points':
+            raise NotImplementedError(f"VoxelSetAbstraction: POINT_SOURCE = {_get(model_cfg, 'POINT_SOURCE')!r} (only 'raw_points'; "
+                                      f"'voxel_centers' is PV-RCNN++{see})")
+        if _get(model_cfg, 'SAMPLE_METHOD') != 'FPS':
+            raise NotImplementedError(f"VoxelSetAbstraction: SAMPLE_METHOD = {_get(model_cfg, 'SAMPLE_METHOD')!r} (only 'FPS'; 'SPC', the "
+                                      f"sectorized proposal-centric sampling, is PV-RCNN++{see})")
+        SA_cfg = _get(model_cfg, 'SA_LAYER')
+        for src_name in _get(model_cfg, 'FEATURES_SOURCE'):
+            if src_name == 'bev':
+                continue
+            cfg = _get(SA_cfg, src_name)
+            if _get(cfg, 'FILTER_NEIGHBOR_WITH_ROI', False):
+                raise NotImplementedError(f'VoxelSetAbstraction: SA_LAYER.{src_name}.FILTER_NEIGHBOR_WITH_ROI is PV-RCNN++{see}')
+            if _get(cfg, 'NAME', 'StackSAModuleMSG') != 'StackSAModuleMSG':
+                raise NotImplementedError(f"VoxelSetAbstraction: SA_LAYER.{src_name}.NAME = {_get(cfg, 'NAME')!r} (the "
+                                          f"VectorPoolAggregationModuleMSG layers are PV-RCNN++{see})")
 
     # ------------------------------------------------------------------ keypoints
 

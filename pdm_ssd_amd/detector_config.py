@@ -254,6 +254,38 @@ PART_A2_CFG['ROI_HEAD'] = {
     'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
 
 
+# PV-RCNN++: PV_RCNN_CFG with the proposals first, sectorized proposal-centric keypoint sampling and VectorPool aggregation.
+# BUILD-DEFINED, not taken from a YAML (the snapshot this repository was modelled on holds none for this detector): 4096 keypoints
+# by SPC over 6 sectors of the raw points within 1.6 m of a proposal, 90 fused features; bev, x_conv3, x_conv4 and the raw points,
+# each filtered to the neighbourhood of the proposals (4.0 / 6.4 / 2.4 m) and gathered by two-scale local_interpolation VectorPool
+# layers of 3 x 3 x 3 cells (2 x 2 x 2 at the raw points' first scale); a 6 x 6 x 6 RoI grid pooled by voxel_random_choice
+# VectorPool layers at 0.8 / 1.6 m with 32 samples.  Eval only.
+def _vector_pool(kind, reduced, post, cells, distances, nsample, widths):
+    cfg = {'NAME': 'VectorPoolAggregationModuleMSG', 'NUM_GROUPS': 2, 'LOCAL_AGGREGATION_TYPE': kind, 'NUM_REDUCED_CHANNELS': reduced,
+           'NUM_CHANNELS_OF_LOCAL_AGGREGATION': 32, 'MSG_POST_MLPS': [post]}
+    for k in range(2):
+        cfg[f'GROUP_CFG_{k}'] = {'NUM_LOCAL_VOXEL': list(cells[k]), 'MAX_NEIGHBOR_DISTANCE': distances[k], 'NEIGHBOR_NSAMPLE': nsample,
+                                 'POST_MLPS': list(widths)}
+    return cfg
+
+
+PV_RCNN_PP_CFG = copy.deepcopy(PV_RCNN_CFG)
+PV_RCNN_PP_CFG['NAME'] = 'PVRCNNPlusPlus'
+PV_RCNN_PP_CFG['PFE'] = {
+    'NAME': 'VoxelSetAbstractionSPC', 'POINT_SOURCE': 'raw_points', 'NUM_KEYPOINTS': 4096, 'NUM_OUTPUT_FEATURES': 90, 'SAMPLE_METHOD': 'SPC',
+    'SPC_SAMPLING': {'NUM_SECTORS': 6, 'SAMPLE_RADIUS_WITH_ROI': 1.6},
+    'FEATURES_SOURCE': ['bev', 'x_conv3', 'x_conv4', 'raw_points'],
+    'SA_LAYER': {
+        'raw_points': dict(_vector_pool('local_interpolation', 1, 32, ([2, 2, 2], [3, 3, 3]), (0.2, 0.4), -1, [32, 32]),
+                           FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=2.4),
+        'x_conv3': dict(_vector_pool('local_interpolation', 32, 128, ([3, 3, 3], [3, 3, 3]), (1.2, 2.4), -1, [64, 64]),
+                        DOWNSAMPLE_FACTOR=4, INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=4.0),
+        'x_conv4': dict(_vector_pool('local_interpolation', 32, 128, ([3, 3, 3], [3, 3, 3]), (2.4, 4.8), -1, [64, 64]),
+                        DOWNSAMPLE_FACTOR=8, INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=6.4)}}
+PV_RCNN_PP_CFG['ROI_HEAD']['ROI_GRID_POOL'] = dict(
+    _vector_pool('voxel_random_choice', 30, 128, ([3, 3, 3], [3, 3, 3]), (0.8, 1.6), 32, [64, 64]), GRID_SIZE=6)
+
+
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
     return SimpleNamespace(class_names=CLASS_NAMES, grid_size=GRID_SIZE, voxel_size=VOXEL_SIZE,
@@ -355,4 +387,14 @@ def build_part_a2(model_cfg=None, num_point_features=4, dataset=None):
     Runs in eval mode only."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(PART_A2_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_pv_rcnn_plusplus(model_cfg=None, num_point_features=4, dataset=None):
+    """PVRCNNPlusPlus from PV_RCNN_PP_CFG (or a dict like it): the modules of build_pv_rcnn() with VoxelSetAbstractionSPC as the pfe
+    (DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> VoxelSetAbstractionSPC -> BaseBEVBackbone -> AnchorHeadSingle ->
+    PointHeadSimple -> PVRCNNHead in the template's build order; the detector's forward runs the proposal layer before the pfe), on
+    voxel_dataset() unless another dataset namespace is given.  Runs in eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(PV_RCNN_PP_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

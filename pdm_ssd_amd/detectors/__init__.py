@@ -9,6 +9,7 @@ from .pdm_ssd import PDMSSD
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
+from .pv_rcnn_plusplus import PVRCNNPlusPlus
 from .second_net import SECONDNet
 from .voxel_rcnn import VoxelRCNN
 
@@ -21,6 +22,7 @@ __all__ = {
     'SECONDNet': SECONDNet,
     'VoxelRCNN': VoxelRCNN,
     'PVRCNN': PVRCNN,
+    'PVRCNNPlusPlus': PVRCNNPlusPlus,
     'PartA2Net': PartA2Net,
 }
 

@@ -7,8 +7,9 @@ checkpoint loading).  The reference's template cannot be imported on this platfo
 pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
 (DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and the voxel family (DynamicMeanVFE ->
 VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
-outside the registries (MeanVFE, PillarVFE, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction, the roi_head slot
-the RoI heads of roi_heads/ (PointRCNN's second stage, Voxel R-CNN's, PV-RCNN's in eval mode).
+outside the registries (MeanVFE, PillarVFE, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction or PV-RCNN++'s
+VoxelSetAbstractionSPC, the roi_head slot the RoI heads of roi_heads/ (PointRCNN's second stage, Voxel R-CNN's, PV-RCNN's in eval
+mode).
 """
 import torch
 import torch.nn as nn

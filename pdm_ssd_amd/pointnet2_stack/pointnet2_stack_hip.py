@@ -97,6 +97,25 @@ def stack_farthest_point_sampling_wrapper(xyz, temp, xyz_batch_cnt, idx, num_sam
     return 1
 
 
+def stack_farthest_point_sampling_counts(xyz, temp, xyz_batch_cnt, idx, num_sampled_points):
+    """stack_farthest_point_sampling_wrapper for segments that fill only the FRONT of xyz (the counts may sum to fewer rows than
+    xyz holds: spc_ops.sector_fps_batch samples a compacted buffer whose fill is known on the device alone).  The same one host
+    read; returns it: (xyz_batch_cnt, num_sampled_points) as a (2, B) int32 tensor on the host."""
+    _check("xyz", xyz, torch.float32); _check("temp", temp, torch.float32); _check("idx", idx, torch.int32)
+    B = xyz_batch_cnt.numel()
+    _cnt("xyz_batch_cnt", xyz_batch_cnt, B); _cnt("num_sampled_points", num_sampled_points, B)
+    _numel_at_least("temp", temp, xyz.shape[0])
+    counts = torch.stack([xyz_batch_cnt, num_sampled_points]).cpu()
+    if bool((counts < 0).any()) or int(counts[0].sum()) > xyz.shape[0]:
+        raise ValueError("xyz_batch_cnt is negative or sums to more than the number of points")
+    if bool(((counts[1] > 0) & (counts[0] < 1)).any()):
+        raise ValueError("a sample with no points cannot be sampled")
+    _numel_at_least("idx", idx, int(counts[1].sum()))
+    _run("pdm_stack_furthest_point_sampling", xyz, B, int(counts[0].max()) if B else 0, xyz.data_ptr(), temp.data_ptr(),
+         xyz_batch_cnt.data_ptr(), idx.data_ptr(), num_sampled_points.data_ptr())
+    return counts
+
+
 # ---- voxel query and vector pool (pointnet2_api.cpp:14, :25-30) -------------------------------------------------
 
 def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_range, new_xyz, xyz, new_coords, point_indices, idx):

@@ -9,7 +9,7 @@ roi_grid_pool (`use_fused_pool`, default on): ONE launch of pdm_roi_keypoint_que
 grid points and, for all scales at once, the global neighbour rows and empty-ball masks; the existing fused gather -> MLP -> max
 kernels then run once per scale on those rows and write their columns of the (B n G^3, sum C) output.  No host read, no
 torch.cat, graph-capturable.  More keypoints a sample than the operator's cap, more than two scales, a module the fused
-kernels do not serve and use_fused_pool = False take the composed path (torch grid points, then ball_query per scale inside
+kernels do not serve (a VectorPoolAggregationModuleMSG ROI_GRID_POOL among them) and use_fused_pool = False take the composed path (torch grid points, then ball_query per scale inside
 the module): the on-device checker.  `last_pool_path` tells which ran.
 
 Training raises NotImplementedError: eval only.
@@ -88,7 +88,8 @@ class PVRCNNHead(RoIHeadTemplate):
         new_cnt = torch.full((B,), n * G ** 3, dtype=torch.int32, device=rois.device)
 
         bound = int(batch_dict.get('point_coords_max_per_sample', xyz.shape[0]))
-        if (self.use_fused_pool and rois.is_cuda and len(layer.groupers) <= 2 and 0 < xyz.shape[0] and bound <= pv_rcnn_ops.roi_keypoint_query_cap()
+        # (a VectorPool ROI_GRID_POOL, PV-RCNN++'s, has no groupers: it pools through the composed path, its own forward)
+        if (self.use_fused_pool and rois.is_cuda and hasattr(layer, 'groupers') and len(layer.groupers) <= 2 and 0 < xyz.shape[0] and bound <= pv_rcnn_ops.roi_keypoint_query_cap()
                 and self.num_pooled_channels % 4 == 0 and layer._fused_ok(xyz, features)):
             grid, idx, empty = pv_rcnn_ops.roi_keypoint_query(rois, G, xyz, xyz_batch_cnt, bound, [g.radius for g in layer.groupers],
                                                               [g.nsample for g in layer.groupers])

@@ -1289,6 +1289,39 @@ int pdm_spc_partition(void *stream, int N, const float *xyz, int B, const int *x
                       float radius, int num_sectors, int num_keypoints, int fallback, float *seg_xyz, int *seg_row, int *seg_cnt,
                       int *seg_take, int *kept_cnt, unsigned char *mask, void *workspace, size_t workspace_bytes);
 
+/* SECOND-IoU's RoI pooling (csrc/bev_roi_crop.hip).  Both check every argument before any launch, use no atomics (two
+ * runs give the same bits), read nothing on the host and can be captured in a graph.  Neither has a gradient: the head detaches the
+ * map and the rois in front of this step.
+ * pdm_bev_roi_crop: rois (B, n, roi_stride >= 7) fp32 rows (x, y, z, dx, dy, dz, heading, ...); spatial_features_2d (B, C, H, W) fp32
+ *   contiguous, as BaseBEVBackbone leaves it, read in place; (x0, y0) the range minima; cell_x, cell_y = VOXEL_SIZE * DOWNSAMPLE_RATIO
+ *   (the double product rounded once to fp32); 2 <= G <= 8 (G = 1 has no corner-aligned lattice: PDM_E_BADARG).
+ *   -> pooled (B n, C, G, G), rows of ld >= C G^2 floats, column c G^2 + i G + j: the reference's affine_grid + grid_sample
+ *   (align_corners = True, zero padding) of the RoI's rotated rectangle.  Pixel position of cell (i, j), fp32, one rounding per
+ *   operation, in this order:  cx = (x - x0) / cell_x; hx = (dx * 0.5) / cell_x; cy, hy likewise; (s, c) = sincosf(heading);
+ *   u = (2 j - (G - 1)) / (G - 1); v = (2 i - (G - 1)) / (G - 1);
+ *   px = (((hx c) u) - ((hx s) v)) + cx;  py = (((hy s) u) + ((hy c) v)) + cy
+ *   (theta multiplied out: the (W - 1), (H - 1) terms cancel).  fx = px - floor(px), fy likewise;
+ *   value = ((v00 ((1 - fx)(1 - fy)) + v01 (fx (1 - fy))) + v10 ((1 - fx) fy)) + v11 (fx fy), v00 = im[floor py][floor px], v01 its
+ *   right, v10 its lower, v11 its lower right neighbour; a corner outside the map is 0 and is not read; a position outside
+ *   (-1, W) x (-1, H), or NaN, gives exactly 0.  H, W in [2, 32768], C <= 65536.  One launch.
+ * pdm_bev_roi_crop_fc: out (B n, Cout) = epilogue(crop(r) . W^T) without the (B n, C G^2) tensor; epilogue(v) = relu(v scale + shift)
+ *   as one multiply and one add, scale / shift (Cout) both or neither.  wpack (pdm_bev_roi_crop_fc_packed_floats, 16-byte aligned):
+ *   [kb][nb][lane][j] = W[16 nb + (lane & 15)][16 kb + 4 (lane >> 4) + j] of the Conv1d weight (Cout, C G^2).  The crop's values
+ *   have pdm_bev_roi_crop's bits (the same device routine); the products go through mfma_f32_16x16x4f32 (an fp32 fma chain in
+ *   ascending k) and the contraction K = C G^2 is cut into pdm_bev_roi_crop_fc_chunks(R, C, G, Cout) runs of whole 128-index
+ *   stages, a function of those four numbers alone, whose partials are added in ascending order.  C a multiple of 16 up to 512,
+ *   Cout a multiple of 16 up to 1024, R Cout < 2^31.  workspace: pdm_bev_roi_crop_fc_workspace_bytes bytes (0 for sizes the call
+ *   refuses), 16-byte aligned, contents irrelevant.  Two launches. */
+/* align: rois, map, pooled, out any (4-byte accesses); wpack and workspace 16 B (checked). */
+int pdm_bev_roi_crop(void *stream, int B, int n, int roi_stride, const float *rois, int C, int H, int W, const float *spatial_features_2d,
+                     float x0, float y0, float cell_x, float cell_y, int G, float *pooled, long long ld);
+size_t pdm_bev_roi_crop_fc_packed_floats(int C, int G, int Cout);
+int pdm_bev_roi_crop_fc_chunks(int R, int C, int G, int Cout);
+size_t pdm_bev_roi_crop_fc_workspace_bytes(int R, int C, int G, int Cout);
+int pdm_bev_roi_crop_fc(void *stream, int B, int n, int roi_stride, const float *rois, int C, int H, int W, const float *spatial_features_2d,
+                        float x0, float y0, float cell_x, float cell_y, int G, int Cout, const float *wpack, const float *scale,
+                        const float *shift, int relu, float *out, void *workspace, size_t workspace_bytes);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -11,13 +11,14 @@
 //           tile's boxes' rows of a cell are a contiguous piece of its list; products are added into an LDS accumulator
 //           (TR x Cout) by the one wave that owns the output channels, so every element sees its terms in ascending cell order.
 //           The tile is written whole, zeros included, to partial[chunk]
-//   reduce  out = epilogue(partial[0] + partial[1] + ...), ascending
+//   reduce  out = epilogue(partial[0] + partial[1] + ...), ascending (fc_reduce.h, shared with bev_roi_crop.hip)
 // Fixed-order partials rather than 64-bit fixed-point atomics: the chunk boundaries are a function of (R, cells, Cout) alone, so
 // two runs give the same bits, the result keeps fp32's relative error bound with no quantisation term, no scale has to be taken
 // from the data first, and the partials (chunks x R x Cout floats) are small beside the weight.
 #include <algorithm>
 
 #include "common.h"
+#include "fc_reduce.h"
 
 namespace pdm {
 
@@ -185,18 +186,6 @@ __global__ __launch_bounds__(FC_NT) void fc_main_kernel(FcArgs a) {
     __syncthreads();
     float *out = a.partial + ((size_t)blockIdx.y * a.R + r_lo) * a.Cout;
     for (int e = tid; e < (r_hi - r_lo) * a.Cout; e += FC_NT) out[e] = acc[e];
-}
-
-__global__ __launch_bounds__(FC_NT) void fc_reduce_kernel(int R, int Cout, int nchunk, const float *__restrict__ partial,
-                                                          const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                          float *__restrict__ out) {
-    const size_t n = (size_t)R * Cout, e = (size_t)blockIdx.x * FC_NT + threadIdx.x;
-    if (e >= n) return;
-    float v = 0.f;
-    for (int k = 0; k < nchunk; ++k) v += partial[(size_t)k * n + e];
-    if (scale) v = v * scale[e % Cout] + shift[e % Cout];
-    if (relu) v = v < 0.0f ? 0.0f : v;      // a NaN stays, as torch's ReLU keeps it
-    out[e] = v;
 }
 
 }  // namespace pdm

@@ -200,6 +200,35 @@ VOXEL_RCNN_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
     'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
     'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0, 'code_weights': [1.0] * 7}}
 
+# SECOND-IoU: SECOND_CFG's front as it is, plus SECONDHead on the 2-D backbone's 512-channel map (stride 8).  The snapshot this
+# repository was modelled on holds no YAML for this detector, so the ROI_HEAD values are BUILD-DEFINED and were not checked
+# against any file: class-agnostic head, a 7 x 7 crop of the 512 channels at DOWNSAMPLE_RATIO 8, FC stacks of 256 -> 256, dropout
+# 0.3, 512 train proposals at NMS 0.8, 100 test proposals at NMS 0.7.  Of TARGET_CONFIG it holds the box coder alone, so its second
+# stage has no training half (SECOND_IOU_TRAIN_CFG below adds it).  POST_PROCESSING scores the boxes by the predicted IoU.
+SECOND_IOU_CFG = copy.deepcopy(SECOND_CFG)
+SECOND_IOU_CFG['NAME'] = 'SECONDNetIoU'
+SECOND_IOU_CFG['ROI_HEAD'] = {
+    'NAME': 'SECONDHead', 'CLASS_AGNOSTIC': True,
+    'SHARED_FC': [256, 256], 'IOU_FC': [256, 256], 'DP_RATIO': 0.3,
+    'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                             'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                   'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 2048,
+                            'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+    'ROI_GRID_POOL': {'GRID_SIZE': 7, 'IN_CHANNEL': 512, 'DOWNSAMPLE_RATIO': 8},
+    'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder'}}
+SECOND_IOU_CFG['POST_PROCESSING']['NMS_CONFIG']['SCORE_TYPE'] = 'iou'
+
+# SECOND_IOU_CFG plus the proposal-target sampler (TARGET_CONFIG) and the IoU loss settings (LOSS_CONFIG): a head built from this
+# dict has the training half, and build_second_iou(SECOND_IOU_TRAIN_CFG) takes training steps.  BUILD-DEFINED like the dict above:
+# 128 rois a sample, 'roi_iou' labels graded between 0.25 and 0.75, the binary cross-entropy IoU loss.  code_weights is what
+# RoIHeadTemplate.build_losses reads; this head regresses no box, so they weigh nothing.
+SECOND_IOU_TRAIN_CFG = copy.deepcopy(SECOND_IOU_CFG)
+SECOND_IOU_TRAIN_CFG['ROI_HEAD']['TARGET_CONFIG'].update(
+    ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE='roi_iou', CLS_FG_THRESH=0.75, CLS_BG_THRESH=0.25,
+    CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
+SECOND_IOU_TRAIN_CFG['ROI_HEAD']['LOSS_CONFIG'] = {
+    'IOU_LOSS': 'BinaryCrossEntropy', 'LOSS_WEIGHTS': {'rcnn_iou_weight': 1.0, 'code_weights': [1.0] * 7}}
+
 # PV-RCNN: SECOND_CFG's front as it is, plus the voxel set abstraction (PFE), the keypoint segmentation head and PVRCNNHead.  The
 # snapshot this repository was modelled on holds no YAML for this detector, so the PFE, POINT_HEAD and ROI_HEAD values are
 # BUILD-DEFINED: they restate the upstream project's published KITTI setting for PV-RCNN as far as it is remembered here (2048
@@ -369,6 +398,15 @@ def build_voxel_rcnn(model_cfg=None, num_point_features=4, dataset=None):
     voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and, from the training dict, takes training steps."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(VOXEL_RCNN_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def build_second_iou(model_cfg=None, num_point_features=4, dataset=None):
+    """SECONDNetIoU from SECOND_IOU_CFG, SECOND_IOU_TRAIN_CFG (with the second stage's training half) or a dict like them:
+    DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle -> SECONDHead, on voxel_dataset()
+    unless another dataset namespace is given.  Runs in eval mode and, from the training dict, takes training steps."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(SECOND_IOU_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
 
 

@@ -11,6 +11,7 @@ from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
 from .pv_rcnn_plusplus import PVRCNNPlusPlus
 from .second_net import SECONDNet
+from .second_net_iou import SECONDNetIoU
 from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
@@ -24,6 +25,7 @@ __all__ = {
     'PVRCNN': PVRCNN,
     'PVRCNNPlusPlus': PVRCNNPlusPlus,
     'PartA2Net': PartA2Net,
+    'SECONDNetIoU': SECONDNetIoU,
 }
 
 

@@ -3,6 +3,7 @@ from .partA2_head import PartA2FCHead
 from .pointrcnn_head import PointRCNNHead
 from .pvrcnn_head import PVRCNNHead
 from .roi_head_template import RoIHeadTemplate
+from .second_head import SECONDHead
 from .voxelrcnn_head import VoxelRCNNHead
 
 __all__ = {
@@ -11,4 +12,5 @@ __all__ = {
     'VoxelRCNNHead': VoxelRCNNHead,
     'PVRCNNHead': PVRCNNHead,
     'PartA2FCHead': PartA2FCHead,
+    'SECONDHead': SECONDHead,
 }

@@ -41,6 +41,12 @@ class SigmoidFocalClassificationLoss(nn.Module):
         return per_elem * weights
 
 
+def sigmoid_focal_cls_loss(input, target, gamma=2.0, alpha=0.25):
+    """SigmoidFocalClassificationLoss per element without weights, as a function: what SECONDHead's IOU_LOSS 'focalbce' calls
+    (the reference's second_head.py names loss_utils.sigmoid_focal_cls_loss; its own loss_utils does not define it)."""
+    return SigmoidFocalClassificationLoss(gamma=gamma, alpha=alpha)(input, target, torch.ones_like(input))
+
+
 class WeightedSmoothL1Loss(nn.Module):
     """Huber-style regression loss with the knee at beta (default 1/9): quadratic inside, linear outside; residuals are
     scaled per code before the loss and per anchor after it; a NaN target switches its element off."""

@@ -1072,6 +1072,39 @@ int pdm_pillar_scatter(void *stream, int P, int C, const float *pillar_features,
 int pdm_pillar_scatter_grad(void *stream, int P, int C, const float *grad_canvas, const int *voxel_coords, int B, int nx, int ny,
                             int nz, float *grad_features);
 
+/* Hard voxels (csrc/hard_voxel.hip, DESIGN.md "Hard voxels"): the reference's voxel generator and its MeanVFE / PillarVFE
+ * without a host loop, a sort or a float atomic: every result is a function of the input alone, bit for bit.  A grid may hold
+ * up to 2^35 cells (64-bit keys; PDM_E_TOOLARGE beyond, the size query returns 0); rows x columns must fit int32.
+ *
+ * pdm_hard_voxelize: points (N, C1) fp32 rows (batch_idx, x, y, z, ...); the rows of a sample contiguous, samples ascending.
+ *   cell = floor((v - v0) / size) in fp32 with an IEEE division on x, y and z; a row is dropped when a cell is out of range (NaN
+ *   drops, z is tested on a pillar grid too) or batch_idx is outside [0, B).  Per sample, cells are ranked by their first row;
+ *   a cell whose rank is below max_voxels is voxel `rank` of the sample and keeps its T smallest rows in ascending order; the
+ *   rows of the other cells are dropped.  Samples ascend in the output.  T = points per voxel, 1 <= T <=
+ *   pdm_hard_voxel_max_points() = 128, max_voxels >= 1 (PDM_E_BADARG otherwise).  Outputs at capacity cap = min(N, B max_voxels,
+ *   cells), only the first M voxels written: slot_rows (cap, T) input rows, -1 padding; voxel_coords (cap, 4) = (b, cz, cy, cx);
+ *   voxel_num_points (cap); voxels (cap, T, C1 - 1) or null (not written): bit copies of the rows past batch_idx, every padding
+ *   element zero.  record (2) = {M, unsorted}: unsorted = 1 when batch_idx[i] <= batch_idx[i + 1] fails for some i (a NaN
+ *   fails); then M = 0 and no output is valid.  workspace >= pdm_hard_voxelize_workspace_bytes, 8-byte aligned.  N = 0 is valid.
+ * pdm_hard_voxel_materialize: slot_rows (M, T) -> voxels (M, T, C1 - 1), every element written.
+ * pdm_hard_voxel_mean: out (M, C1 - 1) = the fp32 sum of the voxel's slots in slot order / max(num, 1), one IEEE division.
+ * pdm_hard_pillar_pfn: the reference's PillarVFE with one PFN layer in eval mode in one launch: columns [points[:, 1:] |
+ *   points[:, 4:], xyz - fp32 mean of the kept slots, xyz - cell centre on x, y and z (float(cell) * voxel + offset, product and
+ *   sum rounded separately), |xyz| if with_dist] -> weight (K, F <= 16) -> * scale + shift -> ReLU -> max over the slots; a
+ *   voxel with fewer than T points also takes relu(shift[k]), its padding rows' value: out (M, K). */
+/* align: any (4-byte accesses), except the workspace: 8 B (PDM_E_BADARG otherwise). */
+int pdm_hard_voxel_max_points(void);
+size_t pdm_hard_voxelize_workspace_bytes(int N, int B, int nx, int ny, int nz);
+int pdm_hard_voxelize(void *stream, int N, int C1, const float *points, int B, int nx, int ny, int nz, float x0, float y0, float z0,
+                      float vx, float vy, float vz, int T, int max_voxels, int *slot_rows, int *voxel_coords,
+                      int *voxel_num_points, float *voxels, int *record, void *workspace, size_t workspace_bytes);
+int pdm_hard_voxel_materialize(void *stream, int M, int T, int C1, const float *points, const int *slot_rows, float *voxels);
+int pdm_hard_voxel_mean(void *stream, int M, int T, int C1, const float *points, const int *slot_rows, const int *voxel_num_points,
+                        float *out);
+int pdm_hard_pillar_pfn(void *stream, int M, int K, int T, int C1, const float *points, const int *slot_rows,
+                        const int *voxel_num_points, const int *voxel_coords, int abs_xyz, int with_dist, float vx, float vy, float vz,
+                        float xoff, float yoff, float zoff, const float *weight, const float *scale, const float *shift, float *out);
+
 /* The anchor head (csrc/anchor_head.hip, DESIGN.md "Anchor head"): AxisAlignedTargetAssigner.assign_targets, the head's three
  * loss terms with their gradients, and generate_predicted_boxes, each for the whole batch on the caller's stream with no host
  * read and no float atomics on a result: two calls give the same bits.  Anchors are ordered y, x, slot (A = H W A_loc); a map

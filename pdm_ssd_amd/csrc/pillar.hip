@@ -8,14 +8,13 @@
 //   * xyz sums are 64-bit fixed point (llrint(x * 2^20)), added with integer atomics, which commute;
 //   * the rows of a pillar are listed in a CSR whose slot order is arbitrary (an integer atomic cursor): the only readers
 //     take a max with ties to the lower row, or an integer sum, neither of which depends on the order.
-#include "common.h"
+#include "pillar_feat.h"
 
 namespace pdm {
 
 constexpr int PL_T = 256;                  // threads per workgroup of every kernel here
 constexpr int PL_ITEMS = 8;                // scan items per thread
 constexpr int PL_TILE = PL_T * PL_ITEMS;   // scan items per workgroup
-constexpr int PL_MAXF = 16;                // input columns of the fused PFN layer (the reference's is 10 or 11 wide)
 constexpr double PL_FIX = 1048576.0;       // 2^20: one step of the fixed-point sums is about a micrometre
 
 struct PlGrid {
@@ -152,26 +151,7 @@ __global__ __launch_bounds__(PL_T) void pl_mean_kernel(const int *__restrict__ r
 }
 
 // ---- b. features ----------------------------------------------------------------------------------------------------
-struct PlFeat {
-    int C1, abs_xyz, with_dist, F;
-    float vx, vy, xoff, yoff, zoff;
-};
-
-// The derived columns of one kept row, after its raw ones (points[:, 1:] or points[:, 4:]): f_cluster = xyz - pillar mean,
-// f_center = xyz - cell centre as the reference orders it, x - (float(cx) * vx + x_offset) with the product and the sum
-// rounded separately, and |xyz| = sqrt(fma(z, z, fma(y, y, x * x))), what torch.norm's CPU kernel rounds to (0 without it).
-__device__ __forceinline__ void pl_derived(const PlFeat &a, const float *__restrict__ p, const float *__restrict__ mean,
-                                           const int *__restrict__ vc, float d[7]) {
-    const float x = p[1], y = p[2], z = p[3];
-    d[0] = __fsub_rn(x, mean[0]);
-    d[1] = __fsub_rn(y, mean[1]);
-    d[2] = __fsub_rn(z, mean[2]);
-    d[3] = __fsub_rn(x, __fadd_rn(__fmul_rn((float)vc[3], a.vx), a.xoff));
-    d[4] = __fsub_rn(y, __fadd_rn(__fmul_rn((float)vc[2], a.vy), a.yoff));
-    d[5] = __fsub_rn(z, a.zoff);
-    d[6] = a.with_dist ? sqrtf(sqdist(x, y, z)) : 0.0f;      // sqrtf is correctly rounded here; __fsqrt_rn is the 1-ulp native one
-}
-
+// PlFeat, pl_derived and the PFN channel: pillar_feat.h (shared with hard_voxel.hip)
 __global__ __launch_bounds__(PL_T) void pl_features_kernel(int n_kept, PlFeat a, const float *__restrict__ points, const int *__restrict__ kept_idx,
                                                            const int *__restrict__ unq_inv, const int *__restrict__ voxel_coords,
                                                            const float *__restrict__ pillar_mean, float *__restrict__ out) {
@@ -229,29 +209,13 @@ __global__ __launch_bounds__(PL_T) void pl_fused_pfn_kernel(long long total, int
     const long long t = (long long)blockIdx.x * PL_T + threadIdx.x;
     if (t >= total) return;
     const int p = (int)(t / K), k = (int)(t % K);
-    // the channel's weights in registers under static indices: the raw columns' and the seven derived columns' (0 for an
-    // absent |xyz|)
-    const int first = a.abs_xyz ? 1 : 4, nraw = a.C1 - first;
-    float w_raw[PL_MAXF - 6], w_der[7];
-#pragma unroll
-    for (int c = 0; c < PL_MAXF - 6; ++c) w_raw[c] = c < nraw ? weight[(size_t)k * a.F + c] : 0.0f;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) w_der[j] = (j < 6 || a.with_dist) ? weight[(size_t)k * a.F + nraw + j] : 0.0f;
-    const float sc = scale[k], sh = shift[k];
+    PlChannel w;
+    pl_channel_load(a, k, weight, scale, shift, w);
     const float *mean = pillar_mean + (size_t)p * 3;
     const int *vc = voxel_coords + (size_t)p * 4;
     float best = 0.0f;                     // after the ReLU nothing is below zero, and no pillar is empty
     for (int s = seg_start[p]; s < seg_start[p + 1]; ++s) {
-        const float *row = points + (size_t)kept_idx[seg_rows[s]] * a.C1;
-        float d[7];
-        pl_derived(a, row, mean, vc, d);
-        float acc = 0.0f;
-#pragma unroll
-        for (int c = 0; c < PL_MAXF - 6; ++c)
-            if (c < nraw) acc = __fmaf_rn(row[first + c], w_raw[c], acc);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) acc = __fmaf_rn(d[j], w_der[j], acc);
-        const float y = fmaxf(__fmaf_rn(acc, sc, sh), 0.0f);
+        const float y = pl_channel_row(a, w, points + (size_t)kept_idx[seg_rows[s]] * a.C1, mean, vc);
         best = (y > best || y != y) ? y : best;        // a NaN stays, as torch's amax keeps it
     }
     out[t] = best;
@@ -340,12 +304,6 @@ static int pl_check_grid(const char *who, long long N, int C1, int B, int nx, in
     PDM_REQUIRE(N >= 0 && B >= 0 && nx >= 1 && ny >= 1 && C1 >= 4, PDM_E_BADARG, "%s: bad size", who);
     PDM_REQUIRE((long long)B * nx * ny <= 0x7fffffffll, PDM_E_TOOLARGE, "%s: %lld cells exceed int32", who, (long long)B * nx * ny);
     PDM_REQUIRE(N * C1 <= 0x7fffffffll, PDM_E_TOOLARGE, "%s: %lld point elements exceed int32", who, N * C1);
-    return 0;
-}
-
-static int pl_feat_args(const char *who, PlFeat *a, int C1, int abs_xyz, int with_dist, float vx, float vy, float xoff, float yoff, float zoff) {
-    PDM_REQUIRE(C1 >= 4, PDM_E_BADARG, "%s: rows are (batch_idx, x, y, z, ...)", who);
-    *a = PlFeat{C1, abs_xyz != 0, with_dist != 0, (abs_xyz ? C1 - 1 : C1 - 4) + 6 + (with_dist ? 1 : 0), vx, vy, xoff, yoff, zoff};
     return 0;
 }
 

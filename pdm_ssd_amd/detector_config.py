@@ -154,6 +154,16 @@ SECOND_CFG = {
 for _anchor_cfg in SECOND_CFG['DENSE_HEAD']['ANCHOR_GENERATOR_CONFIG']:
     _anchor_cfg['feature_map_stride'] = 8
 
+# The same two detectors on HARD voxels, what the upstream project's published KITTI models were trained on: at most
+# MAX_POINTS_PER_VOXEL points a cell and MAX_NUMBER_OF_VOXELS cells a sample (its transform_points_to_voxels values: 32 and 5
+# points, 16000 / 40000 voxels), voxelized on the device by the encoder itself.  Every other detector on SECOND_CFG's or
+# POINT_PILLAR_CFG's front end takes the same one-line change of its VFE entry.
+HARD_MAX_NUMBER_OF_VOXELS = {'train': 16000, 'test': 40000}
+POINT_PILLAR_HARD_CFG = copy.deepcopy(POINT_PILLAR_CFG)
+POINT_PILLAR_HARD_CFG['VFE'].update(NAME='HardPillarVFE', MAX_POINTS_PER_VOXEL=32, MAX_NUMBER_OF_VOXELS=dict(HARD_MAX_NUMBER_OF_VOXELS))
+SECOND_HARD_CFG = copy.deepcopy(SECOND_CFG)
+SECOND_HARD_CFG['VFE'].update(NAME='HardMeanVFE', MAX_POINTS_PER_VOXEL=5, MAX_NUMBER_OF_VOXELS=dict(HARD_MAX_NUMBER_OF_VOXELS))
+
 # CenterPoint on voxels: SECOND_CFG's front with the residual backbone, then CenterHead at FEATURE_MAP_STRIDE 8 (the head of
 # CENTER_PDM_CFG, whose map has the same 200 x 176 cells).
 CENTER_VOXEL_CFG = {
@@ -361,7 +371,8 @@ def build_center_pillar(model_cfg=None, num_point_features=4, dataset=None):
 
 def build_point_pillar(model_cfg=None, num_point_features=4, dataset=None):
     """PointPillar from POINT_PILLAR_CFG (or a dict like it): DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone ->
-    AnchorHeadSingle, on pillar_dataset() unless another dataset namespace is given."""
+    AnchorHeadSingle, on pillar_dataset() unless another dataset namespace is given.  POINT_PILLAR_HARD_CFG puts HardPillarVFE
+    (hard voxels) in front instead."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(POINT_PILLAR_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillar_dataset(num_point_features) if dataset is None else dataset)
@@ -377,7 +388,8 @@ def voxel_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None,
 
 def build_second(model_cfg=None, num_point_features=4, dataset=None):
     """SECONDNet from SECOND_CFG (or a dict like it): DynamicMeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone ->
-    AnchorHeadSingle, on voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and takes training steps."""
+    AnchorHeadSingle, on voxel_dataset() unless another dataset namespace is given.  Runs in eval mode and takes training steps.
+    SECOND_HARD_CFG puts HardMeanVFE (hard voxels) in front instead."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(SECOND_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)

@@ -6,8 +6,9 @@ Contract restated from /root/reference/pcdet/models/detectors/detector3d_templat
 checkpoint loading).  The reference's template cannot be imported on this platform (it pulls in spconv,
 pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2d slots build the pillar family
 (DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and the voxel family (DynamicMeanVFE ->
-VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution; a NAME
-outside the registries (MeanVFE, PillarVFE, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction or PV-RCNN++'s
+VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution, each also
+on hard voxels (HardPillarVFE / HardMeanVFE, which voxelize on the device with the two sizes of their own config); a NAME outside
+the registries (the plain MeanVFE and PillarVFE among them, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction or PV-RCNN++'s
 VoxelSetAbstractionSPC, the roi_head slot the RoI heads of roi_heads/ (PointRCNN's second stage, Voxel R-CNN's, PV-RCNN's in eval
 mode).
 """

@@ -1209,6 +1209,31 @@ size_t pdm_sparse_conv_wgrad_workspace_bytes(int P_out, int kvol, int Cin, int C
 int pdm_sparse_conv_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
                           const int *nbr, float *dw, void *workspace, size_t workspace_bytes);
 
+/* The sparse convolution and its weight gradient up to 256 channels (csrc/sparse_conv_mfma.hip, csrc/sparse_conv_wgrad.hip,
+ * DESIGN.md 7zb): what a sparse 2-D pillar backbone's 128 -> 256 and 256 -> 256 layers run.  Arguments, checks, epilogue,
+ * alignment and determinism as the narrow counterparts; Cin in {3..8, 16, 32, 64, 128, 256}, Cout in {16, 32, 64, 128, 256}
+ * (PDM_E_BADARG otherwise, before any launch).  The narrow entries keep refusing 256.
+ * pdm_sparse_conv_wide, pdm_sparse_conv_wide_split: pdm_sparse_conv, pdm_sparse_conv_split.  wpack as there
+ *   (pdm_sparse_conv_packed_floats covers 256).  One accumulator chain per output element over the present offsets k ascending
+ *   and the 16-channel blocks kb ascending, whatever the blocking of the output columns: for Cin, Cout <= 128 the narrow
+ *   entries' bits; columns [0, 128) and [128, 256) of a Cout = 256 run are the bits of two Cout = 128 runs on the weight's halves.
+ *   The data gradient is pdm_sparse_conv_wide_split with the channels swapped, as in the narrow form.
+ * pdm_sparse_conv_wide_wgrad: pdm_sparse_conv_wgrad.  A 256-wide side runs as two 128-wide sub-blocks, each on its columns of
+ *   dy and x; every element of every (Cout, Cin padded to 16) partial has one writer, phase two adds the chunks in ascending
+ *   order.  pdm_sparse_conv_wide_wgrad_chunk_rows and pdm_sparse_conv_wide_wgrad_workspace_bytes: the narrow rule over the wide
+ *   channel sets, a function of (P_out, kvol, Cin, Cout) alone (0 for sizes the operator rejects); for Cin, Cout <= 128 the
+ *   narrow entry's chunks and bits. */
+/* align: any (4-byte accesses, 16-byte ones only where the pointer allows), except the workspace: 8 B and wpack: 16 B
+ * (PDM_E_BADARG otherwise). */
+int pdm_sparse_conv_wide(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+                         const float *scale, const float *shift, const float *residual, int relu, float *out);
+int pdm_sparse_conv_wide_split(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr,
+                               const float *wpack, const float *scale, const float *shift, const float *residual, int relu, float *out);
+int pdm_sparse_conv_wide_wgrad_chunk_rows(int P_out, int kvol, int Cin, int Cout);
+size_t pdm_sparse_conv_wide_wgrad_workspace_bytes(int P_out, int kvol, int Cin, int Cout);
+int pdm_sparse_conv_wide_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
+                               const int *nbr, float *dw, void *workspace, size_t workspace_bytes);
+
 /* Voxel R-CNN's RoI-grid pooling (csrc/sparse_conv.hip, csrc/roi_grid_pool.hip).
  * pdm_sparse_index: indices (P, 4) int32 rows (b, z, y, x), distinct sites in any row order on the grid (B, D, H, W) -> the
  *   level's site index in `workspace` (>= pdm_sparse_index_workspace_bytes, 8-byte aligned): occupancy bitmap, group prefixes

@@ -1,6 +1,7 @@
 """2-D backbones, registered by NAME as the reference's pcdet/models/backbones_2d/__init__.py does."""
-from .base_bev_backbone import BaseBEVBackbone
+from .base_bev_backbone import BaseBEVBackbone, BaseBEVBackboneV1
 
 __all__ = {
     'BaseBEVBackbone': BaseBEVBackbone,
+    'BaseBEVBackboneV1': BaseBEVBackboneV1,
 }

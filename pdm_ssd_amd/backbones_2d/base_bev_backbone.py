@@ -1,6 +1,9 @@
 """BaseBEVBackbone of the reference's pcdet/models/backbones_2d/base_bev_backbone.py, restated: plain torch
 convolutions (MIOpen on the GPU), the same config keys and state_dict keys (blocks.{i}.{j}.*, deblocks.{i}.{j}.*).
-The reference's `np.round(1 / stride).astype(np.int)` (np.int no longer exists) is int(round(1 / stride))."""
+The reference's `np.round(1 / stride).astype(np.int)` (np.int no longer exists) is int(round(1 / stride)).
+
+BaseBEVBackboneV1 is the 2-D backbone of the sparse pillar family (PillarNet): it reads the dense x_conv4 and x_conv5 maps a sparse
+2-D backbone left in multi_scale_2d_features, not spatial_features."""
 import torch
 import torch.nn as nn
 
@@ -72,4 +75,50 @@ class BaseBEVBackbone(nn.Module):
         if len(self.deblocks) > len(self.blocks):
             x = self.deblocks[-1](x)
         data_dict['spatial_features_2d'] = x
+        return data_dict
+
+
+class BaseBEVBackboneV1(nn.Module):
+    def __init__(self, model_cfg, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        layer_nums, num_filters = list(_get(model_cfg, 'LAYER_NUMS')), list(_get(model_cfg, 'NUM_FILTERS'))
+        assert len(layer_nums) == len(num_filters) == 2
+        num_upsample_filters, upsample_strides = list(_get(model_cfg, 'NUM_UPSAMPLE_FILTERS')), list(_get(model_cfg, 'UPSAMPLE_STRIDES'))
+        assert len(num_upsample_filters) == len(upsample_strides)
+
+        def bn(c):
+            return nn.BatchNorm2d(c, eps=1e-3, momentum=0.01)
+
+        num_levels = len(layer_nums)
+        self.blocks = nn.ModuleList()
+        self.deblocks = nn.ModuleList()
+        for idx in range(num_levels):
+            cur_layers = [nn.ZeroPad2d(1), nn.Conv2d(num_filters[idx], num_filters[idx], kernel_size=3, stride=1, padding=0, bias=False),
+                          bn(num_filters[idx]), nn.ReLU()]
+            for _ in range(layer_nums[idx]):
+                cur_layers.extend([nn.Conv2d(num_filters[idx], num_filters[idx], kernel_size=3, padding=1, bias=False),
+                                   bn(num_filters[idx]), nn.ReLU()])
+            self.blocks.append(nn.Sequential(*cur_layers))
+            if len(upsample_strides) > 0:
+                stride = upsample_strides[idx]
+                if stride >= 1:
+                    up = nn.ConvTranspose2d(num_filters[idx], num_upsample_filters[idx], stride, stride=stride, bias=False)
+                else:
+                    stride = int(round(1 / stride))
+                    up = nn.Conv2d(num_filters[idx], num_upsample_filters[idx], stride, stride=stride, bias=False)
+                self.deblocks.append(nn.Sequential(up, bn(num_upsample_filters[idx]), nn.ReLU()))
+        c_in = sum(num_upsample_filters)
+        if len(upsample_strides) > num_levels:
+            self.deblocks.append(nn.Sequential(
+                nn.ConvTranspose2d(c_in, c_in, upsample_strides[-1], stride=upsample_strides[-1], bias=False), bn(c_in), nn.ReLU()))
+        self.num_bev_features = c_in
+
+    def forward(self, data_dict):
+        """multi_scale_2d_features['x_conv4'] (B, C4, H, W) and ['x_conv5'] (B, C5, H / 2, W / 2), both dense ->
+        spatial_features_2d: blocks[0] over the concatenation of deblocks[0](x_conv4) and deblocks[1](blocks[1](x_conv5))"""
+        feats = data_dict['multi_scale_2d_features']
+        ups = [self.deblocks[0](feats['x_conv4'])]
+        ups.append(self.deblocks[1](self.blocks[1](feats['x_conv5'])))
+        data_dict['spatial_features_2d'] = self.blocks[0](torch.cat(ups, dim=1))
         return data_dict

@@ -9,6 +9,11 @@
 // SPLIT (pdm_sparse_conv_split, the training path's forward and data gradient): every offset's products are added
 // in an accumulator of their own, which is then added to the running sum: the order of `per offset mm, then add`, whose rounding
 // error is about a third of one long chain's.  The same operands, the same skip, no atomics; other bits than the plain form.
+// WIDE (pdm_sparse_conv_wide, pdm_sparse_conv_wide_split): the same kernel with 256 channels admitted.  Cin = 256 is
+// 16 blocks kb instead of 8; Cout = 256 is the NB = 16 instantiation, 16 accumulator blocks a lane over ONE gather of the rows
+// (48 KB of weight and row stages instead of 32).  An output element's chain (k ascending, kb ascending, four MFMA steps a block)
+// does not depend on how the output columns are blocked, so for Cin, Cout <= 128 the wide entries run the narrow instantiations
+// and give the narrow entries' bits.
 #include "common.h"
 
 namespace pdm {
@@ -198,13 +203,20 @@ extern "C" size_t pdm_sparse_conv_packed_floats(int kvol, int Cin, int Cout) {
 // x (P_in, Cin), nbr (P_out, kvol) input rows or -1 (an entry outside [0, P_in) counts as -1), wpack as above (16-byte
 // aligned) -> out (P_out, Cout).  scale and shift come together or not at all; residual (P_out, Cout) or null.
 template <bool SPLIT>
-static int scv_run(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
+static int scv_run(bool wide, void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
                    const float *scale, const float *shift, const float *residual, int relu, float *out) {
     PDM_REQUIRE(P_out >= 0 && P_in >= 0, PDM_E_BADARG, "sparse_conv: bad size");
     PDM_REQUIRE(kvol >= 1 && kvol <= SCV_MAXK, PDM_E_BADARG, "sparse_conv: %d offsets, at most %d", kvol, SCV_MAXK);
-    PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128, PDM_E_BADARG,
-                "sparse_conv: %d input channels (3 to 8, 16, 32, 64 or 128)", Cin);
-    PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128, PDM_E_BADARG, "sparse_conv: %d output channels (16, 32, 64 or 128)", Cout);
+    if (wide) {
+        PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256, PDM_E_BADARG,
+                    "sparse_conv_wide: %d input channels (3 to 8, 16, 32, 64, 128 or 256)", Cin);
+        PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256, PDM_E_BADARG,
+                    "sparse_conv_wide: %d output channels (16, 32, 64, 128 or 256)", Cout);
+    } else {
+        PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128, PDM_E_BADARG,
+                    "sparse_conv: %d input channels (3 to 8, 16, 32, 64 or 128)", Cin);
+        PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128, PDM_E_BADARG, "sparse_conv: %d output channels (16, 32, 64 or 128)", Cout);
+    }
     PDM_REQUIRE((long long)P_out * kvol <= 0x7fffffffll, PDM_E_TOOLARGE, "sparse_conv: %d rows x %d offsets exceed int32", P_out, kvol);
     PDM_REQUIRE((scale == nullptr) == (shift == nullptr), PDM_E_BADARG, "sparse_conv: scale and shift come together");
     if (P_out == 0) return 0;
@@ -217,19 +229,33 @@ static int scv_run(void *stream, int P_out, int P_in, int kvol, int Cin, int Cou
         case 1: hipLaunchKernelGGL((sparse_conv_kernel<1, SPLIT>), grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((sparse_conv_kernel<2, SPLIT>), grid, block, 0, s, a); break;
         case 4: hipLaunchKernelGGL((sparse_conv_kernel<4, SPLIT>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((sparse_conv_kernel<8, SPLIT>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((sparse_conv_kernel<8, SPLIT>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((sparse_conv_kernel<16, SPLIT>), grid, block, 0, s, a); break;
     }
     return check_launch("sparse_conv");
 }
 
 extern "C" int pdm_sparse_conv(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr, const float *wpack,
                                const float *scale, const float *shift, const float *residual, int relu, float *out) {
-    return scv_run<false>(stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
+    return scv_run<false>(false, stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
 }
 
 // pdm_sparse_conv with one accumulator per offset added to a running sum (the SPLIT form above): what the training path runs in
 // its forward and its data gradient.  Same arguments, same checks, as deterministic; not the same bits as pdm_sparse_conv.
 extern "C" int pdm_sparse_conv_split(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr,
                                      const float *wpack, const float *scale, const float *shift, const float *residual, int relu, float *out) {
-    return scv_run<true>(stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
+    return scv_run<true>(false, stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
+}
+
+// pdm_sparse_conv and pdm_sparse_conv_split with Cin and Cout up to 256 (the WIDE note above): the same arguments, checks, chain and
+// epilogue; for Cin, Cout <= 128 the same launches, so the same bits.
+extern "C" int pdm_sparse_conv_wide(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr,
+                                    const float *wpack, const float *scale, const float *shift, const float *residual, int relu, float *out) {
+    return scv_run<false>(true, stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
+}
+
+extern "C" int pdm_sparse_conv_wide_split(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *x, const int *nbr,
+                                          const float *wpack, const float *scale, const float *shift, const float *residual, int relu,
+                                          float *out) {
+    return scv_run<true>(true, stream, P_out, P_in, kvol, Cin, Cout, x, nbr, wpack, scale, shift, residual, relu, out);
 }

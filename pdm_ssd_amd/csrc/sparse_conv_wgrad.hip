@@ -9,6 +9,11 @@
 //   2. one launch sums the chunks in ascending order and writes (Cout, kvol, Cin) fp32, the layout of weight.grad.
 // The chunk boundaries are a function of (P_out, kvol, Cin, Cout) alone (scw_chunk_rows), never of the device: two runs and
 // a graph replay give the same bits.
+// WIDE (pdm_sparse_conv_wide_wgrad): Cin or Cout = 256 does not fit the one-workgroup-holds-all-blocks layout (the
+// 128 x 128 tile already fills LDS).  The (Cout, Cin) block runs as sub-blocks of at most 128 x 128 on a third grid dimension,
+// z = (Cout sub-block) * (Cin sub-blocks) + (Cin sub-block): a sub-block reads its 128 columns of dy and of x at a column offset
+// with the full row strides and writes its corner of the same [chunk][k][Cout][Cin] partial.  Every partial element has one
+// writer and the same chain over the rows as a narrow run on those columns; phase two is unchanged.
 #include "common.h"
 
 namespace pdm {
@@ -33,6 +38,9 @@ static int scw_cin_pad(int cin) { return cin < 16 ? 16 : cin; }
 static bool scw_widths_ok(int cin, int cout) {
     return ((cin >= 3 && cin <= 8) || cin == 16 || cin == 32 || cin == 64 || cin == 128) && (cout == 16 || cout == 32 || cout == 64 || cout == 128);
 }
+static bool scw_widths_ok_wide(int cin, int cout) {
+    return (cin == 256 || cout == 256) ? scw_widths_ok(cin == 256 ? 128 : cin, cout == 256 ? 128 : cout) : scw_widths_ok(cin, cout);
+}
 static size_t scw_partial_bytes(int kvol, int cin, int cout) { return sizeof(float) * (size_t)kvol * (size_t)cout * (size_t)scw_cin_pad(cin); }
 // rows of a chunk: a multiple of 64, at least SCW_MIN_CHUNK, and large enough that the partials stay under both caps
 static int scw_chunk_rows(int P_out, int kvol, int cin, int cout) {
@@ -47,7 +55,7 @@ static int scw_chunk_rows(int P_out, int kvol, int cin, int cout) {
 // ds_read_b32 (16 lanes each) fall on disjoint banks
 constexpr int scw_stride(int c) { return c % 32 == 0 ? c + 16 : c; }
 
-template <int CB, int IB>
+template <int CB, int IB, bool WIDE>
 __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
     constexpr int ROWS = (CB + IB == 16) ? 32 : 64;         // 128 x 128: two 64-row tiles would not fit 64 KB
     constexpr int SD = scw_stride(16 * CB), SX = scw_stride(16 * IB);
@@ -62,6 +70,10 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pos = lane & 15, g = lane >> 4;
     const int chunk = blockIdx.x, k = blockIdx.y;
+    // WIDE: this workgroup's sub-block of (16 CB, 16 IB) channels and the partial's row stride (the whole padded Cin)
+    const int nsub_i = WIDE && a.cin > 16 * IB ? a.cin / (16 * IB) : 1;
+    const int co0 = WIDE ? ((int)blockIdx.z / nsub_i) * (16 * CB) : 0, ci0 = WIDE ? ((int)blockIdx.z % nsub_i) * (16 * IB) : 0;
+    const int pstride = WIDE ? nsub_i * (16 * IB) : 16 * IB;
     const long long c0 = (long long)chunk * a.chunk_rows;
     const long long c1 = min(c0 + (long long)a.chunk_rows, (long long)a.P_out);
     const bool active = wave < WC * WI;
@@ -89,7 +101,7 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
             const int row = q / (4 * CB), c = 4 * (q % (4 * CB));
             wf4 v = {0.f, 0.f, 0.f, 0.f};
             if (row < live) {
-                const float *p = a.dy + (size_t)(r0 + row) * a.cout + c;
+                const float *p = a.dy + (size_t)(r0 + row) * a.cout + co0 + c;
                 if (vec_dy) {
                     v = *reinterpret_cast<const wf4 *>(p);
                 } else {
@@ -103,14 +115,14 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
             wf4 v = {0.f, 0.f, 0.f, 0.f};
             const int rr = s_nbr[row];
             if (rr >= 0) {
-                const float *p = a.x + (size_t)rr * a.cin + c;
-                if (vec_x && c + 4 <= a.cin) {
+                const float *p = a.x + (size_t)rr * a.cin + ci0 + c;
+                if (vec_x && ci0 + c + 4 <= a.cin) {
                     v = *reinterpret_cast<const wf4 *>(p);
                 } else {
-                    if (c < a.cin) v.x = p[0];
-                    if (c + 1 < a.cin) v.y = p[1];
-                    if (c + 2 < a.cin) v.z = p[2];
-                    if (c + 3 < a.cin) v.w = p[3];
+                    if (ci0 + c < a.cin) v.x = p[0];
+                    if (ci0 + c + 1 < a.cin) v.y = p[1];
+                    if (ci0 + c + 2 < a.cin) v.z = p[2];
+                    if (ci0 + c + 3 < a.cin) v.w = p[3];
                 }
             }
             *reinterpret_cast<wf4 *>(&s_x[row * SX + c]) = v;
@@ -136,14 +148,14 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
     // lane (pos, g), register j of block (c, i) = dW[co = 16 (cb0 + c) + 4 g + j][ci = 16 (ib0 + i) + pos]; written even when every
     // tile was skipped: phase two reads every partial
     if (!active) return;
-    float *dst = a.part + ((size_t)chunk * a.kvol + k) * (size_t)a.cout * (16 * IB);
+    float *dst = a.part + (((size_t)chunk * a.kvol + k) * (size_t)a.cout + co0) * pstride + ci0;
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
 #pragma unroll
         for (int i = 0; i < NIB; ++i) {
             const float v[4] = {acc[c][i].x, acc[c][i].y, acc[c][i].z, acc[c][i].w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(size_t)(16 * (cb0 + c) + 4 * g + j) * (16 * IB) + 16 * (ib0 + i) + pos] = v[j];
+            for (int j = 0; j < 4; ++j) dst[(size_t)(16 * (cb0 + c) + 4 * g + j) * pstride + 16 * (ib0 + i) + pos] = v[j];
         }
 }
 
@@ -161,10 +173,21 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_reduce_kernel(int nch
 template <int CB>
 static void scw_launch(int ib, dim3 grid, hipStream_t s, const ScwArgs &a) {
     switch (ib) {
-        case 1: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 1>), grid, dim3(SCW_T), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 2>), grid, dim3(SCW_T), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 4>), grid, dim3(SCW_T), 0, s, a); break;
-        default: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 8>), grid, dim3(SCW_T), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 1, false>), grid, dim3(SCW_T), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 2, false>), grid, dim3(SCW_T), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 4, false>), grid, dim3(SCW_T), 0, s, a); break;
+        default: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 8, false>), grid, dim3(SCW_T), 0, s, a); break;
+    }
+}
+
+// a 256-wide side runs as two sub-blocks of 8 blocks; the other side keeps its own block count
+template <int CB>
+static void scw_launch_wide(int ib, dim3 grid, hipStream_t s, const ScwArgs &a) {
+    switch (ib) {
+        case 1: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 1, true>), grid, dim3(SCW_T), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 2, true>), grid, dim3(SCW_T), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 4, true>), grid, dim3(SCW_T), 0, s, a); break;
+        default: hipLaunchKernelGGL((sparse_conv_wgrad_kernel<CB, 8, true>), grid, dim3(SCW_T), 0, s, a); break;
     }
 }
 
@@ -187,14 +210,21 @@ extern "C" size_t pdm_sparse_conv_wgrad_workspace_bytes(int P_out, int kvol, int
 
 // dy (P_out, Cout), x (P_in, Cin), nbr (P_out, kvol) input rows or -1 (an entry outside [0, P_in) counts as -1) ->
 // dw (Cout, kvol, Cin) fp32, every element written (zeros for P_out == 0).
-extern "C" int pdm_sparse_conv_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
-                                     const int *nbr, float *dw, void *workspace, size_t workspace_bytes) {
+static int scw_run(bool wide, void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x, const int *nbr,
+                   float *dw, void *workspace, size_t workspace_bytes) {
     PDM_REQUIRE(P_out >= 0 && P_in >= 0, PDM_E_BADARG, "sparse_conv_wgrad: bad size");
     PDM_REQUIRE(kvol >= 1 && kvol <= SCW_MAXK, PDM_E_BADARG, "sparse_conv_wgrad: %d offsets, at most %d", kvol, SCW_MAXK);
-    PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128, PDM_E_BADARG,
-                "sparse_conv_wgrad: %d input channels (3 to 8, 16, 32, 64 or 128)", Cin);
-    PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128, PDM_E_BADARG, "sparse_conv_wgrad: %d output channels (16, 32, 64 or 128)",
-                Cout);
+    if (wide) {
+        PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256, PDM_E_BADARG,
+                    "sparse_conv_wide_wgrad: %d input channels (3 to 8, 16, 32, 64, 128 or 256)", Cin);
+        PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256, PDM_E_BADARG,
+                    "sparse_conv_wide_wgrad: %d output channels (16, 32, 64, 128 or 256)", Cout);
+    } else {
+        PDM_REQUIRE((Cin >= 3 && Cin <= 8) || Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128, PDM_E_BADARG,
+                    "sparse_conv_wgrad: %d input channels (3 to 8, 16, 32, 64 or 128)", Cin);
+        PDM_REQUIRE(Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128, PDM_E_BADARG, "sparse_conv_wgrad: %d output channels (16, 32, 64 or 128)",
+                    Cout);
+    }
     PDM_REQUIRE((long long)P_out * kvol <= 0x7fffffffll, PDM_E_TOOLARGE, "sparse_conv_wgrad: %d rows x %d offsets exceed int32", P_out, kvol);
     PDM_REQUIRE(dw && workspace && (P_out == 0 || (dy && nbr)) && (P_out == 0 || P_in == 0 || x), PDM_E_BADARG, "sparse_conv_wgrad: null pointer");
     PDM_WS_ALIGNED("sparse_conv_wgrad", workspace);
@@ -206,16 +236,50 @@ extern "C" int pdm_sparse_conv_wgrad(void *stream, int P_out, int P_in, int kvol
     const int cin_pad = scw_cin_pad(Cin);
     if (nchunks) {
         const ScwArgs a{P_out, P_in, kvol, Cin, Cout, chunk_rows, dy, x, nbr, part};
-        const dim3 grid((unsigned)nchunks, (unsigned)kvol);
-        switch (Cout / 16) {
-            case 1: scw_launch<1>(cin_pad / 16, grid, s, a); break;
-            case 2: scw_launch<2>(cin_pad / 16, grid, s, a); break;
-            case 4: scw_launch<4>(cin_pad / 16, grid, s, a); break;
-            default: scw_launch<8>(cin_pad / 16, grid, s, a); break;
+        if (Cin <= 128 && Cout <= 128) {        // the narrow launch, also under the wide entry: the same bits
+            const dim3 grid((unsigned)nchunks, (unsigned)kvol);
+            switch (Cout / 16) {
+                case 1: scw_launch<1>(cin_pad / 16, grid, s, a); break;
+                case 2: scw_launch<2>(cin_pad / 16, grid, s, a); break;
+                case 4: scw_launch<4>(cin_pad / 16, grid, s, a); break;
+                default: scw_launch<8>(cin_pad / 16, grid, s, a); break;
+            }
+        } else {
+            const int cb = (Cout > 128 ? 128 : Cout) / 16, ib = (cin_pad > 128 ? 128 : cin_pad) / 16;
+            const dim3 grid((unsigned)nchunks, (unsigned)kvol, (unsigned)((Cout / (16 * cb)) * (cin_pad / (16 * ib))));
+            switch (cb) {
+                case 1: scw_launch_wide<1>(ib, grid, s, a); break;
+                case 2: scw_launch_wide<2>(ib, grid, s, a); break;
+                case 4: scw_launch_wide<4>(ib, grid, s, a); break;
+                default: scw_launch_wide<8>(ib, grid, s, a); break;
+            }
         }
         if (int rc = check_launch("sparse_conv_wgrad(partials)")) return rc;
     }
     hipLaunchKernelGGL(sparse_conv_wgrad_reduce_kernel, dim3((unsigned)divup((long long)Cout * kvol * Cin, SCW_T)), dim3(SCW_T), 0, s, nchunks, kvol, Cin,
                        cin_pad, Cout, part, dw);
     return check_launch("sparse_conv_wgrad(sum)");
+}
+
+extern "C" int pdm_sparse_conv_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
+                                     const int *nbr, float *dw, void *workspace, size_t workspace_bytes) {
+    return scw_run(false, stream, P_out, P_in, kvol, Cin, Cout, dy, x, nbr, dw, workspace, workspace_bytes);
+}
+
+// pdm_sparse_conv_wgrad and its two queries with Cin and Cout up to 256 (the WIDE note above).  The chunk rule is the narrow
+// one, so for Cin, Cout <= 128 the launches and the bits are the narrow entry's.
+extern "C" int pdm_sparse_conv_wide_wgrad_chunk_rows(int P_out, int kvol, int Cin, int Cout) {
+    if (P_out < 0 || kvol < 1 || kvol > SCW_MAXK || !scw_widths_ok_wide(Cin, Cout)) return 0;
+    return scw_chunk_rows(P_out, kvol, Cin, Cout);
+}
+
+extern "C" size_t pdm_sparse_conv_wide_wgrad_workspace_bytes(int P_out, int kvol, int Cin, int Cout) {
+    if (P_out < 0 || kvol < 1 || kvol > SCW_MAXK || !scw_widths_ok_wide(Cin, Cout)) return 0;
+    const int nchunks = divup(P_out, scw_chunk_rows(P_out, kvol, Cin, Cout));
+    return align256(scw_partial_bytes(kvol, Cin, Cout) * (size_t)(nchunks < 1 ? 1 : nchunks));
+}
+
+extern "C" int pdm_sparse_conv_wide_wgrad(void *stream, int P_out, int P_in, int kvol, int Cin, int Cout, const float *dy, const float *x,
+                                          const int *nbr, float *dw, void *workspace, size_t workspace_bytes) {
+    return scw_run(true, stream, P_out, P_in, kvol, Cin, Cout, dy, x, nbr, dw, workspace, workspace_bytes);
 }

@@ -324,6 +324,30 @@ PV_RCNN_PP_CFG['PFE'] = {
 PV_RCNN_PP_CFG['ROI_HEAD']['ROI_GRID_POOL'] = dict(
     _vector_pool('voxel_random_choice', 30, 128, ([3, 3, 3], [3, 3, 3]), (0.8, 1.6), 32, [64, 64]), GRID_SIZE=6)
 
+# PillarNet: DynamicPillarVFESimple2D -> PillarBackBone8x -> BaseBEVBackboneV1 -> CenterHead.  The snapshot this repository was
+# modelled on holds no YAML for this detector, so the values are BUILD-DEFINED and were not checked against any file: the KITTI
+# voxel range with pillars of 0.05 x 0.05 x 4 m (grid 1408 x 1600 x 1), one PFN layer of 32 filters, the sparse 2-D backbone's
+# 256-channel x_conv4 (stride 8, 200 x 176 cells) and x_conv5 (stride 16) through five 256-wide convolutions each and up to two
+# 128-channel maps, and CENTER_PDM_CFG's CenterHead at FEATURE_MAP_STRIDE 8 with batched post-processing.  The reference's head for
+# this detector also predicts an IoU (an `iou` head, IOU_REG_LOSS, USE_IOU_TO_RECTIFY_SCORE), which CenterHead here refuses: it is
+# not part of this build.  PILLARNET_TRAIN_CFG is the same dict: CenterHead carries its training half, so
+# build_pillarnet(PILLARNET_TRAIN_CFG) takes training steps; the name marks the intent, as the other *_TRAIN_CFG dicts do.
+PILLARNET_RANGE = [0, -40, -3, 70.4, 40, 1]
+PILLARNET_VOXEL_SIZE = [0.05, 0.05, 4]
+PILLARNET_GRID_SIZE = [1408, 1600, 1]
+PILLARNET_CFG = {
+    'NAME': 'PillarNet',
+    'VFE': {'NAME': 'DynamicPillarVFESimple2D', 'USE_NORM': True, 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'NUM_FILTERS': [32]},
+    'BACKBONE_3D': {'NAME': 'PillarBackBone8x'},
+    'BACKBONE_2D': {'NAME': 'BaseBEVBackboneV1', 'LAYER_NUMS': [5, 5], 'NUM_FILTERS': [256, 256], 'UPSAMPLE_STRIDES': [1, 2],
+                    'NUM_UPSAMPLE_FILTERS': [128, 128]},
+    'DENSE_HEAD': copy.deepcopy(CENTER_PDM_CFG['DENSE_HEAD']),
+    'POST_PROCESSING': copy.deepcopy(CENTER_PDM_CFG['POST_PROCESSING']),
+}
+PILLARNET_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['FEATURE_MAP_STRIDE'] = 8
+PILLARNET_CFG['DENSE_HEAD']['POST_PROCESSING']['BATCHED'] = True
+PILLARNET_TRAIN_CFG = copy.deepcopy(PILLARNET_CFG)
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -448,3 +472,20 @@ def build_pv_rcnn_plusplus(model_cfg=None, num_point_features=4, dataset=None):
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(PV_RCNN_PP_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=voxel_dataset(num_point_features) if dataset is None else dataset)
+
+
+def pillarnet_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None, grid_size=None):
+    """PillarNet's dataset namespace: the KITTI voxel range on 0.05 m pillars over the whole height unless other values are given."""
+    return SimpleNamespace(class_names=CLASS_NAMES, grid_size=list(PILLARNET_GRID_SIZE if grid_size is None else grid_size),
+                           voxel_size=list(PILLARNET_VOXEL_SIZE if voxel_size is None else voxel_size),
+                           point_cloud_range=list(PILLARNET_RANGE if point_cloud_range is None else point_cloud_range),
+                           point_feature_encoder=SimpleNamespace(num_point_features=num_point_features))
+
+
+def build_pillarnet(model_cfg=None, num_point_features=4, dataset=None):
+    """PillarNet from PILLARNET_CFG, PILLARNET_TRAIN_CFG or a dict like them: DynamicPillarVFESimple2D -> PillarBackBone8x (or
+    PillarRes18BackBone8x) -> BaseBEVBackboneV1 -> CenterHead, on pillarnet_dataset() unless another dataset namespace is given.
+    Runs in eval mode and takes training steps."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(PILLARNET_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillarnet_dataset(num_point_features) if dataset is None else dataset)

@@ -6,6 +6,7 @@ from .detector3d_template import BACKBONES_2D, BACKBONES_3D, MAP_TO_BEV, VFE, De
 from .centerpoint import CenterPoint
 from .partA2_net import PartA2Net
 from .pdm_ssd import PDMSSD
+from .pillarnet import PillarNet
 from .point_rcnn import PointRCNN
 from .pointpillar import PointPillar
 from .pv_rcnn import PVRCNN
@@ -26,6 +27,7 @@ __all__ = {
     'PVRCNNPlusPlus': PVRCNNPlusPlus,
     'PartA2Net': PartA2Net,
     'SECONDNetIoU': SECONDNetIoU,
+    'PillarNet': PillarNet,
 }
 
 

@@ -8,7 +8,9 @@ pcdet/utils/spconv_utils.py:3).  The vfe, backbone_3d, map_to_bev and backbone_2
 (DynamicPillarVFE -> PointPillarScatter -> BaseBEVBackbone) and the voxel family (DynamicMeanVFE ->
 VoxelBackBone8x / VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone) on this package's own sparse convolution, each also
 on hard voxels (HardPillarVFE / HardMeanVFE, which voxelize on the device with the two sizes of their own config); a NAME outside
-the registries (the plain MeanVFE and PillarVFE among them, ...) is refused.  The pfe slot builds PV-RCNN's VoxelSetAbstraction or PV-RCNN++'s
+the registries (the plain MeanVFE and PillarVFE among them, ...) is refused.  The sparse pillar family (DynamicPillarVFESimple2D ->
+PillarBackBone8x / PillarRes18BackBone8x -> BaseBEVBackboneV1, PillarNet) has no map_to_bev module: its 2-D backbone reads the dense
+levels the sparse 2-D backbone leaves, and is refused without one.  The pfe slot builds PV-RCNN's VoxelSetAbstraction or PV-RCNN++'s
 VoxelSetAbstractionSPC, the roi_head slot the RoI heads of roi_heads/ (PointRCNN's second stage, Voxel R-CNN's, PV-RCNN's in eval
 mode).
 """
@@ -106,7 +108,13 @@ class Detector3DTemplate(nn.Module):
         cfg = self._registered('BACKBONE_2D', BACKBONES_2D)
         if cfg is None:
             return None, model_info_dict
-        module = BACKBONES_2D[_get(cfg, 'NAME')](model_cfg=cfg, input_channels=model_info_dict['num_bev_features'])
+        if _get(cfg, 'NAME') == 'BaseBEVBackboneV1':
+            # it reads multi_scale_2d_features['x_conv4' / 'x_conv5']: the model's BACKBONE_3D must have published those two widths
+            channels = model_info_dict.get('backbone_channels', None) or {}
+            assert 'x_conv4' in channels and 'x_conv5' in channels, \
+                ('BACKBONE_2D BaseBEVBackboneV1 needs a sparse 2-D (spconv-style) BACKBONE_3D such as PillarBackBone8x, whose dense '
+                 f'x_conv4 / x_conv5 maps it reads; this model\'s backbone published {sorted(channels)}')
+        module = BACKBONES_2D[_get(cfg, 'NAME')](model_cfg=cfg, input_channels=model_info_dict.get('num_bev_features', None))
         model_info_dict['module_list'].append(module)
         model_info_dict['num_bev_features'] = module.num_bev_features
         return module, model_info_dict

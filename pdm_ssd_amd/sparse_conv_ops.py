@@ -28,6 +28,9 @@ from . import _native
 HOST_READS = 0              # device-to-host copies this module has made
 CIN_SUPPORTED = (3, 4, 5, 6, 7, 8, 16, 32, 64, 128)
 COUT_SUPPORTED = (16, 32, 64, 128)
+# wide=True (pdm_sparse_conv_wide*): the 2-D pillar backbones' 256-wide layers; the defaults keep refusing 256
+CIN_WIDE = CIN_SUPPORTED + (256,)
+COUT_WIDE = COUT_SUPPORTED + (256,)
 
 Voxels = namedtuple('Voxels', ['kept_idx', 'unq_inv', 'voxel_coords', 'voxel_count', 'voxel_mean', 'num_kept', 'num_voxels'])
 # in_indices / in_shape: the input rows and grid the table was built over, where an inverse convolution finds them
@@ -255,13 +258,19 @@ class RoIGridPoolFunction(torch.autograd.Function):
         return dfeat, dwp.reshape(wp.shape), dscale, dshift, None, None
 
 
-def pack_weight(weight):
+def _check_widths(cin, cout, wide):
+    cins, couts = (CIN_WIDE, COUT_WIDE) if wide else (CIN_SUPPORTED, COUT_SUPPORTED)
+    if cin not in cins or cout not in couts:
+        raise ValueError(f'sparse_conv: {cin} -> {cout} channels; Cin in {cins}, Cout in {couts}' + ('' if wide else ' (wide=True: up to 256)'))
+
+
+def pack_weight(weight, wide=False):
     """weight (Cout, kz, ky, kx, Cin) (spconv 2.x's layout) -> the kernel's packed form, a flat fp32 tensor
     [k][kb][nb][lane][j] = W[cout = 16 nb + (lane & 15)][k][cin = 16 kb + 4 (lane >> 4) + j], zero past Cin: the A fragments
-    of mfma_f32_16x16x4f32 in the order the kernel reads them.  Device arithmetic only."""
+    of mfma_f32_16x16x4f32 in the order the kernel reads them.  Device arithmetic only.  wide: CIN_WIDE / COUT_WIDE, for the
+    wide entries (the same layout, nb and kb up to 16)."""
     cout, cin = weight.shape[0], weight.shape[-1]
-    if cin not in CIN_SUPPORTED or cout not in COUT_SUPPORTED:
-        raise ValueError(f'sparse_conv: {cin} -> {cout} channels; Cin in {CIN_SUPPORTED}, Cout in {COUT_SUPPORTED}')
+    _check_widths(cin, cout, wide)
     w = weight.detach().float().reshape(cout, -1, cin)
     kvol, nkb, nb = w.shape[1], (cin + 15) // 16, cout // 16
     w = torch.nn.functional.pad(w, (0, 16 * nkb - cin))                        # (cout, kvol, 16 nkb)
@@ -272,12 +281,13 @@ def pack_weight(weight):
 
 
 @torch.no_grad()
-def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residual=None, relu=False, out=None, split=False):
+def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residual=None, relu=False, out=None, split=False, wide=False):
     """out[i, :] = epilogue(sum over k ascending of W[k] features[nbr[i, k], :]) (pdm_sparse_conv): features (P_in, cin) fp32,
     nbr (P_out, kvol) int32, wpack = pack_weight(weight); epilogue = * scale + shift (the folded BatchNorm, both or neither),
     + residual (P_out, cout), ReLU.  Output-stationary on the exact f32 MFMA, no atomics: two runs and a graph replay give
     the same bits.  No host read.  split: pdm_sparse_conv_split, which adds every offset's products in an accumulator of their own
-    and that to a running sum (about a third of the rounding error of the one long chain; other bits): the training path's form."""
+    and that to a running sum (about a third of the rounding error of the one long chain; other bits): the training path's form.
+    wide: pdm_sparse_conv_wide / pdm_sparse_conv_wide_split, which also take 256 channels and give the narrow entries' bits below."""
     assert features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[1] == cin, tuple(features.shape)
     assert nbr.dtype == torch.int32 and nbr.dim() == 2
     features, nbr = features.contiguous(), nbr.contiguous()
@@ -289,25 +299,25 @@ def sparse_conv(features, nbr, wpack, cin, cout, scale=None, shift=None, residua
         assert residual.shape == (P_out, cout) and residual.dtype == torch.float32
         residual = residual.contiguous()
     opt = [None if t is None else t.detach().float().contiguous() for t in (scale, shift)]
-    _native.call("pdm_sparse_conv_split" if split else "pdm_sparse_conv", _native.stream(features), P_out, features.shape[0], kvol, cin, cout, features.data_ptr(), nbr.data_ptr(),
+    entry = ("pdm_sparse_conv_wide_split" if split else "pdm_sparse_conv_wide") if wide else ("pdm_sparse_conv_split" if split else "pdm_sparse_conv")
+    _native.call(entry, _native.stream(features), P_out, features.shape[0], kvol, cin, cout, features.data_ptr(), nbr.data_ptr(),
                  wpack.data_ptr(), *(None if t is None else t.data_ptr() for t in opt), None if residual is None else residual.data_ptr(),
                  1 if relu else 0, out.data_ptr())
     return out
 
 
-def pack_weight_transposed(weight, flip=False):
+def pack_weight_transposed(weight, flip=False, wide=False):
     """weight (Cout, kz, ky, kx, Cin) -> pack_weight of W^T, the convolution Cout -> Cin (padded to 16 when Cin < 16) that the
     data gradient runs: [k][kb][nb][lane][j] = W[cout = 16 kb + 4 (lane >> 4) + j][k' ][cin = 16 nb + (lane & 15)], zero past Cin,
     with k' = k, or k' = kvol - 1 - k when `flip` (the offset order reversed: a submanifold layer's data gradient walks the
     forward's own nbr, since nbr_t[j][k] == nbr[j][kvol - 1 - k]).  Device arithmetic only."""
     cout, cin = weight.shape[0], weight.shape[-1]
-    if cin not in CIN_SUPPORTED or cout not in COUT_SUPPORTED:
-        raise ValueError(f'sparse_conv: {cin} -> {cout} channels; Cin in {CIN_SUPPORTED}, Cout in {COUT_SUPPORTED}')
+    _check_widths(cin, cout, wide)
     w = weight.detach().float().reshape(cout, -1, cin)
     if flip:
         w = w.flip(1)
     w = torch.nn.functional.pad(w.permute(2, 1, 0), (0, 0, 0, 0, 0, max(16 - cin, 0)))      # (cin padded, kvol, cout)
-    return pack_weight(w.reshape(w.shape[0], *weight.shape[1:4], cout))
+    return pack_weight(w.reshape(w.shape[0], *weight.shape[1:4], cout), wide=wide)
 
 
 @torch.no_grad()
@@ -323,17 +333,19 @@ def rulebook_transpose(nbr, num_in_rows):
     return nbr_t
 
 
-def wgrad_chunk_rows(num_out_rows, kvol, cin, cout):
+def wgrad_chunk_rows(num_out_rows, kvol, cin, cout, wide=False):
     """rows of one chunk of sparse_conv_wgrad's first phase: a function of these four numbers alone"""
-    return _native.lib().pdm_sparse_conv_wgrad_chunk_rows(int(num_out_rows), int(kvol), int(cin), int(cout))
+    query = _native.lib().pdm_sparse_conv_wide_wgrad_chunk_rows if wide else _native.lib().pdm_sparse_conv_wgrad_chunk_rows
+    return query(int(num_out_rows), int(kvol), int(cin), int(cout))
 
 
 @torch.no_grad()
-def sparse_conv_wgrad(dy, features, nbr, kernel_size, out=None):
+def sparse_conv_wgrad(dy, features, nbr, kernel_size, out=None, wide=False):
     """dW (Cout, kz, ky, kx, Cin)[co, k, ci] = sum over i of dy[i, co] features[nbr[i, k], ci] (pdm_sparse_conv_wgrad): dy (P_out,
     Cout), features (P_in, Cin) fp32, nbr (P_out, kvol) int32.  Rows are the contraction of the exact f32 MFMA; partial blocks
     per (row chunk, offset) in a workspace, then one launch adds the chunks in ascending order.  No atomics, chunk boundaries a
-    function of the sizes alone: two runs and a graph replay give the same bits.  No host read."""
+    function of the sizes alone: two runs and a graph replay give the same bits.  No host read.  wide: pdm_sparse_conv_wide_wgrad,
+    a 256-wide side as two 128-wide sub-blocks."""
     assert dy.is_cuda and dy.dtype == torch.float32 and dy.dim() == 2 and features.dtype == torch.float32 and features.dim() == 2
     assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == dy.shape[0], (tuple(nbr.shape), tuple(dy.shape))
     dy, features, nbr = dy.contiguous(), features.contiguous(), nbr.contiguous()
@@ -343,19 +355,20 @@ def sparse_conv_wgrad(dy, features, nbr, kernel_size, out=None):
     if out is None:
         out = torch.empty((cout, *k, cin), dtype=torch.float32, device=dy.device)
     assert out.shape == (cout, *k, cin) and out.is_contiguous() and out.dtype == torch.float32
-    nbytes = _native.lib().pdm_sparse_conv_wgrad_workspace_bytes(P_out, kvol, cin, cout)
+    entry = "pdm_sparse_conv_wide_wgrad" if wide else "pdm_sparse_conv_wgrad"
+    nbytes = getattr(_native.lib(), entry + "_workspace_bytes")(P_out, kvol, cin, cout)
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dy.device)
-    _native.call("pdm_sparse_conv_wgrad", _native.stream(dy), P_out, features.shape[0], kvol, cin, cout, dy.data_ptr(), features.data_ptr(),
+    _native.call(entry, _native.stream(dy), P_out, features.shape[0], kvol, cin, cout, dy.data_ptr(), features.data_ptr(),
                  nbr.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
-def sparse_conv_dgrad(dy, table, wpack_t, cin, cout):
+def sparse_conv_dgrad(dy, table, wpack_t, cin, cout, wide=False):
     """dx (P_in, cin) = sum over k of W[k]^T dy[table[:, k]]: the forward kernel (its split form) over `table` (P_in, kvol), which is
     rulebook_transpose(nbr, P_in) with wpack_t = pack_weight_transposed(weight), or a submanifold layer's own nbr with
     wpack_t = pack_weight_transposed(weight, flip=True).  Sliced to cin when the pack padded it to 16."""
     cin_p = max(cin, 16)
-    dx = sparse_conv(dy, table, wpack_t, cout, cin_p, split=True)
+    dx = sparse_conv(dy, table, wpack_t, cout, cin_p, split=True, wide=wide)
     return dx if cin_p == cin else dx[:, :cin].contiguous()
 
 
@@ -363,18 +376,20 @@ class SparseConvFunction(torch.autograd.Function):
     """out = pdm_sparse_conv_split(features, nbr, W) + bias, with its gradients: dW by sparse_conv_wgrad, dbias = dy.sum(0), and, when
     the input requires grad, dx by sparse_conv_dgrad.  nbr_t: rulebook_transpose(nbr, P_in), or True for a submanifold layer
     (odd kernels), whose data gradient walks nbr itself; None when the input takes no gradient.  wpack / wpack_t: the packed
-    weights when the caller keeps them (pack_weight, pack_weight_transposed with flip = nbr_t is True), else packed here."""
+    weights when the caller keeps them (pack_weight, pack_weight_transposed with flip = nbr_t is True), else packed here.
+    wide: every launch through the wide entries (up to 256 channels)."""
 
     @staticmethod
-    def forward(ctx, features, weight, bias, nbr, nbr_t, cin, cout, wpack=None, wpack_t=None):
+    def forward(ctx, features, weight, bias, nbr, nbr_t, cin, cout, wpack=None, wpack_t=None, wide=False):
         assert weight.shape[0] == cout and weight.shape[-1] == cin and weight.dim() == 5, (tuple(weight.shape), cin, cout)
         features = features.contiguous()
         if wpack is None:
-            wpack = pack_weight(weight)
+            wpack = pack_weight(weight, wide=wide)
         shift = None if bias is None else bias.detach()
-        out = sparse_conv(features.detach(), nbr, wpack, cin, cout, None if shift is None else torch.ones_like(shift), shift, split=True)
+        out = sparse_conv(features.detach(), nbr, wpack, cin, cout, None if shift is None else torch.ones_like(shift), shift, split=True,
+                          wide=wide)
         ctx.save_for_backward(features, weight, nbr, nbr_t if torch.is_tensor(nbr_t) else None, wpack_t)
-        ctx.subm_identity, ctx.has_bias, ctx.dims = nbr_t is True, bias is not None, (cin, cout)
+        ctx.subm_identity, ctx.has_bias, ctx.dims, ctx.wide = nbr_t is True, bias is not None, (cin, cout), bool(wide)
         return out
 
     @staticmethod
@@ -388,13 +403,13 @@ class SparseConvFunction(torch.autograd.Function):
             if table is None:
                 raise RuntimeError('SparseConvFunction: the input requires grad but no transposed rulebook was given')
             if wpack_t is None:
-                wpack_t = pack_weight_transposed(weight, flip=ctx.subm_identity)
-            dx = sparse_conv_dgrad(dy, table, wpack_t, cin, cout)
+                wpack_t = pack_weight_transposed(weight, flip=ctx.subm_identity, wide=ctx.wide)
+            dx = sparse_conv_dgrad(dy, table, wpack_t, cin, cout, wide=ctx.wide)
         if ctx.needs_input_grad[1]:
-            dw = sparse_conv_wgrad(dy, features, nbr, weight.shape[1:4])
+            dw = sparse_conv_wgrad(dy, features, nbr, weight.shape[1:4], wide=ctx.wide)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = dy.sum(0)
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 class ToDenseFunction(torch.autograd.Function):

@@ -18,6 +18,11 @@ the one the data gradient walks (one (indice_key, 'nbr_t') slot for both).  Eval
 A rulebook is built once per indice_key per forward and shared by the layers that name the key (the tensors of one forward
 share one indice_dict), as spconv shares them.  Row orders: a submanifold convolution keeps its input's rows; a strided one
 numbers its output sites in ascending key order of the output grid, which is build-defined (spconv's comes from a hash).
+
+2-D: a SparseConvTensor with indices (P, 3) = (b, y, x) and spatial_shape (H, W); SubMConv2d and SparseConv2d,
+weight (Cout, kh, kw, Cin).  They are the 3-D layers on a depth-1 grid (kd = 1, sd = 1, pd = 0) with everything above shared,
+and they run the WIDE entries (pdm_sparse_conv_wide, _wide_split, _wide_wgrad), so they take up to 256 channels; the 3-D
+classes keep the narrow entries and their 128.  dense() is (B, C, H, W).  SparseInverseConv2d is not built.
 """
 import math
 
@@ -31,20 +36,40 @@ NEXT_STEP = ("the voxel path runs in eval mode only: the sparse convolution's da
 
 
 class SparseConvTensor:
-    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None):
-        """features (P, C) fp32, indices (P, 4) int32 (b, z, y, x), spatial_shape (D, H, W)"""
+    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None, indices4=None):
+        """features (P, C) fp32, indices (P, 4) int32 (b, z, y, x), spatial_shape (D, H, W); or 2-D: indices (P, 3) int32
+        (b, y, x), spatial_shape (H, W) (indices4: the same rows as (b, 0, y, x) when the caller holds them)"""
         self.features = features
         self.indices = indices
         self.spatial_shape = [int(v) for v in spatial_shape]
         self.batch_size = int(batch_size)
         self.indice_dict = {} if indice_dict is None else indice_dict      # indice_key -> sparse_conv_ops.Rulebook
+        self._indices4 = indices4
+
+    @property
+    def ndim(self):
+        return len(self.spatial_shape)
+
+    def indices4(self):
+        """the rows as the 3-D operators take them: `indices`, or (b, 0, y, x) of a 2-D tensor (made once, device arithmetic)"""
+        if self.ndim == 3:
+            return self.indices
+        if self._indices4 is None:
+            i = self.indices
+            self._indices4 = torch.stack([i[:, 0], torch.zeros_like(i[:, 0]), i[:, 1], i[:, 2]], 1).contiguous()
+        return self._indices4
+
+    def shape3(self):
+        return self.spatial_shape if self.ndim == 3 else [1] + self.spatial_shape
 
     def replace_feature(self, feature):
-        return SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict)
+        return SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self._indices4)
 
     def dense(self):
-        """(B, C, D, H, W), zeros where no site is active: one launch writes every element; differentiable in the features"""
-        return sparse_conv_ops.to_dense(self.features, self.indices, self.batch_size, self.spatial_shape)
+        """(B, C, D, H, W), or (B, C, H, W) of a 2-D tensor, zeros where no site is active: one launch writes every element;
+        differentiable in the features"""
+        out = sparse_conv_ops.to_dense(self.features, self.indices4(), self.batch_size, self.shape3())
+        return out if self.ndim == 3 else out.squeeze(2)
 
 
 def replace_feature(out, new_features):
@@ -68,16 +93,26 @@ def fold_norm(norm, bias, cout, like):
     return scale, shift
 
 
+def _depth1(v, first):
+    """a 2-D layer's (h, w) setting as the depth-1 triple (first, h, w)"""
+    return (first, int(v), int(v)) if isinstance(v, int) else (first, *(int(x) for x in v))
+
+
 class SparseConvolution(SparseModule):
+    ndim = 3            # 2 in the 2-D classes: the weight is (Cout, kh, kw, Cin), the tensors (b, y, x) on (H, W)
+    wide = False        # True in the 2-D classes: the wide entries, up to 256 channels
+
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, indice_key=None, subm=False):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
+        if self.ndim == 2:
+            kernel_size, stride, padding = _depth1(kernel_size, 1), _depth1(stride, 1), _depth1(padding, 0)
         self.kernel_size = sparse_conv_ops._triple(kernel_size)
         self.stride = sparse_conv_ops._triple(stride)
         self.padding = sparse_conv_ops._triple(padding)
         self.indice_key = indice_key
         self.subm = subm
-        self.weight = nn.Parameter(torch.empty(out_channels, *self.kernel_size, in_channels))
+        self.weight = nn.Parameter(torch.empty(out_channels, *self.kernel_size[3 - self.ndim:], in_channels))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self._cache = {}        # 'pack' / 'fold' -> (parameter versions, tensors)
         self.reset_parameters()
@@ -105,10 +140,22 @@ class SparseConvolution(SparseModule):
             assert rb.subm == self.subm and rb.kernel_size == self.kernel_size and (not self.subm or rb.nbr.shape[0] == x.indices.shape[0]), \
                 f'indice_key {self.indice_key}: another convolution geometry built this rulebook'
             return rb
-        rb = sparse_conv_ops.rulebook(x.indices, x.batch_size, x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)
+        rb = sparse_conv_ops.rulebook(x.indices4(), x.batch_size, x.shape3(), self.kernel_size, self.stride, self.padding, self.subm)
         if self.indice_key is not None:
             x.indice_dict[self.indice_key] = rb
         return rb
+
+    def weight5(self):
+        """the weight as the operators take it, (Cout, kz, ky, kx, Cin): the parameter itself, or a view of a 2-D layer's"""
+        return self.weight if self.ndim == 3 else self.weight.view(self.out_channels, *self.kernel_size, self.in_channels)
+
+    def out_tensor(self, x, features, rb):
+        """the layer's output on the rulebook's output sites and grid, in the input's dimensionality"""
+        if self.ndim == 3:
+            return SparseConvTensor(features, rb.out_indices, rb.out_shape, x.batch_size, x.indice_dict)
+        if self.subm:
+            return SparseConvTensor(features, x.indices, x.spatial_shape, x.batch_size, x.indice_dict, x.indices4())
+        return SparseConvTensor(features, rb.out_indices[:, [0, 2, 3]].contiguous(), rb.out_shape[1:], x.batch_size, x.indice_dict, rb.out_indices)
 
     def get_transpose(self, x, rb, num_in_rows=None):
         """the transposed table of a strided rulebook, built once per forward beside the rulebook it belongs to (under the
@@ -130,27 +177,30 @@ class SparseConvolution(SparseModule):
         if grad_path and not x.features.is_cuda:
             raise NotImplementedError(NEXT_STEP)
         assert x.features.shape[1] == self.in_channels, (tuple(x.features.shape), self.in_channels)
+        assert x.ndim == self.ndim, f'a {self.ndim}-D layer on a {x.ndim}-D SparseConvTensor'
         rb = self.get_rulebook(x)
-        wpack = self._cached('pack', [self.weight], lambda: sparse_conv_ops.pack_weight(self.weight))
+        weight, wide = self.weight5(), self.wide
+        wpack = self._cached('pack', [self.weight], lambda: sparse_conv_ops.pack_weight(weight, wide=wide))
         if grad_path:
             nbr_t = wpack_t = None
             if x.features.requires_grad and torch.is_grad_enabled():
                 identity = self.subm and all(k % 2 == 1 for k in self.kernel_size)      # nbr_t[j][k] == nbr[j][kvol - 1 - k]
                 nbr_t = True if identity else self.get_transpose(x, rb)
-                wpack_t = self._cached('pack_t', [self.weight], lambda: sparse_conv_ops.pack_weight_transposed(self.weight, flip=identity))
-            out = sparse_conv_ops.SparseConvFunction.apply(x.features, self.weight, self.bias, rb.nbr, nbr_t, self.in_channels,
-                                                           self.out_channels, wpack, wpack_t)
+                wpack_t = self._cached('pack_t', [self.weight], lambda: sparse_conv_ops.pack_weight_transposed(weight, flip=identity, wide=wide))
+            out = sparse_conv_ops.SparseConvFunction.apply(x.features, weight, self.bias, rb.nbr, nbr_t, self.in_channels,
+                                                           self.out_channels, wpack, wpack_t, wide)
             if norm is not None:
                 out = norm(out)
             if residual is not None:
                 out = out + residual
             if relu:
                 out = torch.relu(out)
-            return SparseConvTensor(out, rb.out_indices, rb.out_shape, x.batch_size, x.indice_dict)
+            return self.out_tensor(x, out, rb)
         sources = [self.bias] + ([norm.weight, norm.bias, norm.running_mean, norm.running_var] if norm is not None else [])
         scale, shift = self._cached('fold', sources, lambda: fold_norm(norm, self.bias, self.out_channels, self.weight))
-        out = sparse_conv_ops.sparse_conv(x.features, rb.nbr, wpack, self.in_channels, self.out_channels, scale, shift, residual, relu)
-        return SparseConvTensor(out, rb.out_indices, rb.out_shape, x.batch_size, x.indice_dict)
+        out = sparse_conv_ops.sparse_conv(x.features, rb.nbr, wpack, self.in_channels, self.out_channels, scale, shift, residual, relu,
+                                          wide=wide)
+        return self.out_tensor(x, out, rb)
 
 
 class SubMConv3d(SparseConvolution):
@@ -160,6 +210,24 @@ class SubMConv3d(SparseConvolution):
 
 
 class SparseConv3d(SparseConvolution):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None, **kwargs):
+        assert dilation == 1 and groups == 1, 'dilation and groups are not built'
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, subm=False)
+
+
+class SubMConv2d(SparseConvolution):
+    """spconv 2.x's SubMConv2d on the depth-1 grid: weight (Cout, kh, kw, Cin), up to 256 channels"""
+    ndim, wide = 2, True
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None, **kwargs):
+        assert dilation == 1 and groups == 1, 'dilation and groups are not built'
+        super().__init__(in_channels, out_channels, kernel_size, 1, padding, bias, indice_key, subm=True)
+
+
+class SparseConv2d(SparseConvolution):
+    """spconv 2.x's SparseConv2d on the depth-1 grid; the output sites ascend in (b W' + x) H' + y of the output grid"""
+    ndim, wide = 2, True
+
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True, indice_key=None, **kwargs):
         assert dilation == 1 and groups == 1, 'dilation and groups are not built'
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias, indice_key, subm=False)
@@ -225,4 +293,5 @@ class SparseSequential(SparseModule, nn.Sequential):
         return x
 
 
-__all__ = ['SparseConvTensor', 'SparseModule', 'SparseSequential', 'SubMConv3d', 'SparseConv3d', 'SparseInverseConv3d', 'replace_feature']
+__all__ = ['SparseConvTensor', 'SparseModule', 'SparseSequential', 'SubMConv3d', 'SparseConv3d', 'SparseInverseConv3d', 'SubMConv2d',
+           'SparseConv2d', 'replace_feature']

@@ -333,6 +333,48 @@ int pdm_center_reg_loss(void *stream, int B, int num_max_objs, int D, int H, int
                         const float *code_weights, float loc_weight, float *loss_per_code, float *out, float *grad,
                         void *workspace, size_t workspace_bytes);
 
+/* ---- TransFusionHead (csrc/attention.hip, csrc/transfusion.hip): fused attention forward, query
+ * initialisation and query-wise box decode of the reference's pcdet/models/dense_heads/transfusion_head.py:151-218, :397-479.
+ * Nothing synchronises, nothing is read on the host, no float atomics, single stream; safe to capture in a graph after one
+ * warm-up call.
+ *
+ * pdm_mha_forward: q (B, P, C), k (B, N, C), v (B, N, C) fp32, each with its own ROW stride in elements (>= C; a sample is
+ *   `rows` consecutive rows, so k and v may be the two halves of one (B, N, 2C) tensor); d = C / nheads.  out (B, P, C),
+ *   contiguous = softmax(q_h k_h^T / sqrt(d)) v_h per head, heads concatenated (what lies between nn.MultiheadAttention's
+ *   in- and out-projection with no mask and no dropout).  Supported: d in {16, 32}, C <= 256, P >= 1, N >= 1; anything
+ *   else is PDM_E_BADARG.  The keys are cut into chunks of keys_per_chunk (0 = pdm_mha_default_keys_per_chunk()); one
+ *   workgroup per (sample, head, chunk, 64 queries) runs an online softmax on the fp32 MFMA and writes (maximum, sum,
+ *   unnormalised accumulator); a second launch folds the partials in chunk order.  The chunking depends on
+ *   (N, keys_per_chunk) alone: two runs give the same bits.  workspace >= pdm_mha_forward_workspace_bytes(...), 8-byte
+ *   aligned.  align: any (q and k are read 16 bytes at a time only when both are 16-byte aligned with strides % 4 == 0).
+ * pdm_tf_proposals: logits (B, C, H, W) fp32 contiguous.  s = sigmoid(logit); a cell of class c keeps s if no cell of its
+ *   nms_kernel x nms_kernel window (odd) has a greater s and the cell is at least nms_kernel / 2 from the border; a class in
+ *   `exempt` (HOST array of num_exempt ints) keeps s everywhere; every other cell scores 0.  Per sample the P <= 16384
+ *   highest scores over the flat (class, y, x) index, ties by lower index (rank_select.h): index (B, P) int64 = y * W + x,
+ *   cls (B, P) int64, query_heatmap_score (B, C, P) = the masked score of every class at the cell, query_pos (B, P, 2) =
+ *   (index % y_size + 0.5, index / y_size + 0.5), the reference's flipped `ij` mesh.  Three launches: the filter over all
+ *   cells, a rank select of the best P of every slice of 4096 flat indices, a rank select over those candidates.
+ *   workspace >= pdm_tf_proposals_workspace_bytes(B, C, H, W, P), 8-byte aligned.
+ * pdm_tf_decode: heatmap (B, C, P) logits, center (B, 2, P) with the query position added, height (B, 1, P), dim (B, 3, P),
+ *   rot (B, 2, P) = [sin, cos], vel (B, 2, P) | NULL, cls (B, P) int64, query_heatmap_score (B, C, P); all contiguous.
+ *   Query p of class c: score = sigmoid(heatmap[c, p]) * query_heatmap_score[c, p]; x = (center_x * stride) * vx + x0 (each
+ *   step one fp32 rounding), y likewise, z = height, sizes exp(dim), angle atan2(rot[0], rot[1]); kept iff score >
+ *   score_thresh (>= 0, strict) and x, y, z within limit_range (HOST [lo3, hi3], inclusive); survivors compacted in query
+ *   order: boxes (B, P, 7 | 9), scores (B, P), labels (B, P) int64 = c + 1, count (B) int32; padding rows zero. */
+int pdm_mha_default_keys_per_chunk(void);
+size_t pdm_mha_forward_workspace_bytes(int B, int P, int N, int C, int nheads, int keys_per_chunk);
+int pdm_mha_forward(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
+                    const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
+                    float *out, void *workspace, size_t workspace_bytes);
+size_t pdm_tf_proposals_workspace_bytes(int B, int C, int H, int W, int P);
+int pdm_tf_proposals(void *stream, int B, int C, int H, int W, const float *logits, int nms_kernel, int num_exempt,
+                     const int *exempt, int P, int y_size, long long *index, long long *cls,
+                     float *query_heatmap_score, float *query_pos, void *workspace, size_t workspace_bytes);
+int pdm_tf_decode(void *stream, int B, int C, int P, const float *heatmap, const float *center, const float *height,
+                  const float *dim, const float *rot, const float *vel, const long long *cls,
+                  const float *query_heatmap_score, float score_thresh, const float *limit_range, float x0, float y0,
+                  float vx, float vy, float stride, float *boxes, float *scores, long long *labels, int *count);
+
 /* OPT-IN: the same three-layer per-row MLP with fp32 EMULATED on the bf16 matrix pipe — every fp32 operand split into three
  * bf16 pieces (8 + 8 + 8 significand bits), a product formed from the six leading partial products on
  * v_mfma_f32_16x16x32_bf16 with fp32 accumulation (3/8 of the fp32-MFMA pipe time; dropped terms <= 2^-24 |a b|).

@@ -7,6 +7,7 @@ from .point_head_box import PointHeadBox
 from .point_head_simple import PointHeadSimple
 from .point_intra_part_head import PointIntraPartOffsetHead
 from .point_head_template import PointHeadTemplate
+from .transfusion_head import TransFusionHead
 
 __all__ = {
     'PointHeadTemplate': PointHeadTemplate,
@@ -17,4 +18,5 @@ __all__ = {
     'CenterHead': CenterHead,
     'AnchorHeadTemplate': AnchorHeadTemplate,
     'AnchorHeadSingle': AnchorHeadSingle,
+    'TransFusionHead': TransFusionHead,
 }

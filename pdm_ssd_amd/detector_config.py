@@ -348,6 +348,43 @@ PILLARNET_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['FEATURE_MAP_STRIDE'] = 8
 PILLARNET_CFG['DENSE_HEAD']['POST_PROCESSING']['BATCHED'] = True
 PILLARNET_TRAIN_CFG = copy.deepcopy(PILLARNET_CFG)
 
+# TransFusion-L: the LiDAR branch of the upstream project's BEVFusion recipe for nuScenes, restated as far as it is remembered
+# here and not checked against any file (the snapshot this repository was modelled on holds no YAML): ten classes, range
+# [-54, 54] m x [-54, 54] m x [-5, 3] m on 0.075 x 0.075 x 0.2 m voxels (grid 1440 x 1440 x 40, a 180 x 180 map at stride 8),
+# mean VFE -> VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone (512 channels out) -> TransFusionHead with 200 queries,
+# 128 hidden channels, 8 attention heads, a 256-wide feed-forward block and a 3 x 3 local-maximum filter.  The encoder is
+# DynamicMeanVFE, as in every voxel detector of this build (the plain NAME MeanVFE stays refused, vfe/__init__.py).  Eval only:
+# the head has no training half, so the LOSS_CONFIG and assigner values are carried for the record alone.
+TRANSFUSION_CLASS_NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle',
+                           'pedestrian', 'traffic_cone']
+TRANSFUSION_RANGE = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
+TRANSFUSION_VOXEL_SIZE = [0.075, 0.075, 0.2]
+TRANSFUSION_GRID_SIZE = [1440, 1440, 40]
+TRANSFUSION_LIDAR_CFG = {
+    'NAME': 'TransFusion',
+    'VFE': {'NAME': 'DynamicMeanVFE'},
+    'BACKBONE_3D': {'NAME': 'VoxelResBackBone8x'},
+    'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256},
+    'BACKBONE_2D': {'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [5, 5], 'LAYER_STRIDES': [1, 2], 'NUM_FILTERS': [128, 256],
+                    'UPSAMPLE_STRIDES': [1, 2], 'NUM_UPSAMPLE_FILTERS': [256, 256]},
+    'DENSE_HEAD': {
+        'NAME': 'TransFusionHead', 'CLASS_AGNOSTIC': False, 'USE_BIAS_BEFORE_NORM': False,
+        'NUM_PROPOSALS': 200, 'HIDDEN_CHANNEL': 128, 'NUM_CLASSES': 10, 'NUM_HEADS': 8, 'NMS_KERNEL_SIZE': 3, 'FFN_CHANNEL': 256,
+        'DROPOUT': 0.1, 'BN_MOMENTUM': 0.1, 'ACTIVATION': 'relu', 'NUM_HM_CONV': 2,
+        'SEPARATE_HEAD_CFG': {'HEAD_ORDER': ['center', 'height', 'dim', 'rot', 'vel'],
+                              'HEAD_DICT': {'center': {'out_channels': 2, 'num_conv': 2}, 'height': {'out_channels': 1, 'num_conv': 2},
+                                            'dim': {'out_channels': 3, 'num_conv': 2}, 'rot': {'out_channels': 2, 'num_conv': 2},
+                                            'vel': {'out_channels': 2, 'num_conv': 2}}},
+        'TARGET_ASSIGNER_CONFIG': {'FEATURE_MAP_STRIDE': 8, 'DATASET': 'nuScenes', 'GAUSSIAN_OVERLAP': 0.1, 'MIN_RADIUS': 2,
+                                   'HUNGARIAN_ASSIGNER': {'cls_cost': {'gamma': 2.0, 'alpha': 0.25, 'weight': 0.15},
+                                                          'reg_cost': {'weight': 0.25}, 'iou_cost': {'weight': 0.25}}},
+        'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'bbox_weight': 0.25, 'hm_weight': 1.0,
+                                         'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2]},
+                        'LOSS_CLS': {'use_sigmoid': True, 'gamma': 2.0, 'alpha': 0.25}},
+        'POST_PROCESSING': {'SCORE_THRESH': 0.0, 'POST_CENTER_RANGE': [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]}},
+    'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False},
+}
+
 
 def synthetic_dataset(num_point_features=4):
     """The attributes Detector3DTemplate.build_networks reads from a dataset (detector3d_template.py:36-43)."""
@@ -489,3 +526,22 @@ def build_pillarnet(model_cfg=None, num_point_features=4, dataset=None):
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(PILLARNET_CFG if model_cfg is None else model_cfg))
     return build_network(cfg, num_class=len(CLASS_NAMES), dataset=pillarnet_dataset(num_point_features) if dataset is None else dataset)
+
+
+def transfusion_dataset(num_point_features=5, point_cloud_range=None, voxel_size=None, grid_size=None):
+    """TransFusion-L's dataset namespace: ten nuScenes class names on the 108 m x 108 m x 8 m range with 0.075 m voxels unless
+    other values are given; points carry (x, y, z, intensity, time lag)."""
+    return SimpleNamespace(class_names=list(TRANSFUSION_CLASS_NAMES),
+                           grid_size=list(TRANSFUSION_GRID_SIZE if grid_size is None else grid_size),
+                           voxel_size=list(TRANSFUSION_VOXEL_SIZE if voxel_size is None else voxel_size),
+                           point_cloud_range=list(TRANSFUSION_RANGE if point_cloud_range is None else point_cloud_range),
+                           point_feature_encoder=SimpleNamespace(num_point_features=num_point_features))
+
+
+def build_transfusion_lidar(model_cfg=None, num_point_features=5, dataset=None):
+    """TransFusion from TRANSFUSION_LIDAR_CFG (or a dict like it): DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression ->
+    BaseBEVBackbone -> TransFusionHead, on transfusion_dataset() unless another dataset namespace is given.  Runs in eval mode only."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(TRANSFUSION_LIDAR_CFG if model_cfg is None else model_cfg))
+    dataset = transfusion_dataset(num_point_features) if dataset is None else dataset
+    return build_network(cfg, num_class=len(dataset.class_names), dataset=dataset)

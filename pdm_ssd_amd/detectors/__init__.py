@@ -13,6 +13,7 @@ from .pv_rcnn import PVRCNN
 from .pv_rcnn_plusplus import PVRCNNPlusPlus
 from .second_net import SECONDNet
 from .second_net_iou import SECONDNetIoU
+from .transfusion import TransFusion
 from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
@@ -28,6 +29,7 @@ __all__ = {
     'PartA2Net': PartA2Net,
     'SECONDNetIoU': SECONDNetIoU,
     'PillarNet': PillarNet,
+    'TransFusion': TransFusion,
 }
 
 

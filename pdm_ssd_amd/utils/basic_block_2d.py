@@ -1,0 +1,17 @@
+"""BasicBlock2D: convolution, BatchNorm, ReLU under the reference's sub-module names (conv, bn, relu;
+pcdet/models/model_utils/basic_block_2d.py)."""
+import torch.nn as nn
+
+
+class BasicBlock2D(nn.Module):
+    def __init__(self, in_channels, out_channels, **kwargs):
+        """kwargs: nn.Conv2d's (kernel_size, padding, bias, ...)"""
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.conv = nn.Conv2d(in_channels=in_channels, out_channels=out_channels, **kwargs)
+        self.bn = nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=True)
+
+    def forward(self, features):
+        """(B, C_in, H, W) -> (B, C_out, H, W)"""
+        return self.relu(self.bn(self.conv(features)))

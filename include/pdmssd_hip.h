@@ -375,6 +375,49 @@ int pdm_tf_decode(void *stream, int B, int C, int P, const float *heatmap, const
                   const float *query_heatmap_score, float score_thresh, const float *limit_range, float x0, float y0,
                   float vx, float vy, float stride, float *boxes, float *scores, long long *labels, int *count);
 
+/* ---- TransFusionHead in training (csrc/tf_assign.hip): a batched linear-sum-assignment solver, the
+ * Hungarian assigner's costs, matching and targets, and the head's three losses with their gradients.  Nothing synchronises;
+ * no atomics on results except the order-free integer max that merges heat-map gaussians; two runs give the same bits.
+ * pdm_lsap: cost (B, P, >= Gmax) fp32 with row stride row_stride (sample stride P * row_stride), num_gt (B) int32 on the DEVICE
+ *   (clamped to [0, Gmax]).  Per sample, min sum cost over the matchings of size min(P, G) of the P x G leading block: what
+ *   scipy.optimize.linear_sum_assignment returns wherever the optimum is unique.  gt_of_row (B, P) int32 = the matched column or
+ *   -1; row_of_gt (B, Gmax) int32 = the matched row, or -1 (columns >= num_gt[b]; unmatched columns when G > P).  One workgroup
+ *   per sample, shortest augmenting paths (Jonker-Volgenant / Crouse), duals and path lengths in fp64, ties by lower column
+ *   index of the solver's matrix (rows = the smaller side).  Loop bounds: min(P, G) augmentations of at most max(P, G) steps.
+ *   A cost that is not finite (NaN, +Inf, -Inf) is read as FLT_MAX (scipy raises instead).  1 <= P <= 1024, 0 <= Gmax <= 1024,
+ *   anything else is PDM_E_BADARG.
+ * pdm_tf_assign: the maps as pdm_tf_decode takes them; gt_boxes (B, M, gt_cols = 8 | 10) [x y z dx dy dz yaw (vx vy) class],
+ *   class 1-based, zero rows = padding; a box is valid iff dx > 0 && dy > 0, valid boxes keep their order.  cost_cfg HOST
+ *   doubles [cls weight, alpha, gamma, eps, reg weight, iou weight]; pc_range HOST [x0 y0 z0 x1 y1 z1].  cost = focal cost at
+ *   the gt's class + L1 of the range-normalised centres + (- IoU3D) (z read as the box's bottom, as the reference's overlaps()
+ *   does), each times its weight, in fp32; then pdm_lsap's solver; then labels (B, P) int64 = class - 1 | num_classes,
+ *   label_weights (B, P) = 1, bbox_targets / bbox_weights (B, P, 8 | 10), ious (B, P) = the matched pair's IoU in [0, 1],
+ *   assigned (B, P) int32 = index among the sample's valid boxes | -1, num_pos (1) int32, matched_ious (1) = mean over the
+ *   samples of the per-sample mean, heatmap_target (B, C, H, W) = the gaussians of the valid boxes (radius from
+ *   gaussian_overlap and min_radius over (dy, dx) cells, centre cell truncated; a centre cell outside the map draws nothing).
+ *   workspace >= pdm_tf_assign_workspace_bytes(B, P, M), 8-byte aligned.  P <= 1024, M <= 1024.
+ * pdm_tf_loss: SigmoidFocalClassificationLoss(alpha, gamma) of heatmap against the one-hot of labels times label_weights, and
+ *   L1 of [center height dim rot (vel)] against bbox_targets times bbox_weights * code_weights (HOST, 8 | 10), each
+ *   / max(num_pos, 1) (read on the device) times its weight; the dense heat-map term is pdm_heatmap_focal_loss.  out (6) =
+ *   [cls, box, heat-map loss, the factor of g_dense, peaks, unused]; g_heatmap .. g_vel = d loss / d map, final; g_dense =
+ *   d S / d dense_heatmap, to be multiplied by out[3].  workspace >= pdm_tf_loss_workspace_bytes(...), 8-byte aligned. */
+int pdm_lsap(void *stream, int B, int P, int Gmax, const float *cost, long long row_stride, const int *num_gt, int *gt_of_row,
+             int *row_of_gt);
+size_t pdm_tf_assign_workspace_bytes(int B, int P, int M);
+int pdm_tf_assign(void *stream, int B, int C, int P, int M, int gt_cols, int H, int W, const float *heatmap, const float *center,
+                  const float *height, const float *dim, const float *rot, const float *vel, const float *gt_boxes,
+                  const double *cost_cfg, const float *pc_range, float vx, float vy, float stride, double gaussian_overlap,
+                  int min_radius, int num_classes, long long *labels, float *label_weights, float *bbox_targets,
+                  float *bbox_weights, float *ious, int *assigned, int *num_pos, float *matched_ious, float *heatmap_target,
+                  void *workspace, size_t workspace_bytes);
+size_t pdm_tf_loss_workspace_bytes(int B, int C, int P, int with_vel, int H, int W);
+int pdm_tf_loss(void *stream, int B, int C, int P, int H, int W, const float *heatmap, const float *center, const float *height,
+                const float *dim, const float *rot, const float *vel, const float *dense_heatmap, const long long *labels,
+                const float *label_weights, const float *bbox_targets, const float *bbox_weights, const int *num_pos,
+                const float *heatmap_target, const float *code_weights, float cls_weight, float bbox_weight, float hm_weight,
+                float alpha, float gamma, float *out, float *g_heatmap, float *g_center, float *g_height, float *g_dim,
+                float *g_rot, float *g_vel, float *g_dense, void *workspace, size_t workspace_bytes);
+
 /* OPT-IN: the same three-layer per-row MLP with fp32 EMULATED on the bf16 matrix pipe — every fp32 operand split into three
  * bf16 pieces (8 + 8 + 8 significand bits), a product formed from the six leading partial products on
  * v_mfma_f32_16x16x32_bf16 with fp32 accumulation (3/8 of the fp32-MFMA pipe time; dropped terms <= 2^-24 |a b|).

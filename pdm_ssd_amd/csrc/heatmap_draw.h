@@ -1,5 +1,6 @@
 // The gaussian of one ground-truth box on a BEV heat map, shared by pdm_heatmap_targets (heatmap_loss.hip) and
-// pdm_center_targets (center_head.hip), so that both draw the same bits by construction:
+// pdm_center_targets (center_head.hip), so that both draw the same bits by construction; pdm_tf_assign (tf_assign.hip) shares
+// the window (hm_draw_window) under TransFusionHead's own rule for cell and radius (hm_draw_box_unclamped).  hm_draw_box:
 //   cell   = trunc(clamp((x - x0) / vx / stride, 0, W - 0.5)), likewise y
 //   r      = max(int(gaussian_radius(dx cells, dy cells, overlap)), min_radius), sigma = (2 r + 1) / 6
 //   value  = exp(-(ddx^2 + ddy^2) / (2 sigma^2)) inside the (2 r + 1)^2 window, values under fp32 eps dropped,
@@ -48,19 +49,11 @@ __device__ __forceinline__ bool hm_size_cells(const HmGrid &a, float dx, float d
     return *dxc > 0.0f && *dyc > 0.0f;
 }
 
-// Called by all NT threads of a workgroup with the same box: (x, y) centre, (dx, dy) size in metres, cls = class channel
-// + 1 as a float (< 1 = padding); map = the sample's (C, H, W) planes.  Each cell's value depends on the cell alone, so
-// the order in which the threads visit the window does not matter.
+// The (2 r + 1)^2 window of radius r around cell (ix, iy) on class plane c, max-merged; called by all NT threads of a
+// workgroup with the same arguments.  Each cell's value depends on the cell alone, so the order in which the threads visit
+// the window does not matter.
 template <int NT>
-__device__ __forceinline__ void hm_draw_box(const HmGrid &a, float x, float y, float dx, float dy, float cls, float *map) {
-    float dxc, dyc, cx, cy;
-    if (!hm_size_cells(a, dx, dy, &dxc, &dyc) || !(cls >= 1.0f)) return;   // padding / degenerate box (uniform over the workgroup)
-    const int c = (int)cls - 1;
-    if (c >= a.C) return;
-    hm_center_cells(a, x, y, &cx, &cy);
-    const int ix = (int)cx, iy = (int)cy;
-    int r = (int)hm_gaussian_radius(dxc, dyc, a.min_overlap);     // (height, width) = (dx, dy) cells as the head passes them
-    if (r < a.min_radius) r = a.min_radius;
+__device__ __forceinline__ void hm_draw_window(const HmGrid &a, int ix, int iy, int r, int c, float *map) {
     const float rt = (float)r;
     const int rw = r < a.max_radius ? r : a.max_radius;
     const float sigma = __fmul_rn(__fadd_rn(__fmul_rn(2.0f, rt), 1.0f), __fdiv_rn(1.0f, 6.0f));
@@ -75,6 +68,38 @@ __device__ __forceinline__ void hm_draw_box(const HmGrid &a, float x, float y, f
         if (v < 1.1920928955078125e-07f) continue;               // h[h < eps * h.max()] = 0 (the window's maximum is 1)
         atomicMax(plane + (size_t)py * a.W + px, __float_as_int(v));
     }
+}
+
+// Called by all NT threads of a workgroup with the same box: (x, y) centre, (dx, dy) size in metres, cls = class channel
+// + 1 as a float (< 1 = padding); map = the sample's (C, H, W) planes.  Each cell's value depends on the cell alone, so
+// the order in which the threads visit the window does not matter.
+template <int NT>
+__device__ __forceinline__ void hm_draw_box(const HmGrid &a, float x, float y, float dx, float dy, float cls, float *map) {
+    float dxc, dyc, cx, cy;
+    if (!hm_size_cells(a, dx, dy, &dxc, &dyc) || !(cls >= 1.0f)) return;   // padding / degenerate box (uniform over the workgroup)
+    const int c = (int)cls - 1;
+    if (c >= a.C) return;
+    hm_center_cells(a, x, y, &cx, &cy);
+    int r = (int)hm_gaussian_radius(dxc, dyc, a.min_overlap);     // (height, width) = (dx, dy) cells as the head passes them
+    if (r < a.min_radius) r = a.min_radius;
+    hm_draw_window<NT>(a, (int)cx, (int)cy, r, c, map);
+}
+
+// TransFusionHead's rule for the same gaussian (pdm_tf_assign, tf_assign.hip): the centre cell is the TRUNCATED, unclamped
+// (x - x0) / vx / stride, and a box whose centre cell lies outside the map draws nothing; the radius takes (height, width) =
+// (dy, dx) cells, as that head passes them.  Same calling convention as hm_draw_box.
+template <int NT>
+__device__ __forceinline__ void hm_draw_box_unclamped(const HmGrid &a, float x, float y, float dx, float dy, float cls, float *map) {
+    float dxc, dyc;
+    if (!hm_size_cells(a, dx, dy, &dxc, &dyc) || !(cls >= 1.0f)) return;
+    const int c = (int)cls - 1;
+    if (c >= a.C) return;
+    const float ivx = __fdiv_rn(1.0f, a.vx), ivy = __fdiv_rn(1.0f, a.vy), is = __fdiv_rn(1.0f, a.stride);
+    const float cx = __fmul_rn(__fmul_rn(x - a.x0, ivx), is), cy = __fmul_rn(__fmul_rn(y - a.y0, ivy), is);
+    if (!(cx > -1.0f && cx < (float)a.W && cy > -1.0f && cy < (float)a.H)) return;       // trunc(c) in [0, n); NaN draws nothing
+    int r = (int)fminf(hm_gaussian_radius(dyc, dxc, a.min_overlap), 1e9f);
+    if (r < a.min_radius) r = a.min_radius;
+    hm_draw_window<NT>(a, (int)cx, (int)cy, r, c, map);
 }
 
 }  // namespace pdm

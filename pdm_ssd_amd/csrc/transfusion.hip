@@ -16,6 +16,7 @@
 //                    block scan, padding rows zeroed
 #include "loss_kit.h"
 #include "rank_select.h"
+#include "tf_decode.h"
 
 namespace pdm {
 
@@ -130,14 +131,7 @@ __global__ __launch_bounds__(TF_T) void tf_decode_kernel(TfdArgs a) {
             c = c < 0 ? 0 : c >= a.C ? a.C - 1 : c;
             const size_t at = ((size_t)b * a.C + c) * P + p;
             score = __fmul_rn(sigmoid_rn(a.heatmap[at]), a.qhs[at]);
-            const float *ctr = a.center + (size_t)b * 2 * P + p, *dm = a.dim + (size_t)b * 3 * P + p, *rt = a.rot + (size_t)b * 2 * P + p;
-            box[0] = __fadd_rn(__fmul_rn(__fmul_rn(ctr[0], a.stride), a.vx), a.x0);
-            box[1] = __fadd_rn(__fmul_rn(__fmul_rn(ctr[P], a.stride), a.vy), a.y0);
-            box[2] = a.height[(size_t)b * P + p];
-            box[3] = expf(dm[0]); box[4] = expf(dm[P]); box[5] = expf(dm[2 * P]);
-            box[6] = atan2f(rt[0], rt[P]);                            // [sin, cos]
-            box[7] = box[8] = 0.0f;
-            if (a.E == 2) { box[7] = a.vel[(size_t)b * 2 * P + p]; box[8] = a.vel[(size_t)b * 2 * P + P + p]; }
+            tf_decode_box(TfBoxMaps{P, a.E, a.center, a.height, a.dim, a.rot, a.vel, a.x0, a.y0, a.vx, a.vy, a.stride}, b, p, box);
             keep = score > a.score_thresh;
 #pragma unroll
             for (int d = 0; d < 3; ++d) keep = keep && box[d] >= a.lo[d] && box[d] <= a.hi[d];

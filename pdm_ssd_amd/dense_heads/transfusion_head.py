@@ -1,4 +1,4 @@
-"""TransFusionHead (LiDAR branch, inference): BEV map -> heat-map queries -> one transformer decoder layer -> boxes, the
+"""TransFusionHead (LiDAR branch): BEV map -> heat-map queries -> one transformer decoder layer -> boxes, the
 reference's pcdet/models/dense_heads/transfusion_head.py on this repository's operators.
 
 Constructor signature, config keys, initialisation and state_dict keys (shared_conv.*, heatmap_head.{0.conv,0.bn,1}.*,
@@ -13,8 +13,13 @@ On the CPU (and with use_fused = False) the torch formulations next to those ope
 The key positional embedding is the same for every sample in eval mode: it is computed for one sample per call and
 broadcast (it is not cached across calls).
 
-Training is out of scope: it needs the Hungarian assigner (the reference calls scipy's linear_sum_assignment on the host
-per sample), so forward() in training mode raises NotImplementedError and the constructor builds no assigner.
+Training is opt-in by a key of this build, TARGET_ASSIGNER_CONFIG.ASSIGN_ON_DEVICE.  Without it forward() in training mode
+raises NotImplementedError and the constructor builds no assigner.  With it the constructor builds bbox_assigner
+(HungarianAssigner3D) and reads the loss weights; forward() in training mode runs predict under autograd (the decoder through
+nn.MultiheadAttention with its dropout; query_heatmap_score carries no gradient), then transfusion_ops.assign and
+transfusion_ops.loss for the whole batch with no host read (the reference walks the samples, calls scipy's
+linear_sum_assignment on the host and ends in four .item() calls), and sets batch_dict['loss'] and batch_dict['tb_dict']
+(detached device tensors).  On the CPU assign_torch and loss_torch run instead.
 """
 import copy
 
@@ -92,6 +97,20 @@ class TransFusionHead(nn.Module):
         self.register_buffer('bev_pos', torch.stack((n % y_size, n // y_size), dim=-1).float()[None] + 0.5, persistent=False)
         self.use_fused = True                       # False: the torch formulations on any device
         self.forward_ret_dict = {}
+        # the training half is opt-in: without the key the head is the eval-only head (no assigner, training refused)
+        self.assign_on_device = bool(_get(assigner_cfg, 'ASSIGN_ON_DEVICE', False))
+        if self.assign_on_device:
+            from .target_assigner.hungarian_assigner import HungarianAssigner3D
+            costs = _get(assigner_cfg, 'HUNGARIAN_ASSIGNER')
+            self.bbox_assigner = HungarianAssigner3D(**{k: dict(_get(costs, k)) for k in ('cls_cost', 'reg_cost', 'iou_cost')})
+            weights = _get(_get(model_cfg, 'LOSS_CONFIG'), 'LOSS_WEIGHTS')
+            self.loss_cls_weight, self.loss_bbox_weight = _get(weights, 'cls_weight'), _get(weights, 'bbox_weight')
+            self.loss_heatmap_weight, self.code_weights = _get(weights, 'hm_weight'), list(_get(weights, 'code_weights'))
+            self.loss_cls_alpha, self.loss_cls_gamma = float(_get(loss_cls, 'alpha')), float(_get(loss_cls, 'gamma'))
+            self.head_order = list(_get(_get(model_cfg, 'SEPARATE_HEAD_CFG'), 'HEAD_ORDER'))
+            if tuple(self.head_order) != transfusion_ops.HEAD_ORDER[:len(self.head_order)] or len(self.head_order) < 4:
+                raise ValueError(f'HEAD_ORDER {self.head_order}: training needs the order of the box code, {list(transfusion_ops.HEAD_ORDER)}')
+            self.gaussian_overlap, self.min_radius = _get(assigner_cfg, 'GAUSSIAN_OVERLAP'), _get(assigner_cfg, 'MIN_RADIUS')
 
     def init_weights(self):
         for p in self.decoder.parameters():
@@ -142,7 +161,59 @@ class TransFusionHead(nn.Module):
         counts = count.tolist()                                       # the one device-to-host read
         return [{'pred_boxes': boxes[k, :n], 'pred_scores': scores[k, :n], 'pred_labels': labels[k, :n].int()} for k, n in enumerate(counts)]
 
+    # ---- training (TARGET_ASSIGNER_CONFIG.ASSIGN_ON_DEVICE) ------------------------------------------------------------------
+    def _assign_args(self):
+        a = self.bbox_assigner
+        H, W = int(self.grid_size[1]) // self.feature_map_stride, int(self.grid_size[0]) // self.feature_map_stride
+        return (a.cls_cost, a.reg_cost, a.iou_cost, list(self.point_cloud_range), list(self.voxel_size), self.feature_map_stride, (H, W),
+                self.gaussian_overlap, self.min_radius, self.num_classes)
+
+    def encode_bbox(self, bboxes):
+        return transfusion_ops.encode_bbox_torch(bboxes, self.point_cloud_range, self.voxel_size, self.feature_map_stride,
+                                                 10 if bboxes.shape[1] >= 9 else 8)
+
+    def _targets(self, gt_boxes, pred_dicts):
+        """gt_boxes (B, M, 8 | 10) with the 1-based class last -> transfusion_ops.assign's dict: one launch chain for the batch
+        on the GPU, the per-sample torch formulation elsewhere"""
+        fn = transfusion_ops.assign if self._on_device(pred_dicts['heatmap']) else transfusion_ops.assign_torch
+        return fn(*[pred_dicts[k] for k in ('heatmap', 'center', 'height', 'dim', 'rot')], pred_dicts.get('vel', None), gt_boxes,
+                  *self._assign_args())
+
+    def get_targets(self, gt_bboxes_3d, gt_labels_3d, pred_dicts):
+        """the reference's tuple (labels, label_weights, bbox_targets, bbox_weights, num_pos, matched_ious, heatmap); num_pos and
+        matched_ious stay 0-dim tensors on the device"""
+        gt_boxes = torch.cat([gt_bboxes_3d, (gt_labels_3d + 1).to(gt_bboxes_3d.dtype).unsqueeze(-1)], dim=-1)
+        t = self._targets(gt_boxes, pred_dicts)
+        return t['labels'], t['label_weights'], t['bbox_targets'], t['bbox_weights'], t['num_pos'], t['matched_ious'], t['heatmap']
+
+    def get_targets_single(self, gt_bboxes_3d, gt_labels_3d, preds_dict):
+        """one sample: gt_bboxes_3d (G, 7 | 9), gt_labels_3d (G) 0-based, preds_dict of (1, c, P) maps -> get_targets' tuple"""
+        return self.get_targets(gt_bboxes_3d[None], gt_labels_3d[None], preds_dict)
+
+    def loss(self, gt_bboxes_3d, gt_labels_3d, pred_dicts, **kwargs):
+        """-> (loss_trans, tb_dict); every entry of tb_dict is a detached tensor on the device (no .item())"""
+        gt_boxes = torch.cat([gt_bboxes_3d, (gt_labels_3d + 1).to(gt_bboxes_3d.dtype).unsqueeze(-1)], dim=-1)
+        return self._loss(gt_boxes, pred_dicts)
+
+    def _loss(self, gt_boxes, pred_dicts):
+        targets = self._targets(gt_boxes, pred_dicts)
+        fn = transfusion_ops.loss if self._on_device(pred_dicts['heatmap']) else transfusion_ops.loss_torch
+        loss_cls, loss_bbox, loss_heatmap = fn(
+            *[pred_dicts[k] for k in ('heatmap', 'center', 'height', 'dim', 'rot')], pred_dicts.get('vel', None), pred_dicts['dense_heatmap'],
+            targets, self.code_weights, self.loss_cls_weight, self.loss_bbox_weight, self.loss_heatmap_weight, self.loss_cls_alpha,
+            self.loss_cls_gamma)
+        loss_all = loss_heatmap + loss_cls + loss_bbox
+        tb_dict = {'loss_heatmap': loss_heatmap.detach(), 'loss_cls': loss_cls.detach(), 'loss_bbox': loss_bbox.detach(),
+                   'matched_ious': targets['matched_ious'], 'loss_trans': loss_all.detach()}
+        self.forward_ret_dict['targets'] = targets
+        return loss_all, tb_dict
+
     def forward(self, batch_dict):
+        if self.training and self.assign_on_device:
+            res = self.predict(batch_dict['spatial_features_2d'])       # under autograd; the queries carry no gradient
+            self.forward_ret_dict['pred_dicts'] = res
+            batch_dict['loss'], batch_dict['tb_dict'] = self._loss(batch_dict['gt_boxes'], res)
+            return batch_dict
         if self.training:
             raise NotImplementedError('TransFusionHead: training needs the Hungarian assigner (HungarianAssigner3D), which this '
                                       'build does not have; the head runs in eval mode only')

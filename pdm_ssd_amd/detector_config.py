@@ -353,8 +353,8 @@ PILLARNET_TRAIN_CFG = copy.deepcopy(PILLARNET_CFG)
 # [-54, 54] m x [-54, 54] m x [-5, 3] m on 0.075 x 0.075 x 0.2 m voxels (grid 1440 x 1440 x 40, a 180 x 180 map at stride 8),
 # mean VFE -> VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone (512 channels out) -> TransFusionHead with 200 queries,
 # 128 hidden channels, 8 attention heads, a 256-wide feed-forward block and a 3 x 3 local-maximum filter.  The encoder is
-# DynamicMeanVFE, as in every voxel detector of this build (the plain NAME MeanVFE stays refused, vfe/__init__.py).  Eval only:
-# the head has no training half, so the LOSS_CONFIG and assigner values are carried for the record alone.
+# DynamicMeanVFE, as in every voxel detector of this build (the plain NAME MeanVFE stays refused, vfe/__init__.py).  This dict
+# is eval only: its head reads neither LOSS_CONFIG nor the assigner values; TRANSFUSION_LIDAR_TRAIN_CFG below adds the training half.
 TRANSFUSION_CLASS_NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle',
                            'pedestrian', 'traffic_cone']
 TRANSFUSION_RANGE = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
@@ -384,6 +384,10 @@ TRANSFUSION_LIDAR_CFG = {
         'POST_PROCESSING': {'SCORE_THRESH': 0.0, 'POST_CENTER_RANGE': [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]}},
     'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False},
 }
+# the same detector with the head's training half: ASSIGN_ON_DEVICE is a key of this build (the reference has none like it);
+# with it the head builds its HungarianAssigner3D and reads LOSS_CONFIG, without it the head is the eval-only one above
+TRANSFUSION_LIDAR_TRAIN_CFG = copy.deepcopy(TRANSFUSION_LIDAR_CFG)
+TRANSFUSION_LIDAR_TRAIN_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['ASSIGN_ON_DEVICE'] = True
 
 
 def synthetic_dataset(num_point_features=4):
@@ -539,8 +543,9 @@ def transfusion_dataset(num_point_features=5, point_cloud_range=None, voxel_size
 
 
 def build_transfusion_lidar(model_cfg=None, num_point_features=5, dataset=None):
-    """TransFusion from TRANSFUSION_LIDAR_CFG (or a dict like it): DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression ->
-    BaseBEVBackbone -> TransFusionHead, on transfusion_dataset() unless another dataset namespace is given.  Runs in eval mode only."""
+    """TransFusion from TRANSFUSION_LIDAR_CFG (eval mode only), TRANSFUSION_LIDAR_TRAIN_CFG (with the head's training half) or a
+    dict like them: DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone -> TransFusionHead, on
+    transfusion_dataset() unless another dataset namespace is given."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(TRANSFUSION_LIDAR_CFG if model_cfg is None else model_cfg))
     dataset = transfusion_dataset(num_point_features) if dataset is None else dataset

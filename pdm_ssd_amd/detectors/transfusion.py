@@ -1,7 +1,9 @@
-"""TransFusion (LiDAR branch): voxel backbone -> BEV neck -> TransFusionHead, the forward and post_processing of the
-reference's pcdet/models/detectors/transfusion.py on this repository's template.  The head has already decoded its boxes
-(final_box_dicts; a transformer head needs no NMS); post_processing only adds the recall record.  Eval mode only: the head
-has no training half yet (dense_heads/transfusion_head.py).
+"""TransFusion (LiDAR branch): voxel backbone -> BEV neck -> TransFusionHead, the forward, get_training_loss and
+post_processing of the reference's pcdet/models/detectors/transfusion.py on this repository's template.  The head has
+already decoded its boxes (final_box_dicts; a transformer head needs no NMS); post_processing only adds the recall record.
+Training needs a head built with TARGET_ASSIGNER_CONFIG.ASSIGN_ON_DEVICE (detector_config.TRANSFUSION_LIDAR_TRAIN_CFG);
+without it the head refuses training mode (dense_heads/transfusion_head.py).  The training forward reads nothing back to
+the host: the loss and every entry of tb_dict are tensors on the device.
 """
 from .detector3d_template import Detector3DTemplate, _get
 
@@ -12,12 +14,18 @@ class TransFusion(Detector3DTemplate):
         self.module_list = self.build_networks()
 
     def forward(self, batch_dict):
-        """eval: (pred_dicts, recall_dict)"""
+        """eval: (pred_dicts, recall_dict); training: ({'loss': loss}, tb_dict, disp_dict)"""
         for cur_module in self.module_list:
             batch_dict = cur_module(batch_dict)
-        if self.training:       # (the head has raised already)
-            raise NotImplementedError('TransFusion runs in eval mode only')
+        if self.training:       # (a head without the training half has raised already)
+            loss, tb_dict, disp_dict = self.get_training_loss(batch_dict)
+            return {'loss': loss}, tb_dict, disp_dict
         return self.post_processing(batch_dict)
+
+    def get_training_loss(self, batch_dict):
+        loss_trans, tb_dict = batch_dict['loss'], batch_dict['tb_dict']
+        tb_dict = {'loss_trans': loss_trans.detach(), **tb_dict}
+        return loss_trans, tb_dict, {}
 
     def post_processing(self, batch_dict):
         thresh_list = _get(_get(self.model_cfg, 'POST_PROCESSING'), 'RECALL_THRESH_LIST')

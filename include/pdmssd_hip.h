@@ -366,6 +366,39 @@ size_t pdm_mha_forward_workspace_bytes(int B, int P, int N, int C, int nheads, i
 int pdm_mha_forward(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
                     const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
                     float *out, void *workspace, size_t workspace_bytes);
+/* ---- Training through the fused attention (csrc/attention.hip, csrc/attention_bwd.hip).  Nothing
+ * synchronises, nothing is read on the host, no float atomics: two runs give the same bits; capturable after one warm-up call.
+ *
+ * Attention dropout (csrc/draws.h): weight (b, h, query i, key j) is kept iff
+ *   fmix32(draw_key(seed, step, b * H + h, i) ^ j * 0x9E3779B1) >= floor(dropout_p * 2^32),  0 <= dropout_p < 1,
+ *   and a kept weight is multiplied by 1.0f / (1.0f - (float)dropout_p).  The softmax sum is the sum before dropout.
+ *   dropout_p == 0: no draw is evaluated, step and used_step are not touched and may be NULL.
+ * pdm_mha_forward_train: pdm_mha_forward (the same device code) plus the dropout and stats (B, H, P, 2) = the query's RAW
+ *   score maximum over all keys and its softmax sum.  step: a device-resident counter; the call reads it, copies the value it
+ *   used to used_step[0] (device) and advances it by one in its last launch.  With dropout_p == 0 `out` is pdm_mha_forward's
+ *   bit for bit.  workspace >= pdm_mha_forward_train_workspace_bytes(...), 8-byte aligned.
+ * pdm_mha_backward: q, k, v as the forward took them, out (B, P, C) and dout (B, P, C) contiguous, stats and used_step from the
+ *   forward -> dq (B, P, C), dk (B, N, C), dv (B, N, C), each with its OWN row stride (dk and dv may be the halves of one
+ *   (B, N, 2C) buffer; dq, dk, dv the thirds of a (B, P, 3C) one).  Key-stationary: a workgroup owns
+ *   pdm_mha_backward_keys_per_block(N, keys_per_chunk) keys (16, 64 or 256) and walks the query tiles in ascending order, so dk
+ *   and dv have one writer and one summation order; dq goes through one partial per key block in the workspace, folded in
+ *   block order by a last launch.  The supported set is the forward's; a short workspace is refused.  align: any (16-byte
+ *   accesses only when every buffer is 16-byte aligned with strides % 4 == 0).
+ * pdm_mha_dropout_keep: keep (B, nheads, P, N) uint8 = the mask of step[0] (a device pointer; not advanced). */
+size_t pdm_mha_forward_train_workspace_bytes(int B, int P, int N, int C, int nheads, int keys_per_chunk);
+int pdm_mha_forward_train(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
+                          const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
+                          double dropout_p, unsigned seed, unsigned *step, unsigned *used_step, float *stats,
+                          float *out, void *workspace, size_t workspace_bytes);
+int pdm_mha_backward_keys_per_block(int N, int keys_per_chunk);
+size_t pdm_mha_backward_workspace_bytes(int B, int P, int N, int C, int nheads, int keys_per_chunk);
+int pdm_mha_backward(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
+                     const float *k, long long k_stride, const float *v, long long v_stride, const float *out,
+                     const float *dout, const float *stats, double dropout_p, unsigned seed,
+                     const unsigned *used_step, int keys_per_chunk, float *dq, long long dq_stride, float *dk,
+                     long long dk_stride, float *dv, long long dv_stride, void *workspace, size_t workspace_bytes);
+int pdm_mha_dropout_keep(void *stream, int B, int nheads, int P, int N, double dropout_p, unsigned seed,
+                         const unsigned *step, unsigned char *keep);
 size_t pdm_tf_proposals_workspace_bytes(int B, int C, int H, int W, int P);
 int pdm_tf_proposals(void *stream, int B, int C, int H, int W, const float *logits, int nms_kernel, int num_exempt,
                      const int *exempt, int P, int y_size, long long *index, long long *cls,

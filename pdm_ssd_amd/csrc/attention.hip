@@ -22,17 +22,19 @@
 //
 // The chunking depends on (N, keys_per_chunk) alone, there is no atomic and no LDS: two runs give the same bits.  A
 // single key gives out = its v row bit for bit (p = exp2(0) = 1, fma(v, 1, 0) = v, v / 1 = v).
-#include "common.h"
+//
+// The training forward (pdm_mha_forward_train) is the same device code with TRAIN = true: the attention dropout multiplies
+// the weights that enter the P V product (draws.h: attn_keep), the softmax sum stays the sum before dropout, and the combine
+// kernel also writes the query's (raw maximum, sum) for the backward (attention_bwd.hip) and advances the step counter.
+#include "attention.h"
+#include "draws.h"
 
 namespace pdm {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MHA_T = 256;          // 4 waves
 constexpr int MHA_QW = 16;          // queries per wave
 constexpr int MHA_QB = 64;          // queries per workgroup
 constexpr int MHA_KT = 64;          // keys per step of a wave: 4 tiles of 16
-constexpr int MHA_DEFAULT_CHUNK = 1024;
 
 struct MhaArgs {
     int B, P, N, C, H, kpc, nchunk, vec;
@@ -42,16 +44,15 @@ struct MhaArgs {
     float *ml;                       // (B, H, nchunk, P, 2): raw maximum, sum
     float *acc;                      // (B, H, nchunk, P, d)
     float *out;                      // (B, P, C)
+    // TRAIN only
+    int drop;                        // dropout_p > 0
+    unsigned thresh, seed;           // floor(p 2^32); the draws' seed
+    float rinv;                      // 1 / (1 - p)
+    unsigned *step, *used_step;      // the device step counter and the copy of the value this call used
+    float *stats;                    // (B, H, P, 2): raw maximum over all keys, softmax sum
 };
 
-__device__ __forceinline__ f32x4 mha_load4(const float *p, int vec) {
-    if (vec) return *reinterpret_cast<const f32x4 *>(p);
-    f32x4 r;
-    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3];
-    return r;
-}
-
-template <int D>
+template <int D, bool TRAIN>
 __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
     constexpr int DT = D / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, grp = lane >> 4;
@@ -71,6 +72,10 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
 #pragma unroll
     for (int t = 0; t < DT; ++t) { acc[t][0] = f32x4{0, 0, 0, 0}; acc[t][1] = f32x4{0, 0, 0, 0}; }
     float m = -INFINITY, lsum = 0.0f;
+    unsigned dkey = 0;
+    if constexpr (TRAIN) {
+        if (a.drop) dkey = draw_key(a.seed, a.step[0], (unsigned)blockIdx.z, (unsigned)(q0 + col));
+    }
 
     for (int kt = k_lo; kt < k_hi; kt += MHA_KT) {
         f32x4 s[4];
@@ -108,6 +113,15 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
             }
         lsum = lsum * alpha + psum;
         m = m_new;
+        if constexpr (TRAIN) {
+            if (a.drop) {                                            // the sum above is the one before dropout
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        s[j][r] = attn_keep(dkey, (unsigned)(kt + 16 * j + 4 * grp + r), a.thresh) ? s[j][r] * a.rinv : 0.0f;
+            }
+        }
 #pragma unroll
         for (int t = 0; t < DT; ++t) { acc[t][0] *= alpha; acc[t][1] *= alpha; }
 #pragma unroll
@@ -135,8 +149,16 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
     }
 }
 
+template <bool TRAIN>
 __global__ __launch_bounds__(MHA_T) void mha_combine_kernel(MhaArgs a, int D) {
     const long long i = (long long)blockIdx.x * MHA_T + threadIdx.x;
+    if constexpr (TRAIN) {
+        if (a.drop && i == 0) {                                      // the partial launch has read the counter: advance it
+            const unsigned s = a.step[0];
+            a.used_step[0] = s;
+            a.step[0] = s + 1u;
+        }
+    }
     if (i >= (long long)a.B * a.P * a.C) return;
     const int ch = (int)(i % a.C), h = ch / D, dd = ch - h * D;
     const long long bp = i / a.C;
@@ -152,14 +174,22 @@ __global__ __launch_bounds__(MHA_T) void mha_combine_kernel(MhaArgs a, int D) {
         den += w * a.ml[2 * row + 1];
     }
     a.out[i] = num / den;
+    if constexpr (TRAIN) {
+        if (dd == 0) {
+            float *st = a.stats + 2 * (((size_t)b * a.H + h) * a.P + p);
+            st[0] = M;
+            st[1] = den;
+        }
+    }
 }
 
-static int mha_chunk(int keys_per_chunk) { return keys_per_chunk > 0 ? keys_per_chunk : MHA_DEFAULT_CHUNK; }
-
-static bool mha_supported(int B, int P, int N, int C, int nheads, int keys_per_chunk) {
-    if (B < 0 || P < 1 || N < 1 || C < 1 || C > 256 || nheads < 1 || keys_per_chunk < 0 || C % nheads != 0) return false;
-    const int d = C / nheads;
-    return d == 16 || d == 32;
+__global__ __launch_bounds__(MHA_T) void mha_keep_kernel(int H, int P, int N, long long total, unsigned thresh, unsigned seed,
+                                                         const unsigned *step, unsigned char *keep) {
+    const long long i = (long long)blockIdx.x * MHA_T + threadIdx.x;
+    if (i >= total) return;
+    const unsigned j = (unsigned)(i % N);
+    const long long r = i / N;
+    keep[i] = attn_keep(draw_key(seed, step[0], (unsigned)(r / P), (unsigned)(r % P)), j, thresh) ? 1 : 0;
 }
 
 }  // namespace pdm
@@ -175,33 +205,80 @@ extern "C" size_t pdm_mha_forward_workspace_bytes(int B, int P, int N, int C, in
     return align256((size_t)B * nheads * nchunk * P * 2 * sizeof(float)) + (size_t)B * nchunk * P * C * sizeof(float);
 }
 
-extern "C" int pdm_mha_forward(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
-                               const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
-                               float *out, void *workspace, size_t workspace_bytes) {
+extern "C" size_t pdm_mha_forward_train_workspace_bytes(int B, int P, int N, int C, int nheads, int keys_per_chunk) {
+    return pdm_mha_forward_workspace_bytes(B, P, N, C, nheads, keys_per_chunk);
+}
+
+// the two launches of the forward; train: the dropout parameters and stats of `a` are set
+static int mha_forward_launch(const char *who, void *stream, bool train, MhaArgs a, int B, int P, int N, int C, int nheads,
+                              const float *q, long long q_stride, const float *k, long long k_stride, const float *v,
+                              long long v_stride, int keys_per_chunk, float *out, void *workspace, size_t workspace_bytes) {
     PDM_REQUIRE(mha_supported(B, P, N, C, nheads, keys_per_chunk), PDM_E_BADARG,
-                "mha_forward: B = %d, P = %d, N = %d, C = %d, heads = %d, keys_per_chunk = %d: needs P, N >= 1, C <= 256 and "
-                "C / heads in {16, 32}", B, P, N, C, nheads, keys_per_chunk);
-    PDM_REQUIRE(q_stride >= C && k_stride >= C && v_stride >= C, PDM_E_BADARG, "mha_forward: a row stride below C = %d", C);
+                "%s: B = %d, P = %d, N = %d, C = %d, heads = %d, keys_per_chunk = %d: needs P, N >= 1, C <= 256 and "
+                "C / heads in {16, 32}", who, B, P, N, C, nheads, keys_per_chunk);
+    PDM_REQUIRE(q_stride >= C && k_stride >= C && v_stride >= C, PDM_E_BADARG, "%s: a row stride below C = %d", who, C);
     if (B == 0) return 0;
-    PDM_REQUIRE(q && k && v && out && workspace, PDM_E_BADARG, "mha_forward: null pointer");
+    PDM_REQUIRE(q && k && v && out && workspace, PDM_E_BADARG, "%s: null pointer", who);
     const int kpc = mha_chunk(keys_per_chunk), nchunk = divup(N, kpc), d = C / nheads;
     PDM_REQUIRE(nchunk <= 65535 && (long long)B * nheads <= 65535 && (long long)B * P * C <= 0x7fffffffll, PDM_E_TOOLARGE,
-                "mha_forward: %d key chunks x %lld sample-heads exceed the grid", nchunk, (long long)B * nheads);
+                "%s: %d key chunks x %lld sample-heads exceed the grid", who, nchunk, (long long)B * nheads);
     const size_t need = pdm_mha_forward_workspace_bytes(B, P, N, C, nheads, keys_per_chunk);
     PDM_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, PDM_E_BADARG,
-                "mha_forward: workspace of %zu bytes, need %zu (8-byte aligned)", workspace_bytes, need);
-    MhaArgs a{};
+                "%s: workspace of %zu bytes, need %zu (8-byte aligned)", who, workspace_bytes, need);
     a.B = B; a.P = P; a.N = N; a.C = C; a.H = nheads; a.kpc = kpc; a.nchunk = nchunk;
     a.q = q; a.k = k; a.v = v; a.qs = q_stride; a.ks = k_stride; a.vs = v_stride;
-    a.vec = ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0 && q_stride % 4 == 0 && k_stride % 4 == 0;
+    a.vec = mha_aligned16(q) && mha_aligned16(k) && q_stride % 4 == 0 && k_stride % 4 == 0;
     a.c = (float)(1.4426950408889634 / sqrt((double)d));
     a.ml = static_cast<float *>(workspace);
     a.acc = reinterpret_cast<float *>(static_cast<char *>(workspace) + align256((size_t)B * nheads * nchunk * P * 2 * sizeof(float)));
     a.out = out;
     const dim3 grid((unsigned)divup(P, MHA_QB), (unsigned)nchunk, (unsigned)(B * nheads));
-    if (d == 16) hipLaunchKernelGGL(mha_partial_kernel<16>, grid, dim3(MHA_T), 0, as_stream(stream), a);
-    else hipLaunchKernelGGL(mha_partial_kernel<32>, grid, dim3(MHA_T), 0, as_stream(stream), a);
-    if (int rc = check_launch("mha_forward(partial)")) return rc;
-    hipLaunchKernelGGL(mha_combine_kernel, dim3((unsigned)divup((long long)B * P * C, MHA_T)), dim3(MHA_T), 0, as_stream(stream), a, d);
-    return check_launch("mha_forward(combine)");
+    const dim3 cgrid((unsigned)divup((long long)B * P * C, MHA_T));
+    hipStream_t s = as_stream(stream);
+    if (train) {
+        if (d == 16) hipLaunchKernelGGL((mha_partial_kernel<16, true>), grid, dim3(MHA_T), 0, s, a);
+        else hipLaunchKernelGGL((mha_partial_kernel<32, true>), grid, dim3(MHA_T), 0, s, a);
+    } else {
+        if (d == 16) hipLaunchKernelGGL((mha_partial_kernel<16, false>), grid, dim3(MHA_T), 0, s, a);
+        else hipLaunchKernelGGL((mha_partial_kernel<32, false>), grid, dim3(MHA_T), 0, s, a);
+    }
+    if (int rc = check_launch(who)) return rc;
+    if (train) hipLaunchKernelGGL(mha_combine_kernel<true>, cgrid, dim3(MHA_T), 0, s, a, d);
+    else hipLaunchKernelGGL(mha_combine_kernel<false>, cgrid, dim3(MHA_T), 0, s, a, d);
+    return check_launch(who);
+}
+
+extern "C" int pdm_mha_forward(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
+                               const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
+                               float *out, void *workspace, size_t workspace_bytes) {
+    return mha_forward_launch("mha_forward", stream, false, MhaArgs{}, B, P, N, C, nheads, q, q_stride, k, k_stride, v, v_stride,
+                              keys_per_chunk, out, workspace, workspace_bytes);
+}
+
+extern "C" int pdm_mha_forward_train(void *stream, int B, int P, int N, int C, int nheads, const float *q, long long q_stride,
+                                     const float *k, long long k_stride, const float *v, long long v_stride, int keys_per_chunk,
+                                     double dropout_p, unsigned seed, unsigned *step, unsigned *used_step, float *stats,
+                                     float *out, void *workspace, size_t workspace_bytes) {
+    PDM_REQUIRE(mha_dropout_ok(dropout_p), PDM_E_BADARG, "mha_forward_train: dropout_p = %g outside [0, 1)", dropout_p);
+    MhaArgs a{};
+    a.drop = dropout_p > 0.0;
+    PDM_REQUIRE(B == 0 || stats, PDM_E_BADARG, "mha_forward_train: null stats");
+    PDM_REQUIRE(B == 0 || !a.drop || (step && used_step), PDM_E_BADARG, "mha_forward_train: dropout_p > 0 needs step and used_step");
+    a.thresh = mha_dropout_thresh(dropout_p); a.rinv = mha_dropout_rinv(dropout_p); a.seed = seed;
+    a.step = step; a.used_step = used_step; a.stats = stats;
+    return mha_forward_launch("mha_forward_train", stream, true, a, B, P, N, C, nheads, q, q_stride, k, k_stride, v, v_stride,
+                              keys_per_chunk, out, workspace, workspace_bytes);
+}
+
+extern "C" int pdm_mha_dropout_keep(void *stream, int B, int nheads, int P, int N, double dropout_p, unsigned seed,
+                                    const unsigned *step, unsigned char *keep) {
+    PDM_REQUIRE(B >= 0 && nheads >= 1 && P >= 1 && N >= 1 && mha_dropout_ok(dropout_p), PDM_E_BADARG,
+                "mha_dropout_keep: B = %d, heads = %d, P = %d, N = %d, dropout_p = %g", B, nheads, P, N, dropout_p);
+    const long long total = (long long)B * nheads * P * N;
+    if (total == 0) return 0;
+    PDM_REQUIRE(step && keep, PDM_E_BADARG, "mha_dropout_keep: null pointer");
+    PDM_REQUIRE(divup(total, MHA_T) > 0 && total / MHA_T < 0x7fffffffll, PDM_E_TOOLARGE, "mha_dropout_keep: %lld weights", total);
+    hipLaunchKernelGGL(mha_keep_kernel, dim3((unsigned)divup(total, MHA_T)), dim3(MHA_T), 0, as_stream(stream), nheads, P, N, total,
+                       mha_dropout_thresh(dropout_p), seed, step, keep);
+    return check_launch("mha_dropout_keep");
 }

@@ -15,6 +15,13 @@ __device__ __forceinline__ unsigned draw_key(unsigned seed, unsigned step, unsig
     return fmix32(fmix32(seed ^ step * 0x85EBCA6Bu) ^ b * 0x9E3779B1u ^ s * 0x7F4A7C15u);
 }
 
+// The attention dropout (attention.hip, attention_bwd.hip): weight (sample b, head h, query i, key j) is kept iff
+//   fmix32(draw_key(seed, step, b * H + h, i) ^ j * 0x9E3779B1) >= floor(p * 2^32),   0 <= p < 1
+// qkey = the query's draw_key, evaluated once per query; a kept weight is multiplied by 1.0f / (1.0f - p).
+__device__ __forceinline__ bool attn_keep(unsigned qkey, unsigned j, unsigned thresh) {
+    return fmix32(qkey ^ j * 0x9E3779B1u) >= thresh;
+}
+
 __device__ __forceinline__ unsigned feistel_perm(unsigned i, unsigned n, unsigned kp) {
     int w = 1;
     while ((1ull << (2 * w)) < (unsigned long long)n) ++w;

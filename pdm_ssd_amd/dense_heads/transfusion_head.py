@@ -20,6 +20,10 @@ nn.MultiheadAttention with its dropout; query_heatmap_score carries no gradient)
 transfusion_ops.loss for the whole batch with no host read (the reference walks the samples, calls scipy's
 linear_sum_assignment on the host and ends in four .item() calls), and sets batch_dict['loss'] and batch_dict['tb_dict']
 (detached device tensors).  On the CPU assign_torch and loss_torch run instead.
+
+A second key of this build, FUSED_ATTENTION_TRAIN (default False), sends the decoder's two attentions in training mode through
+attention_ops.mha_qkv / mha_kv and their HIP backward instead of nn.MultiheadAttention; the attention dropout then draws from
+ATTENTION_DROPOUT_SEED (default 0) and the decoder's device step counters (utils/transfusion_utils.py), not from torch's generator.
 """
 import copy
 
@@ -88,6 +92,10 @@ class TransFusionHead(nn.Module):
         heads['heatmap'] = dict(out_channels=self.num_classes, num_conv=_get(model_cfg, 'NUM_HM_CONV'))
         self.prediction_head = SeparateHead_Transfusion(hidden, 64, 1, heads, use_bias=bias)
         self.init_weights()
+        # opt-in keys of this build: training mode through attention_ops.mha_kv / mha_qkv and their HIP backward, the
+        # attention dropout drawn from ATTENTION_DROPOUT_SEED (data-parallel ranks: decoder.set_attention_seed(seed + rank))
+        self.decoder.fused_train = bool(_get(model_cfg, 'FUSED_ATTENTION_TRAIN', False))
+        self.decoder.set_attention_seed(int(_get(model_cfg, 'ATTENTION_DROPOUT_SEED', 0)))
 
         # the key positions of the cross-attention, already in (x, y) order: the reference's table runs over
         # (x_size, y_size) in `ij` order, entry n = (n // y_size + 0.5, n % y_size + 0.5), and is flipped before use

@@ -388,6 +388,11 @@ TRANSFUSION_LIDAR_CFG = {
 # with it the head builds its HungarianAssigner3D and reads LOSS_CONFIG, without it the head is the eval-only one above
 TRANSFUSION_LIDAR_TRAIN_CFG = copy.deepcopy(TRANSFUSION_LIDAR_CFG)
 TRANSFUSION_LIDAR_TRAIN_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['ASSIGN_ON_DEVICE'] = True
+# ... and with the decoder's two attentions trained through attention_ops.mha_qkv / mha_kv (the fused forward with dropout and
+# its HIP backward) instead of nn.MultiheadAttention: FUSED_ATTENTION_TRAIN is a key of this build too, opt-in; the attention
+# dropout then draws from the head's ATTENTION_DROPOUT_SEED (default 0) and a device step counter, not from torch's generator
+TRANSFUSION_LIDAR_FUSED_TRAIN_CFG = copy.deepcopy(TRANSFUSION_LIDAR_TRAIN_CFG)
+TRANSFUSION_LIDAR_FUSED_TRAIN_CFG['DENSE_HEAD']['FUSED_ATTENTION_TRAIN'] = True
 
 
 def synthetic_dataset(num_point_features=4):
@@ -543,8 +548,8 @@ def transfusion_dataset(num_point_features=5, point_cloud_range=None, voxel_size
 
 
 def build_transfusion_lidar(model_cfg=None, num_point_features=5, dataset=None):
-    """TransFusion from TRANSFUSION_LIDAR_CFG (eval mode only), TRANSFUSION_LIDAR_TRAIN_CFG (with the head's training half) or a
-    dict like them: DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone -> TransFusionHead, on
+    """TransFusion from TRANSFUSION_LIDAR_CFG (eval mode only), TRANSFUSION_LIDAR_TRAIN_CFG (with the head's training half),
+    TRANSFUSION_LIDAR_FUSED_TRAIN_CFG (training through the fused attention as well) or a dict like them: DynamicMeanVFE -> VoxelResBackBone8x -> HeightCompression -> BaseBEVBackbone -> TransFusionHead, on
     transfusion_dataset() unless another dataset namespace is given."""
     from .detectors import build_network
     cfg = cfg_from_dict(copy.deepcopy(TRANSFUSION_LIDAR_CFG if model_cfg is None else model_cfg))

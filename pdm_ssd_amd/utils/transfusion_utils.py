@@ -6,6 +6,11 @@ training mode and use_fused = False run through them.  On the GPU in eval mode t
 in_proj_weight / in_proj_bias itself (one GEMM gives [Q; K; V] of the self-attention and [K; V] of the cross-attention,
 whose key and value are both key + key_pos_embed), calls attention_ops.mha_forward on the projected rows and then the
 out-projection.  LayerNorm, the feed-forward block and the residuals stay torch.
+
+fused_train = True (TransFusionHead's FUSED_ATTENTION_TRAIN) gives training mode the same structure under autograd:
+attention_ops.mha_qkv / mha_kv on the packed projections, with the modules' attention dropout drawn from the layer's own
+counter-based draws (set_attention_seed; one device step counter per attention, two non-persistent buffers, so the state
+dict is unchanged and the counters are NOT checkpointed: a resumed run draws from step 0 unless the caller restores them).
 """
 import torch
 from torch import nn
@@ -54,6 +59,18 @@ class TransformerDecoderLayer(nn.Module):
         self.fused_self = True           # which of the two attentions the fused path hands to mha_forward
         self.fused_cross = True
         self.keys_per_chunk = 0          # 0: the library's default
+        self.fused_train = False         # True: training mode runs the fused attention under autograd
+        self.attention_seed = 0
+        self.register_buffer('attn_step_self', torch.zeros(1, dtype=torch.int32), persistent=False)
+        self.register_buffer('attn_step_cross', torch.zeros(1, dtype=torch.int32), persistent=False)
+
+    def set_attention_seed(self, seed):
+        """the seed of the fused training path's attention dropout; data-parallel ranks must pass different seeds"""
+        self.attention_seed = int(seed)
+
+    def reset_attention_steps(self, value=0):
+        self.attn_step_self.fill_(int(value))
+        self.attn_step_cross.fill_(int(value))
 
     @staticmethod
     def with_pos_embed(tensor, pos_embed):
@@ -61,12 +78,14 @@ class TransformerDecoderLayer(nn.Module):
 
     def _fusable(self, query):
         d = query.shape[1] // self.nhead
-        return (self.use_fused and not self.training and query.is_cuda and query.dtype == torch.float32 and d in (16, 32)
+        return (self.use_fused and (not self.training or self.fused_train) and query.is_cuda and query.dtype == torch.float32 and d in (16, 32)
                 and query.shape[1] <= 256 and (self.fused_self or self.fused_cross))
 
     def forward(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
         """query (B, C, P), key (B, C, N), query_pos (B, P, 2), key_pos (B | 1, N, 2) -> (B, C, P)"""
         if key_padding_mask is None and attn_mask is None and self._fusable(query):
+            if self.training:
+                return self._forward_fused_train(query, key, query_pos, key_pos)
             return self._forward_fused(query, key, query_pos, key_pos)
         # sequence first, as nn.MultiheadAttention takes it: (P, B, C), (N, B, C)
         query_pos_embed = self.self_posembed(query_pos).permute(2, 0, 1) if self.self_posembed is not None else None
@@ -115,4 +134,53 @@ class TransformerDecoderLayer(nn.Module):
             kv_in = kv_in.expand(B, -1, -1)
         x = self.norm2(x + self._attend(self.multihead_attn, self.fused_cross, self.with_pos_embed(x, qpe), kv_in, False))
         x = self.norm3(x + self.linear2(self.activation(self.linear1(x))))
+        return x.transpose(1, 2)
+
+    def _attend_train(self, attn, fused, q_in, kv_in, same, draws):
+        """_attend under autograd with the module's attention dropout: the packed projections go to mha_qkv / mha_kv"""
+        from .. import attention_ops
+        C = q_in.shape[-1]
+        W, b = attn.in_proj_weight, attn.in_proj_bias
+        p = float(attn.dropout)
+        if same:
+            qkv = F.linear(q_in, W, b)                                # (B, P, 3C)
+            if fused:
+                out = attention_ops.mha_qkv(qkv, self.nhead, p, draws, self.keys_per_chunk)
+            else:
+                out = self._attend_torch(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], p)
+        else:
+            q = F.linear(q_in, W[:C], None if b is None else b[:C])
+            kv = F.linear(kv_in, W[C:], None if b is None else b[C:])    # (B, N, 2C)
+            if fused:
+                out = attention_ops.mha_kv(q, kv, self.nhead, p, draws, self.keys_per_chunk)
+            else:
+                out = self._attend_torch(q, kv[..., :C], kv[..., C:], p)
+        return F.linear(out, attn.out_proj.weight, attn.out_proj.bias)
+
+    def _attend_torch(self, q, k, v, p):
+        """an attention fused_self / fused_cross leaves to torch: the weights materialised, torch's own dropout on them"""
+        B, P, C = q.shape
+        d = C // self.nhead
+        qh, kh, vh = (t.reshape(B, t.shape[1], self.nhead, d).transpose(1, 2) for t in (q, k, v))
+        w = F.dropout(torch.softmax(qh @ kh.transpose(-1, -2) / d ** 0.5, dim=-1), p, True)
+        return (w @ vh).transpose(1, 2).reshape(B, P, C)
+
+    def _forward_fused_train(self, query, key, query_pos, key_pos):
+        from .. import attention_ops
+        B = query.shape[0]
+        seed = (2 * self.attention_seed) & 0xFFFFFFFF                 # two streams of the seed: even self, odd cross
+        x = query.transpose(1, 2)                                     # (B, P, C)
+        qpe = self.self_posembed(query_pos).transpose(1, 2) if self.self_posembed is not None else None
+        kpe = self.cross_posembed(key_pos).transpose(1, 2) if self.cross_posembed is not None else None    # (B | 1, N, C)
+        if not self.cross_only:
+            t = self.with_pos_embed(x, qpe)
+            draws = attention_ops.AttentionDraws(seed, x.device, self.attn_step_self)
+            x = self.norm1(x + self.dropout1(self._attend_train(self.self_attn, self.fused_self, t, t, True, draws)))
+        kv_in = self.with_pos_embed(key.transpose(1, 2), kpe)
+        if kv_in.shape[0] != B:
+            kv_in = kv_in.expand(B, -1, -1)
+        draws = attention_ops.AttentionDraws(seed | 1, x.device, self.attn_step_cross)
+        x = self.norm2(x + self.dropout2(self._attend_train(self.multihead_attn, self.fused_cross, self.with_pos_embed(x, qpe), kv_in,
+                                                            False, draws)))
+        x = self.norm3(x + self.dropout3(self.linear2(self.dropout(self.activation(self.linear1(x))))))
         return x.transpose(1, 2)

@@ -43,6 +43,14 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask, int lane) {
     return __popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// the sum of one value per lane over the wave, to every lane (all 64 lanes call it)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // inclusive scan of one int per lane over the wave (all 64 lanes call it)
 __device__ __forceinline__ int wave_scan_incl(int v) {
     const int lane = threadIdx.x & 63;
@@ -74,7 +82,7 @@ __device__ __forceinline__ int block_scan(int v, int *s_wave, int *total) {
 }
 
 // Exclusive scan of n totals in global memory in place by ONE workgroup of NT threads (the middle launch of a multi-launch
-// scan: pillar.hip, sparse_conv.hip); returns the grand total to every thread.  s_wave: NT / 64 ints of LDS.
+// scan, between tile_reduce and tile_scan below); returns the grand total to every thread.  s_wave: NT / 64 ints of LDS.
 template <int NT>
 __device__ __forceinline__ int scan_totals(int n, int *__restrict__ v, int *s_wave) {
     int carry = 0;
@@ -87,6 +95,56 @@ __device__ __forceinline__ int scan_totals(int n, int *__restrict__ v, int *s_wa
         carry += total;
     }
     return carry;
+}
+
+// ---- the outer launches of a multi-launch scan: scan_totals is the middle one -----------------------------------------
+// A workgroup of NT threads owns a tile of NT * ITEMS items; item j of thread t is blockIdx.x * NT * ITEMS + j * NT + t.
+// Both passes carry K values an item (K = 1 or 2, deduced from the braced list of tiles / bases).
+constexpr int SCAN_T = 256;                        // the voxelizers' tiles (pillar.hip, sc_index.h, hard_voxel.hip)
+constexpr int SCAN_ITEMS = 8;
+constexpr int SCAN_TILE = SCAN_T * SCAN_ITEMS;
+
+// Pass one: tiles[k][blockIdx.x] = the tile's sum of value k.  value(i, sum) adds item i < n to sum[0 .. K); it is not called
+// past n and may have side effects of its own (the first read of a row is where its key and its atomics belong).
+template <int NT, int ITEMS, int K, class F>
+__device__ __forceinline__ void tile_reduce(long long n, int *const (&tiles)[K], F value) {
+    __shared__ int s_total[K];
+    if (threadIdx.x == 0)
+        for (int k = 0; k < K; ++k) s_total[k] = 0;
+    __syncthreads();
+    int sum[K] = {};
+    for (int j = 0; j < ITEMS; ++j) {
+        const long long i = (long long)blockIdx.x * (NT * ITEMS) + j * NT + threadIdx.x;
+        if (i >= n) break;
+        value(i, sum);
+    }
+    for (int k = 0; k < K; ++k)
+        if (sum[k]) atomicAdd(&s_total[k], sum[k]);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 0; k < K; ++k) tiles[k][blockIdx.x] = s_total[k];
+}
+
+// Pass three: base[k] is the tile's entry of the scanned totals.  value(i, v) sets v[0 .. K) of item i < n (an item past n
+// counts as zeros), then body(i, at) runs for the same item with at[k] = base[k] + the exclusive prefix of value k inside
+// the tile: the two may share a captured local.  The block_scans hold barriers, so every thread reaches every one of them:
+// the loop has no break, and a body that has nothing to do returns.
+template <int NT, int ITEMS, int K, class V, class F>
+__device__ __forceinline__ void tile_scan(long long n, const int (&base)[K], V value, F body) {
+    __shared__ int s_wave[NT / 64];
+    int run[K];
+    for (int k = 0; k < K; ++k) run[k] = base[k];
+    for (int j = 0; j < ITEMS; ++j) {
+        const long long i = (long long)blockIdx.x * (NT * ITEMS) + j * NT + threadIdx.x;
+        int v[K] = {}, at[K];
+        if (i < n) value(i, v);
+        for (int k = 0; k < K; ++k) {
+            int total;
+            at[k] = run[k] + block_scan<NT>(v[k], s_wave, &total);
+            run[k] += total;
+        }
+        if (i < n) body(i, at);
+    }
 }
 
 // scan_totals as a launch of its own, ONE workgroup of NT threads: v[0 .. n) -> its exclusive prefix in place, v[n] = the total
@@ -134,7 +192,7 @@ __device__ __forceinline__ void hist_to_cursors(int *hist, int ncells, int *s_wa
     __syncthreads();
 }
 
-// Cell of one coordinate as the reference's dynamic voxel encoders compute it (pillar.hip, sparse_conv.hip):
+// Cell of one coordinate as the reference's dynamic voxel encoders compute it (voxel_grid.h's voxel_key):
 // floor((x - x0) / v) in fp32 with an IEEE division (not a reciprocal multiply: 0.16 is no power of two).  Returns -1
 // outside [0, n) and for NaN.
 __device__ __forceinline__ int cell_1d(float x, float x0, float v, int n) {

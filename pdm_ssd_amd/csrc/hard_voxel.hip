@@ -13,41 +13,26 @@
 // mode in one launch (pillar_feat.h), neither through the padded (M, T, C) tensor.
 #include "pillar_feat.h"
 #include "sc_index.h"
+#include "voxel_grid.h"
 
 namespace pdm {
 
-constexpr int HV_T = 256;                  // threads per workgroup of every kernel here
-constexpr int HV_ITEMS = 8;                // scan items per thread
-constexpr int HV_TILE = HV_T * HV_ITEMS;   // scan items per workgroup
+constexpr int HV_T = SCAN_T;               // threads per workgroup of every kernel here; a scan tile is SCAN_TILE items
 constexpr int HV_MAX_T = 128;              // points per voxel (pdm_hard_voxel_max_points)
 constexpr int HV_SHORT = 32;               // the selection pass: a lane per list up to here, a wave per longer list
 constexpr int HV_NONE = 0x7fffffff;
 enum { HV_UNSORTED = 0, HV_CELLS = 1 };    // words of the workspace's `misc`
 
-struct HvGrid {
-    int B, nx, ny, nz;
-    float x0, y0, z0, vx, vy, vz;
-};
-
-// key of the row's cell, or -1 when the row is dropped (outside on any axis, z included; a sample index outside [0, B); NaN)
-__device__ __forceinline__ long long hv_key(const float *__restrict__ row, const HvGrid &g) {
-    const float bf = row[0];
-    if (!(bf >= 0.0f && bf < (float)g.B)) return -1;
-    const int cx = cell_1d(row[1], g.x0, g.vx, g.nx), cy = cell_1d(row[2], g.y0, g.vy, g.ny), cz = cell_1d(row[3], g.z0, g.vz, g.nz);
-    if (cx < 0 || cy < 0 || cz < 0) return -1;
-    return (((long long)(int)bf * g.nx + cx) * g.ny + cy) * g.nz + cz;
-}
-
-// rows -> keys and occupancy bits; batch_idx[i] <= batch_idx[i + 1] or the input counts as unsorted (a NaN does); the
-// first-row table starts at "none"
-__global__ __launch_bounds__(HV_T) void hv_key_kernel(int N, int C1, const float *__restrict__ points, HvGrid g, int capc,
+// rows -> keys (voxel_grid.h, z tested) and occupancy bits; batch_idx[i] <= batch_idx[i + 1] or the input counts as unsorted
+// (a NaN does); the first-row table starts at "none"
+__global__ __launch_bounds__(HV_T) void hv_key_kernel(int N, int C1, const float *__restrict__ points, VoxelGrid g, int capc,
                                                       long long *__restrict__ point_key, unsigned *__restrict__ bits,
                                                       int *__restrict__ first_row, int *__restrict__ misc) {
     const long long i = (long long)blockIdx.x * HV_T + threadIdx.x;
     if (i < capc) first_row[i] = HV_NONE;
     if (i >= N) return;
     const float *row = points + (size_t)i * C1;
-    const long long key = hv_key(row, g);
+    const long long key = voxel_key<true>(row, g);
     point_key[i] = key;
     if (key >= 0) sc_set(bits, key);
     if (i + 1 < N && !(row[0] <= row[C1])) atomicOr(&misc[HV_UNSORTED], 1);
@@ -73,18 +58,13 @@ __global__ __launch_bounds__(HV_T) void hv_first_kernel(int N, const long long *
 __global__ __launch_bounds__(HV_T) void hv_flag_total_kernel(int N, int C1, const float *__restrict__ points, const int *__restrict__ point_rank,
                                                              const int *__restrict__ first_row, int *__restrict__ ptile,
                                                              int *__restrict__ sample_cnt) {
-    __shared__ int s_total;
-    if (threadIdx.x == 0) s_total = 0;
-    __syncthreads();
     const int lane = threadIdx.x & 63;
-    int mine = 0;
-    for (int j = 0; j < HV_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * HV_TILE + j * HV_T + threadIdx.x;
-        const int r = i < N ? point_rank[i] : -1;
+    tile_reduce<HV_T, SCAN_ITEMS>(N, {ptile}, [&](long long i, int *flags) {
+        const int r = point_rank[i];
         const bool f = r >= 0 && first_row[r] == (int)i;
         const int b = f ? (int)points[(size_t)i * C1] : -1;
-        mine += f;
-        unsigned long long left = __ballot(f);
+        flags[0] += f;
+        unsigned long long left = __ballot(f);          // of the wave's lanes that have a row
         while (left) {                                  // wave-uniform: the flagged lanes of one sample at a time
             const int leader = __ffsll((long long)left) - 1;
             const int lb = __shfl(b, leader, 64);
@@ -92,26 +72,12 @@ __global__ __launch_bounds__(HV_T) void hv_flag_total_kernel(int N, int C1, cons
             if (lane == leader) atomicAdd(&sample_cnt[lb], __popcll(same));
             left &= ~same;
         }
-    }
-    if (mine) atomicAdd(&s_total, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) ptile[blockIdx.x] = s_total;
+    });
 }
 
 // rows of every tile of cells (cells in key order; entries past the occupied cells are zero)
 __global__ __launch_bounds__(HV_T) void hv_cell_total_kernel(int capc, const int *__restrict__ cell_count, int *__restrict__ ctile) {
-    __shared__ int s_total;
-    if (threadIdx.x == 0) s_total = 0;
-    __syncthreads();
-    int n = 0;
-    for (int j = 0; j < HV_ITEMS; ++j) {
-        const long long c = (long long)blockIdx.x * HV_TILE + j * HV_T + threadIdx.x;
-        if (c >= capc) break;
-        n += cell_count[c];
-    }
-    if (n) atomicAdd(&s_total, n);
-    __syncthreads();
-    if (threadIdx.x == 0) ctile[blockIdx.x] = s_total;
+    tile_reduce<HV_T, SCAN_ITEMS>(capc, {ctile}, [&](long long c, int *rows) { rows[0] += cell_count[c]; });
 }
 
 // workgroup 0: the row tiles; 1: the cell tiles; 2: the samples -> sample_cnt becomes the cells in front of every sample,
@@ -138,52 +104,38 @@ __global__ __launch_bounds__(HV_T) void hv_scan_kernel(int ntp, int *__restrict_
 }
 
 // every first row: its cell's appearance rank in the sample -> the voxel (or none), its coordinates and its point count
-__global__ __launch_bounds__(HV_T) void hv_voxel_kernel(int N, HvGrid g, int T, int max_voxels, int cap, const long long *__restrict__ point_key,
+__global__ __launch_bounds__(HV_T) void hv_voxel_kernel(int N, VoxelGrid g, int T, int max_voxels, int cap, const long long *__restrict__ point_key,
                                                         const int *__restrict__ point_rank, const int *__restrict__ first_row,
                                                         const int *__restrict__ cell_count, const int *__restrict__ ptile,
                                                         const int *__restrict__ sample_cnt, const int *__restrict__ sample_vox,
                                                         const int *__restrict__ misc, int *__restrict__ cell_vid, int *__restrict__ voxel_rank,
                                                         int *__restrict__ voxel_coords, int *__restrict__ voxel_num_points) {
-    __shared__ int s_wave[HV_T / 64];
     if (misc[HV_UNSORTED]) return;
-    int base = ptile[blockIdx.x];
-    const long long per_sample = (long long)g.nx * g.ny * g.nz;
-    for (int j = 0; j < HV_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * HV_TILE + j * HV_T + threadIdx.x;
-        const int r = i < N ? point_rank[i] : -1;
-        const bool f = r >= 0 && first_row[r] == (int)i;
-        int total;
-        const int seen = base + block_scan<HV_T>(f, s_wave, &total);      // first rows in front of this one, all samples
-        base += total;
-        if (!f) continue;
-        long long t = point_key[i];
-        const int b = (int)(t / per_sample);
-        const int rank = seen - sample_cnt[b];
+    int r;
+    bool f;
+    tile_scan<HV_T, SCAN_ITEMS>(N, {ptile[blockIdx.x]}, [&](long long i, int *v) {
+        r = point_rank[i];
+        v[0] = f = r >= 0 && first_row[r] == (int)i;
+    }, [&](long long i, const int *seen) {              // seen: first rows in front of this one, all samples
+        if (!f) return;
+        int c[4];
+        voxel_key_coords(point_key[i], g.nx, g.ny, g.nz, c);
+        const int b = c[0], rank = seen[0] - sample_cnt[b];
         const int vid = (rank >= 0 && rank < max_voxels) ? sample_vox[b] + rank : -1;
-        if (vid < 0 || vid >= cap) { cell_vid[r] = -1; continue; }
+        if (vid < 0 || vid >= cap) { cell_vid[r] = -1; return; }
         cell_vid[r] = vid;
         voxel_rank[vid] = r;
-        const int z = (int)(t % g.nz); t /= g.nz;
-        const int y = (int)(t % g.ny); t /= g.ny;
         int *vc = voxel_coords + (size_t)vid * 4;
-        vc[0] = b; vc[1] = z; vc[2] = y; vc[3] = (int)(t % g.nx);
+        vc[0] = b; vc[1] = c[1]; vc[2] = c[2]; vc[3] = c[3];
         voxel_num_points[vid] = min(cell_count[r], T);
-    }
+    });
 }
 
 // the first CSR slot of every cell
 __global__ __launch_bounds__(HV_T) void hv_cell_start_kernel(int capc, const int *__restrict__ cell_count, const int *__restrict__ ctile,
                                                              int *__restrict__ seg_start) {
-    __shared__ int s_wave[HV_T / 64];
-    int base = ctile[blockIdx.x];
-    for (int j = 0; j < HV_ITEMS; ++j) {
-        const long long c = (long long)blockIdx.x * HV_TILE + j * HV_T + threadIdx.x;
-        const int n = c < capc ? cell_count[c] : 0;
-        int total;
-        const int first = base + block_scan<HV_T>(n, s_wave, &total);
-        base += total;
-        if (c < capc) seg_start[c] = first;
-    }
+    tile_scan<HV_T, SCAN_ITEMS>(capc, {ctile[blockIdx.x]}, [&](long long c, int *v) { v[0] = cell_count[c]; },
+                                [&](long long c, const int *at) { seg_start[c] = at[0]; });
 }
 
 // every row of an accepted cell takes a CSR slot of the cell (slot order arbitrary)
@@ -324,7 +276,7 @@ static long long hv_capacity(long long N, int B, int max_voxels, long long ncell
     return a < b ? a : b;
 }
 static HvWorkspace hv_workspace(long long N, int B, long long ncell) {
-    const size_t capc = (size_t)(N < ncell ? N : ncell), ntp = (size_t)divup(N, HV_TILE), ntc = (size_t)divup((long long)capc, HV_TILE);
+    const size_t capc = (size_t)(N < ncell ? N : ncell), ntp = (size_t)divup(N, SCAN_TILE), ntc = (size_t)divup((long long)capc, SCAN_TILE);
     HvWorkspace w{};
     w.isz = sc_index_size(ncell);
     size_t at = 0;
@@ -349,13 +301,6 @@ static HvWorkspace hv_workspace(long long N, int B, long long ncell) {
     return w;
 }
 
-static int hv_check_grid(const char *who, long long N, int C1, int B, int nx, int ny, int nz) {
-    PDM_REQUIRE(N >= 0 && B >= 0 && nx >= 1 && ny >= 1 && nz >= 1 && C1 >= 4, PDM_E_BADARG, "%s: bad size", who);
-    PDM_REQUIRE((long long)nx * ny <= 0x7fffffffll && (long long)nx * ny * nz <= SC_MAXCELL && hv_cells(B, nx, ny, nz) <= SC_MAXCELL, PDM_E_TOOLARGE,
-                "%s: the grid exceeds 2^35 cells", who);
-    PDM_REQUIRE(N * C1 <= 0x7fffffffll, PDM_E_TOOLARGE, "%s: %lld point elements exceed int32", who, N * C1);
-    return 0;
-}
 static int hv_check_slots(const char *who, long long M, int T, int C1) {
     PDM_REQUIRE(M >= 0 && C1 >= 4, PDM_E_BADARG, "%s: bad size", who);
     PDM_REQUIRE(T >= 1 && T <= HV_MAX_T, PDM_E_BADARG, "%s: %d points per voxel, between 1 and %d", who, T, HV_MAX_T);
@@ -370,9 +315,7 @@ using namespace pdm;
 extern "C" int pdm_hard_voxel_max_points(void) { return HV_MAX_T; }
 
 extern "C" size_t pdm_hard_voxelize_workspace_bytes(int N, int B, int nx, int ny, int nz) {
-    if (N < 0 || B < 0 || nx < 1 || ny < 1 || nz < 1 || (long long)nx * ny > 0x7fffffffll || (long long)nx * ny * nz > SC_MAXCELL ||
-        hv_cells(B, nx, ny, nz) > SC_MAXCELL)
-        return 0;
+    if (N < 0 || !voxel_grid_cells_ok(B, nx, ny, nz, SC_MAXCELL)) return 0;
     return hv_workspace(N, B, hv_cells(B, nx, ny, nz)).total;
 }
 
@@ -382,7 +325,7 @@ extern "C" size_t pdm_hard_voxelize_workspace_bytes(int N, int B, int nx, int ny
 extern "C" int pdm_hard_voxelize(void *stream, int N, int C1, const float *points, int B, int nx, int ny, int nz, float x0, float y0, float z0,
                                  float vx, float vy, float vz, int T, int max_voxels, int *slot_rows, int *voxel_coords,
                                  int *voxel_num_points, float *voxels, int *record, void *workspace, size_t workspace_bytes) {
-    if (int rc = hv_check_grid("hard_voxelize", N, C1, B, nx, ny, nz)) return rc;
+    if (int rc = voxel_grid_check("hard_voxelize", N, C1, B, nx, ny, nz, SC_MAXCELL, "the grid exceeds 2^35 cells")) return rc;
     PDM_REQUIRE(vx > 0.0f && vy > 0.0f && vz > 0.0f, PDM_E_BADARG, "hard_voxelize: voxel size must be positive");
     PDM_REQUIRE(max_voxels >= 1, PDM_E_BADARG, "hard_voxelize: max_voxels must be at least 1 (got %d)", max_voxels);
     const long long ncell = hv_cells(B, nx, ny, nz), cap = hv_capacity(N, B, max_voxels, ncell);
@@ -402,8 +345,8 @@ extern "C" int pdm_hard_voxelize(void *stream, int N, int C1, const float *point
     int *seg_rows = ints(w.seg_rows), *voxel_rank = ints(w.voxel_rank), *ptile = ints(w.ptile), *ctile = ints(w.ctile);
     int *sample_vox = ints(w.sample_vox), *cell_count = ints(w.cell_count), *cursor = ints(w.cursor), *sample_cnt = ints(w.sample_cnt);
     int *misc = ints(w.misc);
-    const HvGrid g{B, nx, ny, nz, x0, y0, z0, vx, vy, vz};
-    const int capc = (int)(N < ncell ? N : ncell), ntp = divup(N, HV_TILE), ntc = divup(capc, HV_TILE), nbp = divup(N, HV_T);
+    const VoxelGrid g{B, nx, ny, nz, x0, y0, z0, vx, vy, vz};
+    const int capc = (int)(N < ncell ? N : ncell), ntp = divup(N, SCAN_TILE), ntc = divup(capc, SCAN_TILE), nbp = divup(N, HV_T);
     hipStream_t s = as_stream(stream);
     if (int rc = zero_fill(stream, "hard_voxelize(zero)", ix.bits, w.isz.bits)) return rc;
     if (int rc = zero_fill(stream, "hard_voxelize(zero)", ws + w.zeroed, w.zeroed_end - w.zeroed)) return rc;

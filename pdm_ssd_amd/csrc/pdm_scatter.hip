@@ -202,12 +202,6 @@ __global__ __launch_bounds__(256) void pdm_normalize_cl4_kernel(long long nvec, 
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Backward (gather): dfeat (B,P,C), dsh (B,P,nsh), dinv2s2 (B,P) fully written.
 // (five waves per SIMD: 96 VGPRs, one spill — the kernel is a latency chain, 442 -> 419 us for the neck's backward; six spill 16)
 __global__ __launch_bounds__(PDM_WAVES * 64, 5) void pdm_scatter_grad_kernel(

@@ -5,72 +5,39 @@
 //   * a cell's key is b * nx * ny + cx * ny + cy (x-major: torch.unique's order of the reference's merge_coords), and the
 //     pillar ids are the exclusive scan of the cells' occupancy in key order;
 //   * the scans are multi-launch (tile totals, one workgroup over the totals, tiles again): no workgroup waits for another;
-//   * xyz sums are 64-bit fixed point (llrint(x * 2^20)), added with integer atomics, which commute;
+//   * xyz sums are 64-bit fixed point (voxel_grid.h), added with integer atomics, which commute;
 //   * the rows of a pillar are listed in a CSR whose slot order is arbitrary (an integer atomic cursor): the only readers
 //     take a max with ties to the lower row, or an integer sum, neither of which depends on the order.
 #include "pillar_feat.h"
+#include "voxel_grid.h"
 
 namespace pdm {
 
-constexpr int PL_T = 256;                  // threads per workgroup of every kernel here
-constexpr int PL_ITEMS = 8;                // scan items per thread
-constexpr int PL_TILE = PL_T * PL_ITEMS;   // scan items per workgroup
-constexpr double PL_FIX = 1048576.0;       // 2^20: one step of the fixed-point sums is about a micrometre
-
-struct PlGrid {
-    int B, nx, ny;
-    float x0, y0, vx, vy;
-};
-
-// key of the row's cell, or -1 when the row is dropped (outside in x or y, a sample index outside [0, B), NaN); z is not tested
-__device__ __forceinline__ int pl_key(const float *__restrict__ row, const PlGrid &g) {
-    const float bf = row[0];
-    if (!(bf >= 0.0f && bf < (float)g.B)) return -1;
-    const int cx = cell_1d(row[1], g.x0, g.vx, g.nx), cy = cell_1d(row[2], g.y0, g.vy, g.ny);
-    if (cx < 0 || cy < 0) return -1;
-    return ((int)bf * g.nx + cx) * g.ny + cy;
-}
+constexpr int PL_T = SCAN_T;               // threads per workgroup of every kernel here; a scan tile is SCAN_TILE items
 
 // ---- a. assign ----------------------------------------------------------------------------------------------------
-// rows -> cell keys, per-cell counts (integer atomics) and the kept rows of every tile
-__global__ __launch_bounds__(PL_T) void pl_key_kernel(int N, int C1, const float *__restrict__ points, PlGrid g, int *__restrict__ point_key,
+// rows -> cell keys (voxel_grid.h on the nz = 1 grid, z not tested; the host bounds the cells, and so the keys, by int32),
+// per-cell counts (integer atomics) and the kept rows of every tile
+__global__ __launch_bounds__(PL_T) void pl_key_kernel(int N, int C1, const float *__restrict__ points, VoxelGrid g, int *__restrict__ point_key,
                                                       int *__restrict__ cell_count, int *__restrict__ ptile) {
-    __shared__ int s_total;
-    if (threadIdx.x == 0) s_total = 0;
-    __syncthreads();
-    int kept = 0;
-    for (int j = 0; j < PL_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * PL_TILE + j * PL_T + threadIdx.x;
-        if (i >= N) break;
-        const int key = pl_key(points + (size_t)i * C1, g);
+    tile_reduce<PL_T, SCAN_ITEMS>(N, {ptile}, [&](long long i, int *kept) {
+        const int key = (int)voxel_key<false>(points + (size_t)i * C1, g);
         point_key[i] = key;
         if (key >= 0) {
             atomicAdd(&cell_count[key], 1);
-            ++kept;
+            ++kept[0];
         }
-    }
-    if (kept) atomicAdd(&s_total, kept);
-    __syncthreads();
-    if (threadIdx.x == 0) ptile[blockIdx.x] = s_total;
+    });
 }
 
 // per tile of cells: how many are occupied and how many rows they hold
 __global__ __launch_bounds__(PL_T) void pl_cell_total_kernel(int ncell, const int *__restrict__ cell_count, int *__restrict__ ctile_occ,
                                                              int *__restrict__ ctile_cnt) {
-    __shared__ int s_occ, s_cnt;
-    if (threadIdx.x == 0) { s_occ = 0; s_cnt = 0; }
-    __syncthreads();
-    int occ = 0, cnt = 0;
-    for (int j = 0; j < PL_ITEMS; ++j) {
-        const long long c = (long long)blockIdx.x * PL_TILE + j * PL_T + threadIdx.x;
-        if (c >= ncell) break;
+    tile_reduce<PL_T, SCAN_ITEMS>(ncell, {ctile_occ, ctile_cnt}, [&](long long c, int *sum) {
         const int n = cell_count[c];
-        occ += n > 0;
-        cnt += n;
-    }
-    if (cnt) { atomicAdd(&s_occ, occ); atomicAdd(&s_cnt, cnt); }
-    __syncthreads();
-    if (threadIdx.x == 0) { ctile_occ[blockIdx.x] = s_occ; ctile_cnt[blockIdx.x] = s_cnt; }
+        sum[0] += n > 0;
+        sum[1] += n;
+    });
 }
 
 // workgroup 0: the point tiles -> record[0] = N'; workgroup 1: the cell tiles -> record[1] = P, seg_start[P] = N'
@@ -88,33 +55,26 @@ __global__ __launch_bounds__(PL_T) void pl_scan_totals_kernel(int ntp, int *__re
 }
 
 // every cell: its pillar id (or -1), and per pillar its coordinates, count, first CSR slot, a cleared cursor and cleared sums
-__global__ __launch_bounds__(PL_T) void pl_cell_fill_kernel(int ncell, PlGrid g, const int *__restrict__ cell_count, const int *__restrict__ ctile_occ,
+__global__ __launch_bounds__(PL_T) void pl_cell_fill_kernel(int ncell, VoxelGrid g, const int *__restrict__ cell_count, const int *__restrict__ ctile_occ,
                                                             const int *__restrict__ ctile_cnt, int *__restrict__ cell_table,
                                                             int *__restrict__ voxel_coords, int *__restrict__ pillar_count, int *__restrict__ seg_start,
                                                             int *__restrict__ cursor, long long *__restrict__ sums) {
-    __shared__ int s_wave[PL_T / 64];
-    int base_occ = ctile_occ[blockIdx.x], base_cnt = ctile_cnt[blockIdx.x];
-    const int plane = g.nx * g.ny;
-    for (int j = 0; j < PL_ITEMS; ++j) {
-        const long long c = (long long)blockIdx.x * PL_TILE + j * PL_T + threadIdx.x;
-        const int n = c < ncell ? cell_count[c] : 0;
-        int tot_occ, tot_cnt;
-        const int pid = base_occ + block_scan<PL_T>(n > 0, s_wave, &tot_occ);
-        const int first = base_cnt + block_scan<PL_T>(n, s_wave, &tot_cnt);
-        base_occ += tot_occ;
-        base_cnt += tot_cnt;
-        if (c >= ncell) continue;
+    int n;
+    tile_scan<PL_T, SCAN_ITEMS>(ncell, {ctile_occ[blockIdx.x], ctile_cnt[blockIdx.x]}, [&](long long c, int *v) {
+        n = cell_count[c];
+        v[0] = n > 0;
+        v[1] = n;
+    }, [&](long long c, const int *at) {
+        const int pid = at[0];
         cell_table[c] = n > 0 ? pid : -1;
         if (n > 0) {
-            const int b = (int)(c / plane), r = (int)(c % plane);
-            int *vc = voxel_coords + (size_t)pid * 4;
-            vc[0] = b; vc[1] = 0; vc[2] = r % g.ny; vc[3] = r / g.ny;
+            voxel_key_coords((int)c, g.nx, g.ny, 1, voxel_coords + (size_t)pid * 4);
             pillar_count[pid] = n;
-            seg_start[pid] = first;
+            seg_start[pid] = at[1];
             cursor[pid] = 0;
             sums[(size_t)pid * 3] = 0; sums[(size_t)pid * 3 + 1] = 0; sums[(size_t)pid * 3 + 2] = 0;
         }
-    }
+    });
 }
 
 // every kept row: its place in input order, its pillar, a CSR slot, and its xyz added to the pillar's fixed-point sums
@@ -123,31 +83,17 @@ __global__ __launch_bounds__(PL_T) void pl_point_fill_kernel(int N, int C1, cons
                                                              const int *__restrict__ seg_start, int *__restrict__ cursor,
                                                              unsigned long long *__restrict__ sums, int *__restrict__ kept_idx,
                                                              int *__restrict__ unq_inv, int *__restrict__ seg_rows) {
-    __shared__ int s_wave[PL_T / 64];
-    int base = ptile[blockIdx.x];
-    for (int j = 0; j < PL_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * PL_TILE + j * PL_T + threadIdx.x;
-        const int key = i < N ? point_key[i] : -1;
-        int total;
-        const int row = base + block_scan<PL_T>(key >= 0, s_wave, &total);
-        base += total;
-        if (key < 0) continue;
-        const int pid = cell_table[key];
+    int key;
+    tile_scan<PL_T, SCAN_ITEMS>(N, {ptile[blockIdx.x]}, [&](long long i, int *v) { key = point_key[i]; v[0] = key >= 0; },
+                                [&](long long i, const int *at) {
+        if (key < 0) return;
+        const int row = at[0], pid = cell_table[key];
         kept_idx[row] = (int)i;
         unq_inv[row] = pid;
         seg_rows[seg_start[pid] + atomicAdd(&cursor[pid], 1)] = row;
         const float *p = points + (size_t)i * C1;
-        for (int d = 0; d < 3; ++d)     // two's complement: the unsigned add is the signed one
-            atomicAdd(&sums[(size_t)pid * 3 + d], (unsigned long long)llrint((double)p[1 + d] * PL_FIX));
-    }
-}
-
-// mean = float(double(sum) * 2^-20 / count); launched at capacity, the pillar count is read on the device
-__global__ __launch_bounds__(PL_T) void pl_mean_kernel(const int *__restrict__ record, const long long *__restrict__ sums,
-                                                       const int *__restrict__ pillar_count, float *__restrict__ pillar_mean) {
-    const long long t = (long long)blockIdx.x * PL_T + threadIdx.x;
-    if (t >= (long long)record[1] * 3) return;
-    pillar_mean[t] = (float)((double)sums[t] * (1.0 / PL_FIX) / (double)pillar_count[t / 3]);
+        for (int d = 0; d < 3; ++d) fixed20_add(&sums[(size_t)pid * 3 + d], p[1 + d]);
+    });
 }
 
 // ---- b. features ----------------------------------------------------------------------------------------------------
@@ -285,7 +231,7 @@ struct PlWorkspace {
 };
 static long long pl_capacity(long long N, long long ncell) { return N < ncell ? N : ncell; }
 static PlWorkspace pl_workspace(long long N, long long ncell) {
-    const size_t ntp = (size_t)divup(N, PL_TILE), ntc = (size_t)divup(ncell, PL_TILE), cap = (size_t)pl_capacity(N, ncell);
+    const size_t ntp = (size_t)divup(N, SCAN_TILE), ntc = (size_t)divup(ncell, SCAN_TILE), cap = (size_t)pl_capacity(N, ncell);
     PlWorkspace w{};
     size_t at = 0;
     w.point_key = at; at += align256(sizeof(int) * (size_t)N);
@@ -312,7 +258,7 @@ static int pl_check_grid(const char *who, long long N, int C1, int B, int nx, in
 using namespace pdm;
 
 extern "C" size_t pdm_pillar_assign_workspace_bytes(int N, int B, int nx, int ny) {
-    if (N < 0 || B < 0 || nx < 1 || ny < 1 || (long long)B * nx * ny > 0x7fffffffll) return 0;
+    if (N < 0 || !voxel_grid_cells_ok(B, nx, ny, 1, 0x7fffffffll)) return 0;
     return pl_workspace(N, (long long)B * nx * ny).total;
 }
 
@@ -339,8 +285,8 @@ extern "C" int pdm_pillar_assign(void *stream, int N, int C1, const float *point
     int *ptile = reinterpret_cast<int *>(ws + w.ptile), *ctile_occ = reinterpret_cast<int *>(ws + w.ctile_occ);
     int *ctile_cnt = reinterpret_cast<int *>(ws + w.ctile_cnt), *cursor = reinterpret_cast<int *>(ws + w.cursor);
     long long *sums = reinterpret_cast<long long *>(ws + w.sums);
-    const PlGrid g{B, nx, ny, x0, y0, vx, vy};
-    const int ntp = divup(N, PL_TILE), ntc = divup(ncell, PL_TILE);
+    const VoxelGrid g{B, nx, ny, 1, x0, y0, 0.0f, vx, vy, 1.0f};
+    const int ntp = divup(N, SCAN_TILE), ntc = divup(ncell, SCAN_TILE);
     hipStream_t s = as_stream(stream);
     if (int rc = zero_fill(stream, "pillar_assign(zero)", cell_count, sizeof(int) * (size_t)ncell)) return rc;
     if (ntp) {
@@ -363,7 +309,7 @@ extern "C" int pdm_pillar_assign(void *stream, int N, int C1, const float *point
                            seg_start, cursor, reinterpret_cast<unsigned long long *>(sums), kept_idx, unq_inv, seg_rows);
         if (int rc = check_launch("pillar_assign(points)")) return rc;
         const long long cap3 = 3 * pl_capacity(N, ncell);
-        hipLaunchKernelGGL(pl_mean_kernel, dim3((unsigned)divup(cap3, PL_T)), dim3(PL_T), 0, s, record, sums, pillar_count, pillar_mean);
+        hipLaunchKernelGGL(fixed20_mean_kernel, dim3((unsigned)divup(cap3, SCAN_T)), dim3(SCAN_T), 0, s, record, 3, sums, pillar_count, pillar_mean);
         if (int rc = check_launch("pillar_assign(mean)")) return rc;
     }
     return 0;

@@ -33,12 +33,6 @@ struct RgqArgs {
     double *part;       // (tiles, 9)
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // A wave owns a tile of 16 grid points.  Lane s of the wave holds slot s of the current group: it stores the slot and adds its
 // offset, weighted by the slot's multiplicity in the padded tensor (slot 0 also stands for the S - cnt padding slots), to nine
 // float64 sums; after the tile one butterfly adds the lanes and lane 0 writes the tile's partial.

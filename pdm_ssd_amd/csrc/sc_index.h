@@ -9,9 +9,7 @@
 
 namespace pdm {
 
-constexpr int SC_T = 256;                  // threads per workgroup of every kernel here
-constexpr int SC_ITEMS = 8;                // scan items per thread
-constexpr int SC_TILE = SC_T * SC_ITEMS;   // scan items (groups) per workgroup
+constexpr int SC_T = SCAN_T;               // threads per workgroup of every kernel here; a scan tile is SCAN_TILE groups
 constexpr int SC_GW = 8;                   // 32-bit words per group: 256 cells
 constexpr long long SC_MAXCELL = 1ll << 35;    // 2^30 words
 
@@ -30,7 +28,7 @@ static ScIndexSize sc_index_size(long long ncell) {
     ScIndexSize z{};
     z.ngroups = (int)((ncell + 32 * SC_GW - 1) / (32 * SC_GW));
     z.nwords = z.ngroups * SC_GW;
-    z.ntiles = divup(z.ngroups, SC_TILE);
+    z.ntiles = divup(z.ngroups, SCAN_TILE);
     z.bits = align256(sizeof(unsigned) * (size_t)z.nwords);
     z.gprefix = align256(sizeof(int) * (size_t)z.ngroups);
     z.tiles = align256(sizeof(int) * (size_t)z.ntiles);
@@ -64,18 +62,7 @@ __device__ __forceinline__ void sc_set(unsigned *__restrict__ bits, long long ke
 
 // set cells of every tile of groups
 static __global__ __launch_bounds__(SC_T) void sc_tile_total_kernel(int ngroups, const unsigned *__restrict__ bits, int *__restrict__ tiles) {
-    __shared__ int s_total;
-    if (threadIdx.x == 0) s_total = 0;
-    __syncthreads();
-    int n = 0;
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        const long long g = (long long)blockIdx.x * SC_TILE + j * SC_T + threadIdx.x;
-        if (g >= ngroups) break;
-        n += sc_group_pop(bits, (int)g);
-    }
-    if (n) atomicAdd(&s_total, n);
-    __syncthreads();
-    if (threadIdx.x == 0) tiles[blockIdx.x] = s_total;
+    tile_reduce<SC_T, SCAN_ITEMS>(ngroups, {tiles}, [&](long long g, int *sum) { sum[0] += sc_group_pop(bits, (int)g); });
 }
 
 // workgroup w scans array w (two arrays at most) and leaves its total in slot w
@@ -88,16 +75,8 @@ static __global__ __launch_bounds__(SC_T) void sc_scan_tiles_kernel(int n0, int 
 
 static __global__ __launch_bounds__(SC_T) void sc_group_fill_kernel(int ngroups, const unsigned *__restrict__ bits, const int *__restrict__ tiles,
                                                                     int *__restrict__ gprefix) {
-    __shared__ int s_wave[SC_T / 64];
-    int base = tiles[blockIdx.x];
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        const long long g = (long long)blockIdx.x * SC_TILE + j * SC_T + threadIdx.x;
-        const int n = g < ngroups ? sc_group_pop(bits, (int)g) : 0;
-        int total;
-        const int excl = block_scan<SC_T>(n, s_wave, &total);
-        if (g < ngroups) gprefix[g] = base + excl;
-        base += total;
-    }
+    tile_scan<SC_T, SCAN_ITEMS>(ngroups, {tiles[blockIdx.x]}, [&](long long g, int *v) { v[0] = sc_group_pop(bits, (int)g); },
+                                [&](long long g, const int *at) { gprefix[g] = at[0]; });
 }
 
 // the scan of one or two indices: tile totals, one scan launch, group prefixes

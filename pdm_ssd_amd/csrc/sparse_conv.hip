@@ -8,12 +8,11 @@
 // race (bits are set with integer atomicOr, which commutes), so every result is a function of the input alone.
 //   * voxels of pdm_voxel_assign and output sites of a strided convolution are the set bits, numbered by rank;
 //   * the rows of a sparse tensor arrive in any order: row_of_rank[rank(key)] = row turns the bitmap into a lookup.
-// Feature sums are 64-bit fixed point (llrint(v * 2^20)) added with integer atomics, as pillar.hip's: no float atomics.
+// The grid, the cell key of a point row and the fixed-point feature sums are voxel_grid.h's, shared with the other front ends.
 #include "sc_index.h"
+#include "voxel_grid.h"
 
 namespace pdm {
-
-constexpr double SC_FIX = 1048576.0;       // 2^20
 
 // every set cell -> its coordinates (b, z, y, x) at row rank(cell); rows at or past `cap` are not written
 __global__ __launch_bounds__(SC_T) void sc_sites_kernel(int nwords, int nx, int ny, int nz, const unsigned *__restrict__ bits,
@@ -27,49 +26,22 @@ __global__ __launch_bounds__(SC_T) void sc_sites_kernel(int nwords, int nx, int 
     for (int q = g * SC_GW; q < w; ++q) id += __popc(bits[q]);
     for (; word; word &= word - 1, ++id) {
         if (id >= cap) return;
-        long long t = w * 32 + (__ffs((int)word) - 1);
-        const int z = (int)(t % nz); t /= nz;
-        const int y = (int)(t % ny); t /= ny;
-        int *c = coords + (size_t)id * 4;
-        c[0] = (int)(t / nx); c[1] = z; c[2] = y; c[3] = (int)(t % nx);
+        voxel_key_coords(w * 32 + (__ffs((int)word) - 1), nx, ny, nz, coords + (size_t)id * 4);
     }
 }
 
 // ---- a. points -> voxels --------------------------------------------------------------------------------------------
-struct ScGrid {
-    int B, nx, ny, nz;
-    float x0, y0, z0, vx, vy, vz;
-};
-
-// key of the row's voxel, or -1 when the row is dropped (outside on any axis, a sample index outside [0, B), NaN)
-__device__ __forceinline__ long long va_key(const float *__restrict__ row, const ScGrid &g) {
-    const float bf = row[0];
-    if (!(bf >= 0.0f && bf < (float)g.B)) return -1;
-    const int cx = cell_1d(row[1], g.x0, g.vx, g.nx), cy = cell_1d(row[2], g.y0, g.vy, g.ny), cz = cell_1d(row[3], g.z0, g.vz, g.nz);
-    if (cx < 0 || cy < 0 || cz < 0) return -1;
-    return (((long long)(int)bf * g.nx + cx) * g.ny + cy) * g.nz + cz;
-}
-
 // rows -> keys, occupancy bits and the kept rows of every tile of rows
-__global__ __launch_bounds__(SC_T) void va_key_kernel(int N, int C1, const float *__restrict__ points, ScGrid g, long long *__restrict__ point_key,
+__global__ __launch_bounds__(SC_T) void va_key_kernel(int N, int C1, const float *__restrict__ points, VoxelGrid g, long long *__restrict__ point_key,
                                                       unsigned *__restrict__ bits, int *__restrict__ ptile) {
-    __shared__ int s_total;
-    if (threadIdx.x == 0) s_total = 0;
-    __syncthreads();
-    int kept = 0;
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * SC_TILE + j * SC_T + threadIdx.x;
-        if (i >= N) break;
-        const long long key = va_key(points + (size_t)i * C1, g);
+    tile_reduce<SC_T, SCAN_ITEMS>(N, {ptile}, [&](long long i, int *kept) {
+        const long long key = voxel_key<true>(points + (size_t)i * C1, g);
         point_key[i] = key;
         if (key >= 0) {
             sc_set(bits, key);
-            ++kept;
+            ++kept[0];
         }
-    }
-    if (kept) atomicAdd(&s_total, kept);
-    __syncthreads();
-    if (threadIdx.x == 0) ptile[blockIdx.x] = s_total;
+    });
 }
 
 // every kept row: its place in input order, its voxel, and its columns added to the voxel's fixed-point sums
@@ -77,32 +49,18 @@ __global__ __launch_bounds__(SC_T) void va_point_kernel(int N, int C1, const flo
                                                         const int *__restrict__ ptile, const unsigned *__restrict__ bits,
                                                         const int *__restrict__ gprefix, int *__restrict__ kept_idx, int *__restrict__ unq_inv,
                                                         int *__restrict__ voxel_count, unsigned long long *__restrict__ sums) {
-    __shared__ int s_wave[SC_T / 64];
-    int base = ptile[blockIdx.x];
     const int C = C1 - 1;
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        const long long i = (long long)blockIdx.x * SC_TILE + j * SC_T + threadIdx.x;
-        const long long key = i < N ? point_key[i] : -1;
-        int total;
-        const int row = base + block_scan<SC_T>(key >= 0, s_wave, &total);
-        base += total;
-        if (key < 0) continue;
-        const int vid = sc_rank(bits, gprefix, key);
+    long long key;
+    tile_scan<SC_T, SCAN_ITEMS>(N, {ptile[blockIdx.x]}, [&](long long i, int *v) { key = point_key[i]; v[0] = key >= 0; },
+                                [&](long long i, const int *at) {
+        if (key < 0) return;
+        const int row = at[0], vid = sc_rank(bits, gprefix, key);
         kept_idx[row] = (int)i;
         unq_inv[row] = vid;
         atomicAdd(&voxel_count[vid], 1);
         const float *p = points + (size_t)i * C1 + 1;
-        for (int c = 0; c < C; ++c)     // two's complement: the unsigned add is the signed one
-            atomicAdd(&sums[(size_t)vid * C + c], (unsigned long long)llrint((double)p[c] * SC_FIX));
-    }
-}
-
-// mean = float(double(sum) * 2^-20 / count); launched at capacity, the voxel count is read on the device
-__global__ __launch_bounds__(SC_T) void va_mean_kernel(const int *__restrict__ record, int C, const long long *__restrict__ sums,
-                                                       const int *__restrict__ voxel_count, float *__restrict__ voxel_mean) {
-    const long long t = (long long)blockIdx.x * SC_T + threadIdx.x;
-    if (t >= (long long)record[1] * C) return;
-    voxel_mean[t] = (float)((double)sums[t] * (1.0 / SC_FIX) / (double)voxel_count[t / C]);
+        for (int c = 0; c < C; ++c) fixed20_add(&sums[(size_t)vid * C + c], p[c]);
+    });
 }
 
 struct VaWorkspace {
@@ -115,18 +73,11 @@ static VaWorkspace va_workspace(long long N, int C, long long ncell) {
     w.isz = sc_index_size(ncell);
     size_t at = 0;
     w.point_key = at; at += align256(sizeof(long long) * (size_t)N);
-    w.ptile = at; at += align256(sizeof(int) * (size_t)divup(N, SC_TILE));
+    w.ptile = at; at += align256(sizeof(int) * (size_t)divup(N, SCAN_TILE));
     w.index = at; at += w.isz.bits + w.isz.gprefix + w.isz.tiles;
     w.sums = at; at += align256(sizeof(long long) * (size_t)C * (size_t)va_capacity(N, ncell));
     w.total = at;
     return w;
-}
-static int va_check(const char *who, long long N, int C1, int B, int nx, int ny, int nz) {
-    PDM_REQUIRE(N >= 0 && B >= 0 && nx >= 1 && ny >= 1 && nz >= 1 && C1 >= 4, PDM_E_BADARG, "%s: bad size", who);
-    PDM_REQUIRE((long long)nx * ny <= 0x7fffffffll && (long long)nx * ny * nz <= SC_MAXCELL && (long long)B * nx * ny * nz <= SC_MAXCELL,
-                PDM_E_TOOLARGE, "%s: more than 2^35 cells", who);
-    PDM_REQUIRE(N * C1 <= 0x7fffffffll, PDM_E_TOOLARGE, "%s: %lld point elements exceed int32", who, N * C1);
-    return 0;
 }
 
 // ---- b. rulebook ------------------------------------------------------------------------------------------------------
@@ -256,7 +207,7 @@ __global__ __launch_bounds__(SC_T) void sd_scatter_kernel(int C, long long plane
 using namespace pdm;
 
 extern "C" size_t pdm_voxel_assign_workspace_bytes(int N, int C1, int B, int nx, int ny, int nz) {
-    if (N < 0 || C1 < 4 || B < 0 || nx < 1 || ny < 1 || nz < 1 || (long long)nx * ny * nz > SC_MAXCELL || (long long)B * nx * ny * nz > SC_MAXCELL) return 0;
+    if (N < 0 || C1 < 4 || !voxel_grid_cells_ok(B, nx, ny, nz, SC_MAXCELL)) return 0;
     return va_workspace(N, C1 - 1, (long long)B * nx * ny * nz).total;
 }
 
@@ -266,7 +217,7 @@ extern "C" size_t pdm_voxel_assign_workspace_bytes(int N, int C1, int B, int nx,
 extern "C" int pdm_voxel_assign(void *stream, int N, int C1, const float *points, int B, int nx, int ny, int nz, float x0, float y0, float z0,
                                 float vx, float vy, float vz, int *kept_idx, int *unq_inv, int *voxel_coords, int *voxel_count,
                                 float *voxel_mean, int *record, void *workspace, size_t workspace_bytes) {
-    if (int rc = va_check("voxel_assign", N, C1, B, nx, ny, nz)) return rc;
+    if (int rc = voxel_grid_check("voxel_assign", N, C1, B, nx, ny, nz, SC_MAXCELL, "more than 2^35 cells")) return rc;
     PDM_REQUIRE(vx > 0.0f && vy > 0.0f && vz > 0.0f, PDM_E_BADARG, "voxel_assign: voxel size must be positive");
     PDM_REQUIRE(record, PDM_E_BADARG, "voxel_assign: null pointer");
     const long long ncell = (long long)B * nx * ny * nz, cap = va_capacity(N, ncell);
@@ -282,8 +233,8 @@ extern "C" int pdm_voxel_assign(void *stream, int N, int C1, const float *points
     int *ptile = reinterpret_cast<int *>(ws + w.ptile);
     const ScIndex ix = sc_index_at(ws + w.index, w.isz);
     long long *sums = reinterpret_cast<long long *>(ws + w.sums);
-    const ScGrid g{B, nx, ny, nz, x0, y0, z0, vx, vy, vz};
-    const int ntp = divup(N, SC_TILE);
+    const VoxelGrid g{B, nx, ny, nz, x0, y0, z0, vx, vy, vz};
+    const int ntp = divup(N, SCAN_TILE);
     hipStream_t s = as_stream(stream);
     if (int rc = zero_fill(stream, "voxel_assign(zero)", ix.bits, w.isz.bits)) return rc;
     if (int rc = zero_fill(stream, "voxel_assign(zero)", sums, sizeof(long long) * (size_t)C * (size_t)cap)) return rc;
@@ -308,7 +259,7 @@ extern "C" int pdm_voxel_assign(void *stream, int N, int C1, const float *points
     hipLaunchKernelGGL(va_point_kernel, dim3((unsigned)ntp), dim3(SC_T), 0, s, N, C1, points, point_key, ptile, ix.bits, ix.gprefix, kept_idx, unq_inv,
                        voxel_count, reinterpret_cast<unsigned long long *>(sums));
     if (int rc = check_launch("voxel_assign(points)")) return rc;
-    hipLaunchKernelGGL(va_mean_kernel, dim3((unsigned)divup(cap * C, SC_T)), dim3(SC_T), 0, s, record, C, sums, voxel_count, voxel_mean);
+    hipLaunchKernelGGL(fixed20_mean_kernel, dim3((unsigned)divup(cap * C, SCAN_T)), dim3(SCAN_T), 0, s, record, C, sums, voxel_count, voxel_mean);
     return check_launch("voxel_assign(mean)");
 }
 

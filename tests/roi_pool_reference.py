@@ -131,17 +131,25 @@ def roiaware_pool3d_backward(pts_idx_of_voxels, argmax, grad_out, grad_in, pool_
 
 
 # ---- reject sampling: how close a case comes to a decision that a last-ulp difference in cosf could flip -------------
+def point_face_clearance(pts, bx):
+    """pts (N, 3), one box (7), float64 -> (per point: distance to the nearest face plane of the box, axis by axis;
+    the local coordinates lx, ly, lz)."""
+    c, s = np.cos(-bx[6]), np.sin(-bx[6])
+    sx, sy = pts[:, 0] - bx[0], pts[:, 1] - bx[1]
+    lx, ly, lz = sx * c - sy * s, sx * s + sy * c, pts[:, 2] - bx[2]
+    near = np.full(pts.shape[0], np.inf)
+    for local, d in ((lx, bx[3]), (ly, bx[4]), (lz, bx[5])):
+        near = np.minimum(near, np.abs(np.abs(local) - d / 2))
+    return near, (lx, ly, lz)
+
+
 def face_clearance(pts, boxes):
     """smallest distance (float64) of any point to any face plane of any box, axis by axis (conservative: the planes, not
     the faces)."""
     pts, boxes = np.asarray(pts, dtype=np.float64), np.asarray(boxes, dtype=np.float64)
     best = np.inf
     for bx in boxes:
-        c, s = np.cos(-bx[6]), np.sin(-bx[6])
-        sx, sy = pts[:, 0] - bx[0], pts[:, 1] - bx[1]
-        lx, ly, lz = sx * c - sy * s, sx * s + sy * c, pts[:, 2] - bx[2]
-        for local, d in ((lx, bx[3]), (ly, bx[4]), (lz, bx[5])):
-            best = min(best, float(np.min(np.abs(np.abs(local) - d / 2))))
+        best = min(best, float(np.min(point_face_clearance(pts, bx)[0])))
     return best
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import box_geometry_cases as bg
 from detector_case import scene_boxes
 from pdm_ssd_amd import post_process as pp
 from pdm_ssd_amd.detectors.detector3d_template import Detector3DTemplate
@@ -120,13 +121,14 @@ def test_tie_order_against_cpu_oracle(dev, oracle):
     for b in range(B):
         cand = np.nonzero(probs[b] >= np.float32(0.1))[0]
         order = cand[np.lexsort((cand, -probs[b, cand]))][:pre]        # score descending, lower row first
-        ref = order[oracle.nms(boxes[b, order], thresh)]
+        # the oracle's decisions; a pair whose oracle IoU lies within 1e-4 of NMS_THRESH is decided by the device's IoU
+        sorted_boxes = torch.from_numpy(boxes[b, order]).to(dev)
+        own_iou = iu.boxes_iou_bev(sorted_boxes, sorted_boxes).cpu().numpy()
+        ref = order[bg.hybrid_keep(oracle.boxes_iou_bev(boxes[b, order], boxes[b, order]), own_iou, thresh, 1e-4)]
         got = rows[b, :count[b]]
         assert (rows[b, count[b]:] == -1).all()
-        if not np.array_equal(got, ref):
-            iou = oracle.boxes_iou_bev(boxes[b, order], boxes[b, order])
-            assert (np.abs(iou - thresh) < 1e-4).any(), "NMS differs from the oracle away from the threshold"
-            assert np.array_equal(got[:1], ref[:1])
+        assert np.array_equal(got, ref)
+        assert 0 < len(ref) < len(order)
     # the tie order itself: equal scores ranked by lower row in the selection the NMS walks
     assert np.unique(probs).size < probs.size / 10
 
@@ -168,6 +170,27 @@ def test_prefilter_keeps_pdm_nms_decisions(dev, thresh, nms_type):
         c = int(out['count'][b])
         assert torch.equal(out['rows'][b, :c], keep), b
         assert c < n                                        # something was suppressed
+
+
+@pytest.mark.parametrize("n,post", [(4097, 4097), (16384, 16384), (16384, 100)])
+def test_every_slot_of_the_walk_batched(dev, n, post):
+    """bg.chain_scene with NMS_PRE_MAXSIZE = n: nms_walk's `removed` words beyond the first 4096 boxes, in the batched
+    entry.  The keep list is known by construction; the second sample is the first reversed, and the POST_MAX cut
+    takes the first `post` of the list."""
+    boxes, scores, order, keep = bg.chain_scene_of(n, seed=n)
+    B = 2
+    bx = torch.from_numpy(np.stack([boxes, boxes[::-1].copy()])).to(dev)
+    sc = torch.from_numpy(np.stack([scores, scores[::-1].copy()])).to(dev).view(B, n, 1)
+    bd = {'batch_size': B, 'batch_cls_preds': sc, 'batch_box_preds': bx, 'cls_preds_normalized': True}
+    out = pp.post_process_padded(bd, post_cfg(pre=n, post=post, thresh=0.3), 3)
+    want = [keep[:post], (n - 1 - keep)[:post]]
+    assert len(keep) > post or post == n
+    for b in range(B):
+        c = int(out['count'][b])
+        assert c == len(want[b])
+        assert np.array_equal(out['rows'][b, :c].cpu().numpy(), want[b]), b
+        assert (out['rows'][b, c:] == -1).all()
+        assert torch.equal(out['boxes'][b, :c], bx[b][out['rows'][b, :c]])
 
 
 def reference_multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh):

@@ -115,6 +115,17 @@ def stream(x):
     return torch.cuda.current_stream(getattr(x, "device", x)).cuda_stream
 
 
+def mfma_a_fragments(w):
+    """w (..., Cout, K), both multiples of 16 -> (..., Cout / 16, K / 16, 64, 4), the A fragments of mfma_f32_16x16x4f32
+    (csrc/mfma_f32.h): [nb][kb][lane][j] = w[16 nb + (lane & 15)][16 kb + 4 (lane >> 4) + j].  A permutation only, on any device;
+    the packers order the block axes as their kernel walks them."""
+    lead, (cout, k) = w.shape[:-2], w.shape[-2:]
+    assert cout % 16 == 0 and k % 16 == 0, (cout, k)
+    n = len(lead)
+    w = w.reshape(*lead, cout // 16, 16, k // 16, 4, 4)                  # (nb, i, kb, g, j)
+    return w.permute(*range(n), n, n + 2, n + 3, n + 1, n + 4).reshape(*lead, cout // 16, k // 16, 64, 4)
+
+
 def host_array(ctype, values):
     """A ctypes array of `values`, passed as it is for a pointer parameter and alive for the call; at least one element,
     so that an empty list still gives a valid pointer."""

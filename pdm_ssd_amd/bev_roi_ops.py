@@ -106,7 +106,7 @@ def pack_crop_fc_weight(weight, channels, grid_size):
     C, G = int(channels), int(grid_size)
     if K != C * G * G or C % 16 or cout % 16:
         raise ValueError(f'bev_roi_crop_fc: weight {tuple(weight.shape)} for C = {C}, G = {G}; C and Cout must be multiples of 16')
-    out = w.reshape(cout // 16, 16, K // 16, 4, 4).permute(2, 0, 3, 1, 4).contiguous().reshape(-1)      # (kb, nb, g, i, j)
+    out = _native.mfma_a_fragments(w).transpose(0, 1).reshape(-1)      # (kb, nb, lane, j)
     assert not out.is_cuda or out.numel() == _native.lib().pdm_bev_roi_crop_fc_packed_floats(C, G, cout)
     return out
 

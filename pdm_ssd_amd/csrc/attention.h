@@ -1,27 +1,13 @@
 // What the attention forward (attention.hip) and backward (attention_bwd.hip) share: the supported set, the default
-// chunking, the 16-byte row read and the host side of the dropout parameters.
+// chunking and the host side of the dropout parameters.
 #pragma once
 #include <math.h>
 
-#include "common.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int MHA_DEFAULT_CHUNK = 1024;
-
-__device__ __forceinline__ f32x4 mha_load4(const float *p, int vec) {
-    if (vec) return *reinterpret_cast<const f32x4 *>(p);
-    f32x4 r;
-    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3];
-    return r;
-}
-
-__device__ __forceinline__ void mha_store4(float *p, f32x4 x, int vec) {
-    if (vec) { *reinterpret_cast<f32x4 *>(p) = x; return; }
-    p[0] = x[0]; p[1] = x[1]; p[2] = x[2]; p[3] = x[3];
-}
 
 static inline int mha_chunk(int keys_per_chunk) { return keys_per_chunk > 0 ? keys_per_chunk : MHA_DEFAULT_CHUNK; }
 

@@ -64,13 +64,13 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
     const float *qp = a.q + ((size_t)b * a.P + qrow) * a.qs + h * D + 4 * grp;
     const float *kb = a.k + (size_t)b * a.N * a.ks + h * D + 4 * grp;
     const float *vb = a.v + (size_t)b * a.N * a.vs + h * D + col;
-    f32x4 qv[DT];
+    f4 qv[DT];
 #pragma unroll
-    for (int t = 0; t < DT; ++t) qv[t] = mha_load4(qp + 16 * t, a.vec);
+    for (int t = 0; t < DT; ++t) qv[t] = load_quad(qp + 16 * t, a.vec);
 
-    f32x4 acc[DT][2];
+    f4 acc[DT][2];
 #pragma unroll
-    for (int t = 0; t < DT; ++t) { acc[t][0] = f32x4{0, 0, 0, 0}; acc[t][1] = f32x4{0, 0, 0, 0}; }
+    for (int t = 0; t < DT; ++t) { acc[t][0] = f4{0, 0, 0, 0}; acc[t][1] = f4{0, 0, 0, 0}; }
     float m = -INFINITY, lsum = 0.0f;
     unsigned dkey = 0;
     if constexpr (TRAIN) {
@@ -78,15 +78,15 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
     }
 
     for (int kt = k_lo; kt < k_hi; kt += MHA_KT) {
-        f32x4 s[4];
+        f4 s[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int krow = min(kt + 16 * j + col, k_hi - 1);
             const float *kp = kb + (size_t)krow * a.ks;
-            s[j] = f32x4{0, 0, 0, 0};
+            s[j] = f4{0, 0, 0, 0};
 #pragma unroll
             for (int t = 0; t < DT; ++t) {
-                const f32x4 kv = mha_load4(kp + 16 * t, a.vec);
+                const f4 kv = load_quad(kp + 16 * t, a.vec);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) s[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[i], qv[t][i], s[j], 0, 0, 0);
             }
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(MHA_T) void mha_partial_kernel(MhaArgs a) {
     float *o = a.acc + row * D + 4 * grp;                            // O^T: row = channel 4 grp + r, column = the query
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
-        const f32x4 x = acc[t][0] + acc[t][1];
+        const f4 x = acc[t][0] + acc[t][1];
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[16 * t + r] = x[r];
     }

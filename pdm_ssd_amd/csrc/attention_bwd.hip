@@ -63,18 +63,18 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
     const int krow_c = min(k0 + col, a.N - 1);
     const float *kb = a.k + (size_t)b * a.N * a.ks + h * D;
     const float *vb = a.v + (size_t)b * a.N * a.vs + h * D;
-    f32x4 kA[DT], vA[DT];                                              // [key col][channels 16 t + 4 grp ..]
+    f4 kA[DT], vA[DT];                                              // [key col][channels 16 t + 4 grp ..]
     float kS[DT][4];                                                   // [key 4 grp + r][channel 16 t + col]
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
-        kA[t] = mha_load4(kb + (size_t)krow_c * a.ks + 16 * t + 4 * grp, a.vec);
-        vA[t] = mha_load4(vb + (size_t)krow_c * a.vs + 16 * t + 4 * grp, a.vec);
+        kA[t] = load_quad(kb + (size_t)krow_c * a.ks + 16 * t + 4 * grp, a.vec);
+        vA[t] = load_quad(vb + (size_t)krow_c * a.vs + 16 * t + 4 * grp, a.vec);
 #pragma unroll
         for (int r = 0; r < 4; ++r) kS[t][r] = kb[(size_t)min(k0 + 4 * grp + r, a.N - 1) * a.ks + 16 * t + col];
     }
-    f32x4 dk[DT], dv[DT];                                              // ^T: [channel 16 t + 4 grp + r][key col]
+    f4 dk[DT], dv[DT];                                              // ^T: [channel 16 t + 4 grp + r][key col]
 #pragma unroll
-    for (int t = 0; t < DT; ++t) { dk[t] = f32x4{0, 0, 0, 0}; dv[t] = f32x4{0, 0, 0, 0}; }
+    for (int t = 0; t < DT; ++t) { dk[t] = f4{0, 0, 0, 0}; dv[t] = f4{0, 0, 0, 0}; }
     const unsigned step = a.drop ? a.used_step[0] : 0u;
     const size_t bh = (size_t)b * a.H + h;
     const float *qb = a.q + (size_t)b * a.P * a.qs + h * D;
@@ -83,12 +83,12 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
 
     for (int q0 = 0; q0 < a.P; q0 += 16) {
         const int qrow = min(q0 + col, a.P - 1);
-        f32x4 qB[DT], doB[DT];                                         // [query col][channels 16 t + 4 grp ..]
+        f4 qB[DT], doB[DT];                                         // [query col][channels 16 t + 4 grp ..]
         float qS[DT][4], doS[DT][4];                                   // [query 4 grp + r][channel 16 t + col]
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
-            qB[t] = mha_load4(qb + (size_t)qrow * a.qs + 16 * t + 4 * grp, a.vec);
-            doB[t] = mha_load4(dob + (size_t)qrow * a.C + 16 * t + 4 * grp, a.vec);
+            qB[t] = load_quad(qb + (size_t)qrow * a.qs + 16 * t + 4 * grp, a.vec);
+            doB[t] = load_quad(dob + (size_t)qrow * a.C + 16 * t + 4 * grp, a.vec);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qr = min(q0 + 4 * grp + r, a.P - 1);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
         unsigned dkey = 0;
         if (a.drop) dkey = draw_key(a.seed, step, (unsigned)blockIdx.y, (unsigned)(q0 + col));
 
-        f32x4 s = f32x4{0, 0, 0, 0}, dp = f32x4{0, 0, 0, 0};          // [key 4 grp + r][query col]
+        f4 s = f4{0, 0, 0, 0}, dp = f4{0, 0, 0, 0};          // [key 4 grp + r][query col]
 #pragma unroll
         for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
                 s = __builtin_amdgcn_mfma_f32_16x16x4f32(kA[t][i], qB[t][i], s, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vA[t][i], doB[t][i], dp, 0, 0, 0);
             }
-        f32x4 pd, ds;
+        f4 pd, ds;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = k0 + 4 * grp + r;
@@ -122,15 +122,15 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
             ds[r] = p * (dp[r] * w - delta);
         }
         // the tiles transposed: written [query col][keys 4 grp ..], read [query 4 grp + r][key col]
-        *reinterpret_cast<f32x4 *>(&s_pd[wave][col * 16 + 4 * grp]) = pd;
-        *reinterpret_cast<f32x4 *>(&s_ds[wave][col * 16 + 4 * grp]) = ds;
-        f32x4 dq[DT];
+        *reinterpret_cast<f4 *>(&s_pd[wave][col * 16 + 4 * grp]) = pd;
+        *reinterpret_cast<f4 *>(&s_ds[wave][col * 16 + 4 * grp]) = ds;
+        f4 dq[DT];
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
-            dq[t] = f32x4{0, 0, 0, 0};
+            dq[t] = f4{0, 0, 0, 0};
 #pragma unroll
             for (int r = 0; r < 4; ++r) dq[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kS[t][r], ds[r], dq[t], 0, 0, 0);
-            *reinterpret_cast<f32x4 *>(&s_dq[wave][col * D + 16 * t + 4 * grp]) = dq[t];   // [channel 16 t + 4 grp + r][query col]
+            *reinterpret_cast<f4 *>(&s_dq[wave][col * D + 16 * t + 4 * grp]) = dq[t];   // [channel 16 t + 4 grp + r][query col]
         }
         __syncthreads();
 #pragma unroll
@@ -156,8 +156,8 @@ __global__ __launch_bounds__(NW * 64) void mha_bwd_kernel(MhaBwdArgs a) {
     float *dvp = a.dv + ((size_t)b * a.N + k0 + col) * a.dvs + h * D + 4 * grp;
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
-        mha_store4(dkp + 16 * t, dk[t] * a.scale, a.vec);
-        mha_store4(dvp + 16 * t, dv[t], a.vec);
+        store_quad(dkp + 16 * t, dk[t] * a.scale, a.vec);
+        store_quad(dvp + 16 * t, dv[t], a.vec);
     }
 }
 

@@ -24,8 +24,8 @@
 // of (R, C, G, Cout) alone: no atomics, two runs give the same bits.
 #include <algorithm>
 
-#include "common.h"
 #include "fc_reduce.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
@@ -107,8 +107,6 @@ constexpr int CFC_TR = 32;              // RoIs a workgroup owns: two 16-wide B 
 constexpr int CFC_KS = 128;             // contraction indices a stage holds in LDS
 constexpr int CFC_XS = CFC_KS + 4;      // the staged rows' stride in floats
 constexpr int CFC_NCO = 256;            // output channels a workgroup owns: 4 blocks of 16 per wave
-constexpr int CFC_TARGET_WGS = 1024;    // workgroups the grid aims at
-typedef float cfc4 __attribute__((ext_vector_type(4)));
 
 struct CfcPlan {
     int tiles, cblocks, nstage, chunk_stages, nchunk;
@@ -119,9 +117,9 @@ static CfcPlan cfc_plan(int R, int C, int G, int Cout) {
     p.tiles = divup(std::max(R, 1), CFC_TR);
     p.cblocks = divup(Cout, CFC_NCO);
     p.nstage = divup((long long)C * G * G, CFC_KS);
-    const int want = std::min(p.nstage, std::max(1, divup(CFC_TARGET_WGS, (long long)p.tiles * p.cblocks)));
-    p.chunk_stages = divup(p.nstage, want);
-    p.nchunk = divup(p.nstage, p.chunk_stages);
+    const SplitK k = split_k_plan(p.nstage, (long long)p.tiles * p.cblocks);
+    p.chunk_stages = k.chunk;
+    p.nchunk = k.nchunk;
     return p;
 }
 
@@ -153,13 +151,12 @@ __global__ __launch_bounds__(CFC_NT) void bev_roi_crop_fc_kernel(CfcArgs a) {
     }
     if (tid < CFC_TR) s_sample[tid] = min(r_lo + tid, a.R - 1) / a.n;
 
-    cfc4 acc[4][2];
+    f4 acc[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc[q][t] = cfc4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 2; ++t) acc[q][t] = f4{0.f, 0.f, 0.f, 0.f};
     const int nb0 = blockIdx.z * (CFC_NCO / 16) + wave;        // the wave's blocks of 16 channels: nb0 + 4 q
-    const cfc4 *wp = reinterpret_cast<const cfc4 *>(a.wpack);
 
     const int s_lo = blockIdx.y * a.chunk_stages, s_hi = min(a.nstage, s_lo + a.chunk_stages);
     for (int s = s_lo; s < s_hi; ++s) {
@@ -174,27 +171,18 @@ __global__ __launch_bounds__(CFC_NT) void bev_roi_crop_fc_kernel(CfcArgs a) {
         }
         __syncthreads();
         for (int kb = 0; kb < ks / 16; ++kb) {
-            const cfc4 fb0 = *reinterpret_cast<const cfc4 *>(s_x + pos * CFC_XS + 16 * kb + 4 * gq);
-            const cfc4 fb1 = *reinterpret_cast<const cfc4 *>(s_x + (16 + pos) * CFC_XS + 16 * kb + 4 * gq);
+            const f4 fb[2] = {b_frag(s_x, pos, CFC_XS, kb, gq), b_frag(s_x, 16 + pos, CFC_XS, kb, gq)};
             const size_t kbg = (size_t)(k0 / 16 + kb) * NB;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int nb = nb0 + 4 * q;
                 if (nb < NB) {          // wave-uniform
-                    const cfc4 fa = wp[(kbg + nb) * 64 + lane];
-                    acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb0.x, acc[q][0], 0, 0, 0);
-                    acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb1.x, acc[q][1], 0, 0, 0);
-                    acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb0.y, acc[q][0], 0, 0, 0);
-                    acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb1.y, acc[q][1], 0, 0, 0);
-                    acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb0.z, acc[q][0], 0, 0, 0);
-                    acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb1.z, acc[q][1], 0, 0, 0);
-                    acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb0.w, acc[q][0], 0, 0, 0);
-                    acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb1.w, acc[q][1], 0, 0, 0);
+                    mfma4_grid(acc[q], a_frag(a.wpack, kbg + nb, lane), fb);
                 }
             }
         }
     }
-    // lane (pos, gq), register j of tile t = RoI r_lo + 16 t + pos, channel 16 nb + 4 gq + j
+    // D layout of mfma_f32.h: tile t is RoI r_lo + 16 t + pos, g = gq
     float *part = a.partial + (size_t)blockIdx.y * a.R * a.Cout;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -202,7 +190,7 @@ __global__ __launch_bounds__(CFC_NT) void bev_roi_crop_fc_kernel(CfcArgs a) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int r = r_lo + 16 * t + pos;
-            if (nb < NB && r < a.R) *reinterpret_cast<cfc4 *>(part + (size_t)r * a.Cout + 16 * nb + 4 * gq) = acc[q][t];
+            if (nb < NB && r < a.R) *reinterpret_cast<f4 *>(part + (size_t)r * a.Cout + 16 * nb + 4 * gq) = acc[q][t];
         }
     }
 }

@@ -19,14 +19,12 @@
 //               NEXT layer reads as its B operand, so the epilogue is bias + ReLU + one ds_write_b128.
 // Features are point-major ((B, N, C), C contiguous) inside the fused path so a gathered neighbour is
 // one contiguous row.  Max-pool over nsample = DPP row-max over the 16 lanes that share g.
-#include "common.h"
+#include "mfma_f32.h"
 
 #include <mutex>
 #include <set>
 
 namespace pdm {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int FM_MAXL = 4;
 
@@ -78,22 +76,6 @@ struct FpArgs {
     const float *z;       // (B,m,z_stride) pre-projected layer-1 partial sums of the known points, or null
     int z_stride;
 };
-
-__device__ __forceinline__ f4 mfma4(f4 acc, f4 a, f4 b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    return acc;
-}
-
-// max(v, floor) as one v_med3_f32 (fmaxf() costs a canonicalising v_max v,v,v on top; inline asm would hide the
-// MFMA -> VALU read hazard from the compiler).  floor = 0 for ReLU, -inf for a linear last layer.
-__device__ __forceinline__ float max1(float v, float floor) { return __builtin_amdgcn_fmed3f(v, floor, __builtin_inff()); }
-__device__ __forceinline__ f4 floor4(f4 v, float floor) {
-    v.x = max1(v.x, floor); v.y = max1(v.y, floor); v.z = max1(v.z, floor); v.w = max1(v.w, floor);
-    return v;
-}
 
 // max over the 16 lanes of a DPP row (values are >= 0 after ReLU, so the integer image orders them)
 __device__ __forceinline__ float row16_max_nonneg(float f) {
@@ -310,14 +292,7 @@ struct PoolOut {
             *reinterpret_cast<f4 *>(p) = v;
             return;
         }
-        const int c0 = 16 * mb + 4 * g;
-        if (c0 + 4 <= cout) {
-            *reinterpret_cast<f4 *>(orow + c0) = v;  // host guarantees 16-byte alignment of orow
-        } else {
-            if (c0 < cout) orow[c0] = v.x;
-            if (c0 + 1 < cout) orow[c0 + 1] = v.y;
-            if (c0 + 2 < cout) orow[c0 + 2] = v.z;
-        }
+        store_quad_ragged(orow, 16 * mb + 4 * g, cout, v);  // host guarantees 16-byte alignment of orow
     }
 };
 
@@ -340,14 +315,7 @@ struct SegPoolOut {
             *reinterpret_cast<f4 *>(p) = v;
             return;
         }
-        const int c0 = 16 * mb + 4 * g;
-        if (c0 + 4 <= cout) {
-            *reinterpret_cast<f4 *>(orow + c0) = v;
-        } else {
-            if (c0 < cout) orow[c0] = v.x;
-            if (c0 + 1 < cout) orow[c0 + 1] = v.y;
-            if (c0 + 2 < cout) orow[c0 + 2] = v.z;
-        }
+        store_quad_ragged(orow, 16 * mb + 4 * g, cout, v);
     }
 };
 
@@ -356,14 +324,7 @@ struct RowOut {
     int cout, g;
     __device__ __forceinline__ void operator()(int mb, f4 v) const {
         if (!orow) return;
-        const int c0 = 16 * mb + 4 * g;
-        if (c0 + 4 <= cout) {
-            *reinterpret_cast<f4 *>(orow + c0) = v;
-        } else {
-            if (c0 < cout) orow[c0] = v.x;
-            if (c0 + 1 < cout) orow[c0 + 1] = v.y;
-            if (c0 + 2 < cout) orow[c0 + 2] = v.z;
-        }
+        store_quad_ragged(orow, 16 * mb + 4 * g, cout, v);
     }
 };
 
@@ -475,6 +436,8 @@ __device__ __forceinline__ void mlp_pass(int nkb, int mb, const f4 *__restrict__
         continue;
 #endif
 #pragma unroll
+        // (mfma4_grid of mfma_f32.h, written out here and in PDM_MFMA_BLOCK below: through the shared function the generated code of
+        //  this file's kernels moves beyond register names and branch polarity, profiles/mfma_f32_shared.json)
         for (int i = 0; i < NB; ++i)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -922,17 +885,6 @@ __device__ __forceinline__ void sa_reg_hidden(const f4 (&A1)[B1], const f4 (&A2)
     }
 }
 
-// channels c0 .. c0 + 3 of an output row whose width need not be a multiple of 4
-__device__ __forceinline__ void sa_reg_store4(float *orow, int c0, int cout, f4 v) {
-    if (c0 + 4 <= cout) {
-        *reinterpret_cast<f4 *>(orow + c0) = v;
-    } else {
-        if (c0 < cout) orow[c0] = v.x;
-        if (c0 + 1 < cout) orow[c0 + 1] = v.y;
-        if (c0 + 2 < cout) orow[c0 + 2] = v.z;
-    }
-}
-
 // Grouped neighbours (B, M, nsample): a wave walks (unit, sub-step, tile) and pools across the sub-steps of a centre.
 template <int B1, int B2, int B3, bool SAME>   // SAME: nsample >= 32, the two tiles of a step share their centre
 __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *__restrict__ wpack,
@@ -1033,7 +985,7 @@ __global__ __launch_bounds__(256) void sa_reg_mlp_kernel(SaArgs a, const float *
             if (ctr >= ncentres || pos != 0) continue;
             float *orow = a.out + (size_t)ctr * a.out_stride + a.out_coff;
 #pragma unroll
-            for (int mb = 0; mb < B3; ++mb) sa_reg_store4(orow, 16 * mb + 4 * g, a.cout, best[t][mb]);
+            for (int mb = 0; mb < B3; ++mb) store_quad_ragged(orow, 16 * mb + 4 * g, a.cout, best[t][mb]);
         }
     }
 }
@@ -1102,7 +1054,7 @@ __global__ __launch_bounds__(256) void sa_reg_packed_kernel(SaArgs a, const int2
             }
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                if (orow[t]) sa_reg_store4(orow[t], 16 * mb + 4 * g, a.cout, v[t]);
+                if (orow[t]) store_quad_ragged(orow[t], 16 * mb + 4 * g, a.cout, v[t]);
         }
     }
 }

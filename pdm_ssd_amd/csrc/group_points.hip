@@ -10,6 +10,7 @@
 // store per thread and re-reads the index for every channel.
 #include "bf16.h"
 #include "csr.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
@@ -19,9 +20,8 @@ constexpr int GP_CG = 8;  // channels per workgroup (index registers reused acro
 // vectorised: L % 4 == 0, idx/out 16-byte aligned
 // outputs are written once and read by another kernel much later: non-temporal stores keep them from displacing the index and
 // source lines the gathers hit in L2 (pdm_tune_group_nt; measured with tools/diag/api_block_ab.py)
-typedef float gp_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void gp_store4(float *p, const float4 &v, int nt) {
-    if (nt) __builtin_nontemporal_store(gp_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<gp_f4 *>(p));
+    if (nt) __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4 *>(p));
     else *reinterpret_cast<float4 *>(p) = v;
 }
 

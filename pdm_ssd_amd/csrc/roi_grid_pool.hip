@@ -12,14 +12,12 @@
 // fragment order of sparse_conv_mfma.hip, staged once per workgroup) and the epilogue relu(acc * scale + shift), written at
 // a column offset into rows of the full stride.  No atomics and nothing summed across waves: two runs and a graph replay give
 // the same bits.
+#include "mfma_f32.h"
 #include "roi_grid_geom.h"
 
 namespace pdm {
 
-typedef float gf4 __attribute__((ext_vector_type(4)));
-
 constexpr int RGP_T = 256;          // 4 waves
-constexpr int RGP_HS = 24;          // LDS row stride of a 16-channel slice of the pooled rows (sparse_conv_mfma.hip's SCV_HS)
 constexpr int RGP_MAXBLOCKS = 2048; // workgroups at most; waves walk the tiles with this stride
 
 struct RgpArgs {
@@ -43,13 +41,13 @@ template <int C1, int NB>
 __global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
     constexpr int NKB = C1 / 16, SUB = 64 / C1;
     __shared__ __attribute__((aligned(16))) float s_w[NKB * NB * 256];
-    __shared__ __attribute__((aligned(16))) float s_pool[RGP_T / 64][NKB * RGP_TILE * RGP_HS];
+    __shared__ __attribute__((aligned(16))) float s_pool[RGP_T / 64][NKB * RGP_TILE * MFMA_ROW_STRIDE];
     __shared__ int s_hrow[RGP_T / 64][RGP_MAXS];
     __shared__ float s_hd[RGP_T / 64][RGP_MAXS * 3];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    for (int q = tid; q < NKB * NB * 64; q += RGP_T) reinterpret_cast<gf4 *>(s_w)[q] = reinterpret_cast<const gf4 *>(a.wout)[q];
+    for (int q = tid; q < NKB * NB * 64; q += RGP_T) reinterpret_cast<f4 *>(s_w)[q] = reinterpret_cast<const f4 *>(a.wout)[q];
     __syncthreads();
 
     const int c = lane % C1, sub = lane / C1;       // gather role: channel c of the hits sub, sub + SUB, ...
@@ -87,26 +85,20 @@ __global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
 #pragma unroll
                 for (int off = C1; off < 64; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
             }
-            if (lane < C1) pool[((c >> 4) * RGP_TILE + i) * RGP_HS + (c & 15)] = v;
+            if (lane < C1) pool[((c >> 4) * RGP_TILE + i) * MFMA_ROW_STRIDE + (c & 15)] = v;
             __builtin_amdgcn_wave_barrier();
         }
 
-        // out rows of the tile: C1 -> C2 on the exact f32 MFMA; lane (pos, g), register j of block nb = channel 16 nb + 4 g + j
+        // out rows of the tile: C1 -> C2 on the exact f32 MFMA (fragment layout: mfma_f32.h)
         const int pos = lane & 15, g = lane >> 4;
-        gf4 acc[NB];
+        f4 acc[NB];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = gf4{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
-            const gf4 fb = *reinterpret_cast<const gf4 *>(&pool[(kb * RGP_TILE + pos) * RGP_HS + 4 * g]);
+            const f4 fb = b_frag(pool, kb * RGP_TILE + pos, MFMA_ROW_STRIDE, 0, g);
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const gf4 fa = reinterpret_cast<const gf4 *>(s_w)[(kb * NB + nb) * 64 + lane];
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb.x, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb.y, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb.z, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb.w, acc[nb], 0, 0, 0);
-            }
+            for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma4(acc[nb], a_frag(s_w, kb * NB + nb, lane), fb);
         }
         __builtin_amdgcn_wave_barrier();        // the next tile's rows overwrite `pool`
         const long long m = tile * RGP_TILE + pos;
@@ -116,18 +108,7 @@ __global__ __launch_bounds__(RGP_T) void roi_grid_pool_kernel(RgpArgs a) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int c0 = 16 * nb + 4 * g;
-            float o[4] = {acc[nb].x, acc[nb].y, acc[nb].z, acc[nb].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                o[j] = __fmaf_rn(o[j], a.scale_o[c0 + j], a.shift_o[c0 + j]);
-                o[j] = o[j] < 0.0f ? 0.0f : o[j];
-            }
-            if (vec_o) {
-                *reinterpret_cast<gf4 *>(orow + c0) = gf4{o[0], o[1], o[2], o[3]};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) orow[c0 + j] = o[j];
-            }
+            store_quad(orow + c0, scale_shift_relu4(acc[nb], a.scale_o, a.shift_o, c0, true), vec_o);
         }
     }
 }

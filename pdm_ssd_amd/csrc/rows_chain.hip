@@ -17,11 +17,10 @@
 //     registers one chunk ahead and written to the other buffer behind the MFMAs: one barrier per 64 MFMAs per wave;
 //   * everything is unrolled (the register arrays need constant indices): one instantiation per chain of widths.
 // Bound: fp32 MFMA pipe (16 MFMAs per 4 ds_read_b128; LDS 32 B/clk/CU, L2 -> LDS 16 KB per 2048 pipe cycles).
-#include "common.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 #ifndef DW_PIN
 #define DW_PIN 1    // depthwise prologue: slices whose tap reads may be in flight together
 #endif
@@ -163,13 +162,7 @@ __device__ __forceinline__ void rc_layer(const f4 (&in)[NKB], f4 (&acc)[NMB], co
                 for (int i = 0; i < 4; ++i) an[i] = nbuf[(i * 4) * 64];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f4 b = in[4 * kbi + i];
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b.x, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b.y, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b.z, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b.w, acc[0], 0, 0, 0);
-            }
+            for (int i = 0; i < 4; ++i) acc[0] = mfma4(acc[0], a[i], in[4 * kbi + i]);
             __builtin_amdgcn_sched_barrier(0);
         }
         p ^= 1;
@@ -215,19 +208,7 @@ __device__ __forceinline__ void rc_layer(const f4 (&in)[NKB], f4 (&acc)[NMB], co
             }
             // (pinning these reads in front of the k-block's MFMAs with a sched_barrier measured 1 % slower than the scheduler's own
             //  placement behind the 14th MFMA)
-            const f4 b = in[kb0 + kbi];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nmb) acc[mb0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b.x, acc[mb0 + i], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nmb) acc[mb0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b.y, acc[mb0 + i], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nmb) acc[mb0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b.z, acc[mb0 + i], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nmb) acc[mb0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b.w, acc[mb0 + i], 0, 0, 0);
+            mfma4_grid(&acc[mb0], a, in[kb0 + kbi], nmb);
             // keeps the fragment loads of later k-blocks from piling up in registers
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -235,7 +216,8 @@ __device__ __forceinline__ void rc_layer(const f4 (&in)[NKB], f4 (&acc)[NMB], co
     }
     }
 #pragma unroll
-    for (int mb = 0; mb < NMB; ++mb) {
+    for (int mb = 0; mb < NMB; ++mb) {   // (floor4, written out: with a constant floor of -inf the compiler folds floor4's med3 to max(v, -inf)
+                                         //  and this form to min(v, +inf), which differ for a NaN; profiles/mfma_f32_shared.json)
         acc[mb].x = __builtin_amdgcn_fmed3f(acc[mb].x, floor, __builtin_inff());
         acc[mb].y = __builtin_amdgcn_fmed3f(acc[mb].y, floor, __builtin_inff());
         acc[mb].z = __builtin_amdgcn_fmed3f(acc[mb].z, floor, __builtin_inff());
@@ -422,15 +404,7 @@ __global__ __launch_bounds__(RC_THREADS, DW ? DW_WGS : 2) void rows_chain_kernel
         auto store = [&](auto &y, int nmb) {
             if (!orow) return;
 #pragma unroll
-            for (int mb = 0; mb < nmb; ++mb) {
-                const int c0 = 16 * mb + 4 * g;
-                if (c0 + 4 <= a.cout) *reinterpret_cast<f4 *>(orow + c0) = y[mb];
-                else {
-                    if (c0 < a.cout) orow[c0] = y[mb].x;
-                    if (c0 + 1 < a.cout) orow[c0 + 1] = y[mb].y;
-                    if (c0 + 2 < a.cout) orow[c0 + 2] = y[mb].z;
-                }
-            }
+            for (int mb = 0; mb < nmb; ++mb) store_quad_ragged(orow, 16 * mb + 4 * g, a.cout, y[mb]);
         };
 #if RC_DIAG & 4   // phase timestamps of wave 0 (first two tiles of each workgroup) instead of results: tools/diag/rows_chain_phase.py
         long long ts[4];
@@ -541,15 +515,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void rows_chain_pair_kernel(RowsChai
             float *__restrict__ orow = a.out[br] + (size_t)row * a.out_stride[br];
             const int cout = a.cout[br];
 #pragma unroll
-            for (int mb = 0; mb < NK3; ++mb) {
-                const int c0 = 16 * mb + 4 * g;
-                if (c0 + 4 <= cout) *reinterpret_cast<f4 *>(orow + c0) = y[mb];
-                else {
-                    if (c0 < cout) orow[c0] = y[mb].x;
-                    if (c0 + 1 < cout) orow[c0 + 1] = y[mb].y;
-                    if (c0 + 2 < cout) orow[c0 + 2] = y[mb].z;
-                }
-            }
+            for (int mb = 0; mb < NK3; ++mb) store_quad_ragged(orow, 16 * mb + 4 * g, cout, y[mb]);
         };
         {   // branch A (x0 stays live for branch B: it takes the place the next tile's rows hold in rows_chain_kernel)
             f4 x1[NK1], x2[NK2], x3[NK3];
@@ -813,15 +779,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void fp_chain_kernel(FpChainArgs a) 
                 float *__restrict__ orow = a.hout[br] + (size_t)row * a.hout_stride[br];
                 const int cout = a.hcout[br];
 #pragma unroll
-                for (int mb = 0; mb < H3; ++mb) {
-                    const int c0 = 16 * mb + 4 * g;
-                    if (c0 + 4 <= cout) *reinterpret_cast<f4 *>(orow + c0) = y[mb];
-                    else {
-                        if (c0 < cout) orow[c0] = y[mb].x;
-                        if (c0 + 1 < cout) orow[c0 + 1] = y[mb].y;
-                        if (c0 + 2 < cout) orow[c0 + 2] = y[mb].z;
-                    }
-                }
+                for (int mb = 0; mb < H3; ++mb) store_quad_ragged(orow, 16 * mb + 4 * g, cout, y[mb]);
             };
             {   // class stack (x2 stays live for the box stack)
                 f4 y1[H1], y2[H2], y3[H3];

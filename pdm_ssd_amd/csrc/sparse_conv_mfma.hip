@@ -14,15 +14,12 @@
 // (48 KB of weight and row stages instead of 32).  An output element's chain (k ascending, kb ascending, four MFMA steps a block)
 // does not depend on how the output columns are blocked, so for Cin, Cout <= 128 the wide entries run the narrow instantiations
 // and give the narrow entries' bits.
-#include "common.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
-typedef float sf4 __attribute__((ext_vector_type(4)));
-
 constexpr int SCV_ROWS = 64;    // output rows per workgroup
 constexpr int SCV_T = 256;      // 4 waves
-constexpr int SCV_HS = 24;      // LDS row stride of the gathered rows in floats (16 + 8 pad: rows_gemm.hip's bank argument)
 constexpr int SCV_MAXK = 27;    // offsets at most (3 x 3 x 3): the tile's mask is one 32-bit word
 
 struct ScvArgs {
@@ -38,7 +35,7 @@ template <int NB, bool SPLIT>
 __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
     __shared__ int s_nbr[SCV_ROWS * SCV_MAXK];
     __shared__ unsigned s_mask;
-    __shared__ __attribute__((aligned(16))) float s_x[2][SCV_ROWS * SCV_HS];
+    __shared__ __attribute__((aligned(16))) float s_x[2][SCV_ROWS * MFMA_ROW_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_w[2][NB * 64 * 4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -66,36 +63,29 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
     const int hrow = tid >> 2, part = tid & 3;
     const bool vec_x = (a.cin & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
     auto load_x = [&](int k, int kb) {
-        sf4 v = {0.f, 0.f, 0.f, 0.f};
         const int r = s_nbr[hrow * a.kvol + k];
-        if (r < 0) return v;
+        if (r < 0) return f4{0.f, 0.f, 0.f, 0.f};
         const int c = 16 * kb + 4 * part;
-        const float *p = a.x + (size_t)r * a.cin + c;
-        if (vec_x && c + 4 <= a.cin) return *reinterpret_cast<const sf4 *>(p);
-        if (c < a.cin) v.x = p[0];
-        if (c + 1 < a.cin) v.y = p[1];
-        if (c + 2 < a.cin) v.z = p[2];
-        if (c + 3 < a.cin) v.w = p[3];
-        return v;
+        return load_quad_ragged(a.x + (size_t)r * a.cin + c, c, a.cin, vec_x);
     };
     constexpr int WQ = (NB * 64 + SCV_T - 1) / SCV_T;      // float4s of a weight slice per thread
-    struct Regs { sf4 x, w[WQ]; };
+    struct Regs { f4 x, w[WQ]; };
     auto load = [&](int k, int kb) {
         Regs r;
         r.x = load_x(k, kb);
-        const sf4 *src = reinterpret_cast<const sf4 *>(a.wpack) + ((size_t)k * a.nkb + kb) * (NB * 64);
+        const f4 *src = reinterpret_cast<const f4 *>(a.wpack) + ((size_t)k * a.nkb + kb) * (NB * 64);
 #pragma unroll
         for (int q = 0; q < WQ; ++q) {
-            r.w[q] = sf4{0.f, 0.f, 0.f, 0.f};
+            r.w[q] = f4{0.f, 0.f, 0.f, 0.f};
             if (tid + q * SCV_T < NB * 64) r.w[q] = src[tid + q * SCV_T];
         }
         return r;
     };
     auto stage = [&](int buf, const Regs &r) {
-        *reinterpret_cast<sf4 *>(&s_x[buf][hrow * SCV_HS + 4 * part]) = r.x;
+        *reinterpret_cast<f4 *>(&s_x[buf][hrow * MFMA_ROW_STRIDE + 4 * part]) = r.x;
 #pragma unroll
         for (int q = 0; q < WQ; ++q)
-            if (tid + q * SCV_T < NB * 64) reinterpret_cast<sf4 *>(s_w[buf])[tid + q * SCV_T] = r.w[q];
+            if (tid + q * SCV_T < NB * 64) reinterpret_cast<f4 *>(s_w[buf])[tid + q * SCV_T] = r.w[q];
     };
     // the loads run ahead of the MFMAs: a cursor over (present offset, 16-channel block) in ascending order
     unsigned rem = mask;
@@ -108,11 +98,11 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
         }
     };
 
-    sf4 acc[NB], sum[SPLIT ? NB : 1];       // SPLIT: acc holds the current offset's products, sum the offsets before it
+    f4 acc[NB], sum[SPLIT ? NB : 1];       // SPLIT: acc holds the current offset's products, sum the offsets before it
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) acc[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+    for (int nb = 0; nb < NB; ++nb) acc[nb] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int nb = 0; nb < (SPLIT ? NB : 1); ++nb) sum[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+    for (int nb = 0; nb < (SPLIT ? NB : 1); ++nb) sum[nb] = f4{0.f, 0.f, 0.f, 0.f};
     int kb_of_step = 0;
 
     Regs regs{};
@@ -130,21 +120,18 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     sum[nb] += acc[nb];
-                    acc[nb] = sf4{0.f, 0.f, 0.f, 0.f};
+                    acc[nb] = f4{0.f, 0.f, 0.f, 0.f};
                 }
             }
             ++kb_of_step;
         }
-        const sf4 fb = *reinterpret_cast<const sf4 *>(&s_x[cur][(16 * wave + pos) * SCV_HS + 4 * g]);
-        sf4 fa[NB];
+        const f4 fb = b_frag(s_x[cur], 16 * wave + pos, MFMA_ROW_STRIDE, 0, g);
+        f4 fa[NB];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) fa[nb] = reinterpret_cast<const sf4 *>(s_w[cur])[nb * 64 + lane];
+        for (int nb = 0; nb < NB; ++nb) fa[nb] = a_frag(s_w[cur], nb, lane);
         if (s + 1 < steps) stage(cur ^ 1, regs);        // that stage was last read in step s - 1, behind the barrier
         if (s + 2 < steps) { regs = load(lk, lkb); advance(); }
-#define PDM_SCV_MFMA(C) \
-    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[nb].C, fb.C, acc[nb], 0, 0, 0);
-        PDM_SCV_MFMA(x) PDM_SCV_MFMA(y) PDM_SCV_MFMA(z) PDM_SCV_MFMA(w)
-#undef PDM_SCV_MFMA
+        mfma4_grid(acc, fa, fb);
         __syncthreads();
     }
 
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = sum[nb] + acc[nb];
     }
-    // lane (pos, g), register j of block nb = out[r0 + 16 wave + pos][16 nb + 4 g + j]
+    // D layout of mfma_f32.h: row r0 + 16 wave + pos
     const int lrow = 16 * wave + pos;
     if (lrow >= live) return;
     const size_t row = (size_t)(r0 + lrow);
@@ -161,32 +148,9 @@ __global__ __launch_bounds__(SCV_T) void sparse_conv_kernel(ScvArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int c0 = 16 * nb + 4 * g;
-        float v[4] = {acc[nb].x, acc[nb].y, acc[nb].z, acc[nb].w};
-        if (a.scale) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = __fmaf_rn(v[j], a.scale[c0 + j], a.shift[c0 + j]);
-        }
-        if (a.residual) {
-            const float *rp = a.residual + row * a.cout + c0;
-            if (vec_r) {
-                const sf4 r = *reinterpret_cast<const sf4 *>(rp);
-                v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] += rp[j];
-            }
-        }
-        if (a.relu) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = v[j] < 0.0f ? 0.0f : v[j];      // a NaN stays, as torch's ReLU keeps it
-        }
-        float *op = a.out + row * a.cout + c0;
-        if (vec_o) {
-            *reinterpret_cast<sf4 *>(op) = sf4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) op[j] = v[j];
-        }
+        f4 v = scale_shift_relu4(acc[nb], a.scale, a.shift, c0, false);
+        if (a.residual) v += load_quad(a.residual + row * a.cout + c0, vec_r);
+        store_quad(a.out + row * a.cout + c0, scale_shift_relu4(v, nullptr, nullptr, c0, a.relu), vec_o);
     }
 }
 

@@ -14,11 +14,9 @@
 // z = (Cout sub-block) * (Cin sub-blocks) + (Cin sub-block): a sub-block reads its 128 columns of dy and of x at a column offset
 // with the full row strides and writes its corner of the same [chunk][k][Cout][Cin] partial.  Every partial element has one
 // writer and the same chain over the rows as a narrow run on those columns; phase two is unchanged.
-#include "common.h"
+#include "mfma_f32.h"
 
 namespace pdm {
-
-typedef float wf4 __attribute__((ext_vector_type(4)));
 
 constexpr int SCW_T = 256;                          // 4 waves
 constexpr int SCW_MAXK = 27;
@@ -81,11 +79,11 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
     const bool vec_dy = (reinterpret_cast<uintptr_t>(a.dy) & 15) == 0;
     const bool vec_x = (a.cin & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
 
-    wf4 acc[NCB][NIB];
+    f4 acc[NCB][NIB];
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
 #pragma unroll
-        for (int i = 0; i < NIB; ++i) acc[c][i] = wf4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NIB; ++i) acc[c][i] = f4{0.f, 0.f, 0.f, 0.f};
 
     for (long long r0 = c0; r0 < c1; r0 += ROWS) {
         const int live = (int)min((long long)ROWS, c1 - r0);
@@ -99,33 +97,16 @@ __global__ __launch_bounds__(SCW_T) void sparse_conv_wgrad_kernel(ScwArgs a) {
         if (!__syncthreads_or(r >= 0)) continue;
         for (int q = tid; q < ROWS * CB * 4; q += SCW_T) {
             const int row = q / (4 * CB), c = 4 * (q % (4 * CB));
-            wf4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < live) {
-                const float *p = a.dy + (size_t)(r0 + row) * a.cout + co0 + c;
-                if (vec_dy) {
-                    v = *reinterpret_cast<const wf4 *>(p);
-                } else {
-                    v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3];
-                }
-            }
-            *reinterpret_cast<wf4 *>(&s_dy[row * SD + c]) = v;
+            f4 v = {0.f, 0.f, 0.f, 0.f};
+            if (row < live) v = load_quad(a.dy + (size_t)(r0 + row) * a.cout + co0 + c, vec_dy);
+            *reinterpret_cast<f4 *>(&s_dy[row * SD + c]) = v;
         }
         for (int q = tid; q < ROWS * IB * 4; q += SCW_T) {
             const int row = q / (4 * IB), c = 4 * (q % (4 * IB));
-            wf4 v = {0.f, 0.f, 0.f, 0.f};
+            f4 v = {0.f, 0.f, 0.f, 0.f};
             const int rr = s_nbr[row];
-            if (rr >= 0) {
-                const float *p = a.x + (size_t)rr * a.cin + ci0 + c;
-                if (vec_x && ci0 + c + 4 <= a.cin) {
-                    v = *reinterpret_cast<const wf4 *>(p);
-                } else {
-                    if (ci0 + c < a.cin) v.x = p[0];
-                    if (ci0 + c + 1 < a.cin) v.y = p[1];
-                    if (ci0 + c + 2 < a.cin) v.z = p[2];
-                    if (ci0 + c + 3 < a.cin) v.w = p[3];
-                }
-            }
-            *reinterpret_cast<wf4 *>(&s_x[row * SX + c]) = v;
+            if (rr >= 0) v = load_quad_ragged(a.x + (size_t)rr * a.cin + ci0 + c, ci0 + c, a.cin, vec_x);
+            *reinterpret_cast<f4 *>(&s_x[row * SX + c]) = v;
         }
         __syncthreads();
         if (active) {

@@ -17,15 +17,13 @@
 // from the data first, and the partials (chunks x R x Cout floats) are small beside the weight.
 #include <algorithm>
 
-#include "common.h"
 #include "fc_reduce.h"
+#include "mfma_f32.h"
 
 namespace pdm {
 
 constexpr int FC_NT = 256;
 constexpr int FC_ACC_FLOATS = 16384;   // the LDS accumulator: TR = min(128, 16384 / Cout) boxes
-constexpr int FC_TARGET_WGS = 1024;    // workgroups the (tile, chunk) grid aims at
-typedef float fc4 __attribute__((ext_vector_type(4)));
 
 struct FcPlan {
     int TR, tiles, chunk_cells, nchunk;
@@ -35,9 +33,9 @@ static FcPlan fc_plan(int R, int cells, int Cout) {
     FcPlan p;
     p.TR = std::min(128, FC_ACC_FLOATS / Cout);
     p.tiles = divup(std::max(R, 1), p.TR);
-    const int want = std::min(cells, std::max(1, divup(FC_TARGET_WGS, p.tiles)));
-    p.chunk_cells = divup(cells, want);
-    p.nchunk = divup(cells, p.chunk_cells);
+    const SplitK k = split_k_plan(cells, p.tiles);
+    p.chunk_cells = k.chunk;
+    p.nchunk = k.nchunk;
     return p;
 }
 
@@ -152,32 +150,25 @@ __global__ __launch_bounds__(FC_NT) void fc_main_kernel(FcArgs a) {
             __syncthreads();   // the accumulator's zero fill; the previous tile's reads of xs and s_box
             for (int e = tid; e < 16 * (C / 4); e += FC_NT) {
                 const int row = e / (C / 4), c4 = 4 * (e % (C / 4));
-                fc4 v = {0.f, 0.f, 0.f, 0.f};
+                f4 v = {0.f, 0.f, 0.f, 0.f};
                 if (row < m) {
                     const size_t q = (size_t)a.cell_rows[g0 + row];
-                    v = c4 < a.Ca ? *reinterpret_cast<const fc4 *>(a.xa + q * a.Ca + c4)
-                                  : *reinterpret_cast<const fc4 *>(a.xb + q * a.Cb + (c4 - a.Ca));
+                    v = c4 < a.Ca ? *reinterpret_cast<const f4 *>(a.xa + q * a.Ca + c4)
+                                  : *reinterpret_cast<const f4 *>(a.xb + q * a.Cb + (c4 - a.Ca));
                 }
-                *reinterpret_cast<fc4 *>(xs + row * XS + c4) = v;
+                *reinterpret_cast<f4 *>(xs + row * XS + c4) = v;
             }
             if (tid < 16) s_box[tid] = tid < m ? a.coords[(size_t)a.cell_rows[g0 + tid] * 4] - r_lo : -1;
             __syncthreads();
             const int box = s_box[pos];
             for (int nb = wave; nb < NB; nb += FC_NT / 64) {
-                fc4 d = {0.f, 0.f, 0.f, 0.f};
-                const fc4 *wp = reinterpret_cast<const fc4 *>(a.wpack) + ((size_t)cell * KB * NB + nb) * 64 + lane;
-                for (int kb = 0; kb < KB; ++kb) {
-                    const fc4 fa = wp[(size_t)kb * NB * 64];
-                    const fc4 fb = *reinterpret_cast<const fc4 *>(xs + pos * XS + 16 * kb + 4 * g);
-                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb.x, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb.y, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb.z, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb.w, d, 0, 0, 0);
-                }
-                // lane (pos, g), register j = row pos, channel 16 nb + 4 g + j.  A wave owns its channel blocks for the whole
-                // walk and the rows of a cell are distinct boxes: every accumulator element is one wave's, in program order
+                f4 d = {0.f, 0.f, 0.f, 0.f};
+                for (int kb = 0; kb < KB; ++kb)
+                    d = mfma4(d, a_frag(a.wpack, ((size_t)cell * KB + kb) * NB + nb, lane), b_frag(xs, pos, XS, kb, g));
+                // D layout of mfma_f32.h, row pos.  A wave owns its channel blocks for the whole walk and the rows of a cell
+                // are distinct boxes: every accumulator element is one wave's, in program order
                 if ((unsigned)box < (unsigned)a.TR) {
-                    fc4 *o = reinterpret_cast<fc4 *>(acc + box * a.Cout + 16 * nb + 4 * g);
+                    f4 *o = reinterpret_cast<f4 *>(acc + box * a.Cout + 16 * nb + 4 * g);
                     *o = *o + d;
                 }
             }

@@ -65,11 +65,9 @@ def pack_layer(w, shift):
     cp, kp = _pad16(cout), _pad16(cin)
     wp = np.zeros((cp, kp), dtype=np.float32)
     wp[:cout, :cin] = w
-    # [mb][oc][kb][g][s] -> [mb][kb][g][oc][s]; lane = g*16 + oc
-    packed = wp.reshape(cp // 16, 16, kp // 16, 4, 4).transpose(0, 2, 3, 1, 4)
     bp = np.zeros(cp, dtype=np.float32)
     bp[:cout] = shift
-    return np.ascontiguousarray(packed).reshape(-1), bp, kp, cp
+    return _native.mfma_a_fragments(torch.from_numpy(wp)).reshape(-1).numpy(), bp, kp, cp      # [mb][kb][lane][s]
 
 
 class PackedMLP:

@@ -272,10 +272,9 @@ def pack_weight(weight, wide=False):
     cout, cin = weight.shape[0], weight.shape[-1]
     _check_widths(cin, cout, wide)
     w = weight.detach().float().reshape(cout, -1, cin)
-    kvol, nkb, nb = w.shape[1], (cin + 15) // 16, cout // 16
-    w = torch.nn.functional.pad(w, (0, 16 * nkb - cin))                        # (cout, kvol, 16 nkb)
-    w = w.reshape(nb, 16, kvol, nkb, 4, 4).permute(2, 3, 0, 4, 1, 5)           # (kvol, nkb, nb, g, i, j)
-    out = w.contiguous().reshape(-1)
+    kvol = w.shape[1]
+    w = torch.nn.functional.pad(w, (0, -cin % 16))                              # (cout, kvol, 16 nkb)
+    out = _native.mfma_a_fragments(w.transpose(0, 1)).transpose(1, 2).reshape(-1)      # (kvol, nkb, nb, lane, j)
     assert out.numel() == _native.lib().pdm_sparse_conv_packed_floats(kvol, cin, cout)
     return out
 
@@ -468,8 +467,7 @@ def pack_fc_weight(weight, cells):
     C = w.shape[1] // cells
     if w.shape[1] != C * cells or C % 16 or cout % 16:
         raise ValueError(f'sparse_fc: weight {tuple(weight.shape)} over {cells} cells; C and Cout must be multiples of 16')
-    w = w.reshape(cout // 16, 16, C // 16, 4, 4, cells).permute(5, 2, 0, 3, 1, 4)          # (cell, kb, nb, g, i, j)
-    out = w.contiguous().reshape(-1)
+    out = _native.mfma_a_fragments(w.reshape(cout, C, cells).permute(2, 0, 1)).transpose(1, 2).reshape(-1)     # (cell, kb, nb, lane, j)
     assert out.numel() == _native.lib().pdm_sparse_fc_packed_floats(cells, C, cout)
     return out
 

@@ -34,7 +34,7 @@ def _sa_row(i, cin, mlps, nsamples):
 SA_REG_EDGES = [
     pytest.param(13, [[13, 16, 16, 32]], [16], 2, 1500, 200, True, id="reg-k0-full"),            # 3 + cin == 16: no zero padding in K0
     pytest.param(0, [[0, 32, 32, 64]], [32], 2, 1500, 200, True, id="reg-xyz-only-wide"),        # <2, 2, 4>, SAME
-    # odd widths below the padded ones.  (cout = 30 would reach the guarded tail of sa_reg_store4, but the module only takes its fused
+    # odd widths below the padded ones.  (cout = 30 would reach the guarded tail of store_quad_ragged, but the module only takes its fused
     # path when cout % 4 == 0 — pointnet2_modules.py, _forward — so no width that is not a multiple of 4 gets there from Python.)
     pytest.param(5, [[5, 12, 10, 28]], [16], 2, 1500, 200, True, id="reg-odd-widths"),
     pytest.param(1, [[1, 16, 16, 32]], [48], 2, 1500, 200, True, id="reg-ns48"),                 # 3 tiles: the second sub-step's second tile is dead

@@ -1498,6 +1498,40 @@ int pdm_bev_roi_crop_fc(void *stream, int B, int n, int roi_stride, const float 
                         float x0, float y0, float cell_x, float cell_y, int G, int Cout, const float *wpack, const float *scale,
                         const float *shift, int relu, float *out, void *workspace, size_t workspace_bytes);
 
+/* ---- DSVT: the set partition of one stage and the fused set attention (csrc/dsvt.hip) ----------------------------------------
+ * pdm_dsvt_partition_count, then pdm_dsvt_partition with the same geometry and workspace: voxel_coords (N, 4) int32 (b, z, y, x),
+ *   distinct voxels in any row order on the sparse shape (sx, sy, sz) of B samples; windows[6] = the window (wx, wy, wz) of shift 0
+ *   and of shift 1, shifts[6] = the two shift vectors (x, y, z), 0 <= shift <= window (host arrays; the z shift counts as 0 where
+ *   the window spans z); set_size >= 1.  A voxel lies in window ((b MX + X / wx) MY + Y / wy) MZ + Z / wz with (X, Y, Z) = (x, y, z) +
+ *   shift and M* = ceil(shape / w) + 1; occupied windows are numbered in ascending order of that id, a window of n voxels gets
+ *   ceil(n / set_size) sets, and slot k of its sets holds its voxel number floor(k n / (sets set_size)) under the key
+ *   (iy wx + ix) wz + iz (axis 0) or (ix wy + iy) wz + iz (axis 1) of the in-window position.
+ *   _count: coors_in_win (2, N, 3) int32 (z, y, x in the window, per shift) and set_counts[2] (HOST) = the sets of each shift,
+ *   after ONE host read (the call synchronises the stream).  A coordinate outside the sparse shape is PDM_E_BADARG, found on
+ *   the device and reported by this call.  workspace >= pdm_dsvt_partition_workspace_bytes(...) (0 for sizes the calls refuse),
+ *   8-byte aligned; a window volume the workspace was not sized for is PDM_E_BADARG.
+ *   pdm_dsvt_partition: set_voxel_inds{0,1} (2, S_shift, set_size) int64 and set_voxel_mask{0,1} (2, S_shift, set_size) bytes
+ *   (1 = the slot equals its left neighbour in the set), every element written once, by one thread: two runs give the same bits.
+ *   One launch, no host read.  No sort, no hash, no float atomics, no cursors: an occupancy bitmap and two tiled scans.
+ * pdm_set_attention: q, k, v (N, C) fp32, each with its own ROW stride in elements (>= C; the thirds of one (N, 3C) buffer serve),
+ *   set_voxel_inds (S, set_size) int64 -> out (N, C) contiguous: for every set and head softmax(q_h k_h^T / sqrt(d) + mask) v_h over
+ *   the set's rows, written at the row of every slot that differs from its left neighbour; a slot that equals it is masked as a
+ *   key and skipped as a query (the mask is derived from the indices, not read).  Rows that no set names are not written.
+ *   d = C / nheads in {16, 24, 32}, C <= 256, 1 <= set_size <= 128; anything else is PDM_E_BADARG.  Indices are clamped into
+ *   [0, N).  One launch, one wave per (set, head), both products on mfma_f32_16x16x4f32, no workspace, no LDS, no atomics: two
+ *   runs give the same bits; capturable in a graph. */
+/* align: any (4-byte accesses; 16-byte ones only where the pointers and strides allow), except set_voxel_inds and the workspace: 8 B
+ * (PDM_E_BADARG otherwise). */
+size_t pdm_dsvt_partition_workspace_bytes(int N, int B, int sx, int sy, int sz, const int *windows);
+int pdm_dsvt_partition_count(void *stream, int N, const int *voxel_coords, int B, int sx, int sy, int sz, const int *windows,
+                             const int *shifts, int set_size, int *coors_in_win, int *set_counts, void *workspace, size_t workspace_bytes);
+int pdm_dsvt_partition(void *stream, int N, const int *voxel_coords, int B, int sx, int sy, int sz, const int *windows,
+                       const int *shifts, int set_size, int S0, int S1, long long *set_voxel_inds0, unsigned char *set_voxel_mask0,
+                       long long *set_voxel_inds1, unsigned char *set_voxel_mask1, void *workspace, size_t workspace_bytes);
+int pdm_set_attention(void *stream, int S, int set_size, int N, int C, int nheads, const float *q, long long q_stride,
+                      const float *k, long long k_stride, const float *v, long long v_stride, const long long *set_voxel_inds,
+                      float *out);
+
 /* Diagnostics: *slot = the device's constant-rate counter (100 MHz) when `stream` reaches this point. */
 int pdm_mark_time(void *stream, unsigned long long *slot);
 

@@ -555,3 +555,47 @@ def build_transfusion_lidar(model_cfg=None, num_point_features=5, dataset=None):
     cfg = cfg_from_dict(copy.deepcopy(TRANSFUSION_LIDAR_CFG if model_cfg is None else model_cfg))
     dataset = transfusion_dataset(num_point_features) if dataset is None else dataset
     return build_network(cfg, num_class=len(dataset.class_names), dataset=dataset)
+
+
+# DSVT-Pillar: DynamicPillarVFE -> DSVT -> PointPillarScatter3d -> BaseBEVResBackbone -> CenterHead under the CenterPoint
+# detector.  The reference ships no yaml for it, so the values are build-defined, after the published pillar model: 192 channels in
+# 8 heads (d = 24), sets of 36, one stage of 4 blocks, 12 x 12 x 1 windows with hybrid factor 2 x 2 x 1, a 468 x 468 x 1 grid of
+# 0.32 m pillars, FFN 384 with gelu.  The head is CENTER_PDM_CFG's on the backbone's stride-1 map.  Eval only for the fused
+# operators; CenterHead's iou branch, USE_IOU_TO_RECTIFY_SCORE and class_specific_nms are not built.
+DSVT_RANGE = [-74.88, -74.88, -2, 74.88, 74.88, 4.0]
+DSVT_VOXEL_SIZE = [0.32, 0.32, 6]
+DSVT_GRID_SIZE = [468, 468, 1]
+DSVT_PILLAR_CFG = {
+    'NAME': 'CenterPoint',
+    'VFE': {'NAME': 'DynamicPillarVFE', 'USE_NORM': True, 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'NUM_FILTERS': [192, 192]},
+    'BACKBONE_3D': {'NAME': 'DSVT',
+                    'INPUT_LAYER': {'sparse_shape': [468, 468, 1], 'downsample_stride': [], 'd_model': [192], 'set_info': [[36, 4]],
+                                    'window_shape': [[12, 12, 1]], 'hybrid_factor': [2, 2, 1], 'shifts_list': [[[0, 0, 0], [6, 6, 0]]],
+                                    'normalize_pos': False},
+                    'block_name': ['DSVTBlock'], 'set_info': [[36, 4]], 'd_model': [192], 'nhead': [8], 'dim_feedforward': [384],
+                    'dropout': 0.0, 'activation': 'gelu', 'output_shape': [468, 468], 'conv_out_channel': 192},
+    'MAP_TO_BEV': {'NAME': 'PointPillarScatter3d', 'INPUT_SHAPE': [468, 468, 1], 'NUM_BEV_FEATURES': 192},
+    'BACKBONE_2D': {'NAME': 'BaseBEVResBackbone', 'LAYER_NUMS': [1, 2, 2], 'LAYER_STRIDES': [1, 2, 2], 'NUM_FILTERS': [128, 128, 256],
+                    'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [128, 128, 128]},
+    'DENSE_HEAD': copy.deepcopy(CENTER_PDM_CFG['DENSE_HEAD']),
+    'POST_PROCESSING': copy.deepcopy(CENTER_PDM_CFG['POST_PROCESSING']),
+}
+DSVT_PILLAR_CFG['DENSE_HEAD']['TARGET_ASSIGNER_CONFIG']['FEATURE_MAP_STRIDE'] = 1
+DSVT_PILLAR_CFG['DENSE_HEAD']['POST_PROCESSING']['POST_CENTER_LIMIT_RANGE'] = [-80, -80, -10.0, 80, 80, 10.0]
+
+
+def dsvt_dataset(num_point_features=4, point_cloud_range=None, voxel_size=None, grid_size=None):
+    """DSVT-Pillar's dataset namespace: a 149.76 m square of 0.32 m pillars over the whole height unless other values are given."""
+    return SimpleNamespace(class_names=CLASS_NAMES, grid_size=list(DSVT_GRID_SIZE if grid_size is None else grid_size),
+                           voxel_size=list(DSVT_VOXEL_SIZE if voxel_size is None else voxel_size),
+                           point_cloud_range=list(DSVT_RANGE if point_cloud_range is None else point_cloud_range),
+                           point_feature_encoder=SimpleNamespace(num_point_features=num_point_features))
+
+
+def build_dsvt_pillar(model_cfg=None, num_point_features=4, dataset=None):
+    """CenterPoint from DSVT_PILLAR_CFG (or a dict like it): DynamicPillarVFE -> DSVT -> PointPillarScatter3d ->
+    BaseBEVResBackbone -> CenterHead, on dsvt_dataset() unless another dataset namespace is given.  The backbone's sparse_shape
+    and the scatter's INPUT_SHAPE must be the dataset's grid."""
+    from .detectors import build_network
+    cfg = cfg_from_dict(copy.deepcopy(DSVT_PILLAR_CFG if model_cfg is None else model_cfg))
+    return build_network(cfg, num_class=len(CLASS_NAMES), dataset=dsvt_dataset(num_point_features) if dataset is None else dataset)

@@ -1070,6 +1070,7 @@ int pdm_tune_rows_chain_wg_per_cu(int n); /* grid cap of the many-row chain kern
 int pdm_tune_fp_head_tiles(int n);           /* pdm_fp_head_fused: consecutive 64-row tiles per workgroup (default 2) */
 int pdm_tune_rows_chain_dw_wg_per_cu(int n); /* the same for pdm_bev_head_fused (default 2: every workgroup resident from the start) */
 int pdm_tune_rows_chain_xcd(int on);   /* heat-map chain kernel: contiguous patch range per XCD (default) / launch order */
+int pdm_tune_bev_head_form(int form);  /* pdm_bev_head_fused: 0 every wave runs prologue and chain, 1 depthwise producer waves beside MFMA consumer waves (128 -> 64 -> 64 -> <= 16 only; other shapes take form 0) */
 int pdm_tune_fp_chain_pad_lds(int bytes); /* diagnostic: extra LDS per workgroup of the FP chain kernel (occupancy experiments) */
 int pdm_tune_fp_chain_nt(int on);      /* FP chain kernel: non-temporal output stores (default off) */
 int pdm_tune_fp_chain_mask(int m);     /* which FP shapes take the register-resident chain kernel: bits 0-1 (default 2); m < 0 only reads */

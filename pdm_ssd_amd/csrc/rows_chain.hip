@@ -959,6 +959,10 @@ int rows_chain_pair_launch(void *stream, int rows, int cin, const float *in_pm, 
     return 0;
 }
 
+int bev_head_roles_launch(void *stream, int B, int H, int W, int C, const float *map, const float *dw_w, const float *dw_shift,
+                          int nlayers, const int *dims, const float *wpack, const float *bias, int relu_last, float *out_pm,
+                          int out_stride, int cout, int grid_cap, int by_xcd, int *launched);   // bev_head_roles.hip
+
 // The heat-map head's whole stack in one launch: depthwise 3x3 (+ folded BN + ReLU) as the chain's prologue.
 // Returns 1 in *launched when an instantiation fits.
 int rows_chain_dw_launch(void *stream, int B, int H, int W, int C, const float *map, const float *dw_w, const float *dw_shift,
@@ -979,6 +983,10 @@ int rows_chain_dw_launch(void *stream, int B, int H, int W, int C, const float *
     a.dw_H = H; a.dw_W = W; a.dw_by_xcd = g_rc_dw_xcd; a.dw_w = dw_w; a.dw_shift = dw_shift;
     const long long tiles = (long long)B * ((H + 3) / 4) * ((W + 15) / 16);
     const int grid = (int)(tiles < 256 * g_rc_dw_wg_per_cu ? tiles : 256 * g_rc_dw_wg_per_cu);
+    // pdm_tune_bev_head_form(1): producer and consumer waves (bev_head_roles.hip); shapes it is not written for come back here
+    const int rrc = bev_head_roles_launch(stream, B, H, W, C, map, dw_w, dw_shift, nlayers, dims, wpack, bias, relu_last, out_pm, out_stride,
+                                          cout, g_rc_dw_wg_per_cu, g_rc_dw_xcd, launched);
+    if (rrc || *launched) return rrc;
     if (rc_shape_is(nlayers, dims, 8, 4, 4, 1)) {
         hipLaunchKernelGGL((rows_chain_kernel<8, 4, 4, 1, true>), dim3(grid), dim3(RC_THREADS), 0, as_stream(stream), a);
         *launched = 1;

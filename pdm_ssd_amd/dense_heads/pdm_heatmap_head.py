@@ -94,6 +94,12 @@ class _DepthwiseConv3x3(nn.Conv2d):
 
 # 1 (default): under bf16 autocast in training the depthwise convolution hands on a bf16 map (see _Depthwise3x3CL)
 DEPTHWISE_BF16_OUT = os.environ.get("PDM_DEPTHWISE_BF16_OUT", "1") == "1"
+# which kernel pdm_bev_head_fused launches (pdm_tune_bev_head_form): 0 every wave runs the depthwise prologue and the chain,
+# 1 depthwise producer waves beside MFMA consumer waves (csrc/bev_head_roles.hip); identical logits
+# unset: the library's own default
+if "PDM_BEV_HEAD_FORM" in os.environ:
+    from .. import _native as _native_for_form
+    _native_for_form.lib().pdm_tune_bev_head_form(int(os.environ["PDM_BEV_HEAD_FORM"]))
 
 
 class PDMHeatmapHead(nn.Module):

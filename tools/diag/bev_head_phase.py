@@ -6,6 +6,41 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from pdm_ssd_amd import _native
+if "--roles" in sys.argv:
+    # the role-split form (bev_head_roles_kernel, pdm_tune_bev_head_form(1)): libbr_diag.so of the same make target stamps one
+    # consumer wave and one producer wave on each workgroup's third tile.  MFMA floor per tile with ONE consumer wave per
+    # SIMD: 32 cycles x 208 MFMAs = 6656 cycles.
+    _native.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libbr_diag.so")
+    from pdm_ssd_amd.detector_config import build_pdm_ssd
+    dev = torch.device("cuda:0")
+    head = build_pdm_ssd().to(dev).eval().dense_head
+    l = _native.lib()
+    l.pdm_tune_bev_head_form(1)
+    cap = int(sys.argv[sys.argv.index("--cap") + 1]) if "--cap" in sys.argv else l.pdm_tune_rows_chain_dw_wg_per_cu(0)
+    l.pdm_tune_rows_chain_dw_wg_per_cu(cap)
+    sf = torch.randn(32, 188, 188, 128, device=dev).permute(0, 3, 1, 2)
+    with torch.no_grad():
+        for _ in range(100):
+            logits = head._fused_logits(sf)
+        torch.cuda.synchronize()
+    buf = logits
+    while buf._base is not None:
+        buf = buf._base
+    nwg = 256 * cap
+    ts = buf.contiguous().view(-1).view(torch.int64)[: nwg * 16].view(nwg, 16).cpu()
+
+    def table(title, cols, names):
+        print(title)
+        for (i, j), nm in zip(cols, names):
+            d = (ts[:, j] - ts[:, i]).double()
+            print(f"  {nm:58s} {float(d.mean()):8.0f}  (min {int(d.min())}, max {int(d.max())})")
+    table(f"consumer wave 0, third tile of a workgroup (grid 256 x {cap}):", [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (5, 6), (0, 6)],
+          ["input fragments from the LDS tile", "layer 1 (128 MFMAs, floor 4096)", "layer 2 (64 MFMAs, floor 2048)",
+           "layer 3 (16 MFMAs, floor 512)", "stores", "barrier (waits for the producers)", "whole tile"])
+    table("producer wave 4, same iteration:", [(8, 9), (9, 10), (10, 11), (8, 11)],
+          ["wait for the halo requested ahead + taps + tile write", "request of the next halo (issue only)",
+           "barrier (waits for the consumers)", "whole iteration"])
+    sys.exit(0)
 _native.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librc_diag4.so")
 from pdm_ssd_amd.detector_config import build_pdm_ssd
 dev = torch.device("cuda:0")

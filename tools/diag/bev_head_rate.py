@@ -27,6 +27,18 @@ with torch.no_grad():
         print(f"heat-map head, patches by XCD range = {on}: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us", flush=True)
 l.pdm_tune_rows_chain_xcd(1)
 with torch.no_grad():
+    # the two forms (pdm_tune_bev_head_form: 0 one role, 1 producer and consumer waves) alternately, at grid caps 1 and 2
+    for form, n in ((0, 2), (1, 1), (1, 2), (0, 2), (1, 1), (1, 2), (0, 1)):
+        oldf, old = l.pdm_tune_bev_head_form(form), l.pdm_tune_rows_chain_dw_wg_per_cu(n)
+        m.dense_head({'spatial_features': sf}); torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20): m.dense_head({'spatial_features': sf})
+        e1.record(); torch.cuda.synchronize()
+        print(f"heat-map head, form {form}, grid = 256 x {n} workgroups: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us", flush=True)
+        l.pdm_tune_bev_head_form(oldf); l.pdm_tune_rows_chain_dw_wg_per_cu(old)
+    if "--forms-only" in sys.argv:
+        sys.exit(0)
     for n in (2, 3, 4, 6, 8, 12, 24):        # grid cap = 256 CUs x n workgroups (two resident per CU)
         old = l.pdm_tune_rows_chain_dw_wg_per_cu(n)
         m.dense_head({'spatial_features': sf}); torch.cuda.synchronize()
